@@ -2,6 +2,7 @@
 """Benchmark of the embedding + match hot path (BASELINE.json metric: faces/sec).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload r100_1m|r50|r100|r100_arc|frames|frames_mtcnn]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,14 +15,19 @@ Default workload = the configuration BASELINE.json's metric is quoted on ("512-d
 configs[3]'s per-GPU shape): IResNet-100, 512 faces per GPU, a 1M-row gallery (row-sharded for
 N > 1).  `--workload r50` is configs[1] (ResNet-50V2+GDC, batch 256, 100k gallery).  Weak
 scaling: the per-GPU batch is fixed, the gallery is fixed in total and row-sharded, so both the
-embed and the match work per GPU stay constant as N grows.  The same process also times the
-IResNet-100 forward at batch 256 (north_star states its >= 70 % MFMA target there) and reports
-it as `roofline.b256`.
+embed and the match work per GPU stay constant as N grows.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (the
-convolution kernel family against the f32 MFMA peak) and, at N=1, `cpu_baseline` (the CPU
-oracle = a port of the reference's algorithm, timed on this host's cores on a bounded
-sample).
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0 (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, `phases_ms`).
+`--dump-outputs DIR` writes what the last timed step computed (embeddings, matched gallery rows and
+distances; boxes of the frame workloads, a row sample of the ArcMargin logits) to DIR/<name>.npy;
+the inputs depend on the arguments only, so two builds can be compared output for output.
+
+`--full` adds, after the timed steps: the self-check (`verified`), the small-batch `latency` block,
+the IResNet-100 forward at batch 256 (north_star states its >= 70 % MFMA target there:
+`roofline.b256`), `roofline` (the convolution kernel family against the f32 MFMA peak, from a
+profiled forward), the split-bf16 `throughput_mode` tiers and, at N=1, `cpu_baseline` (the CPU
+oracle = a port of the reference's algorithm, timed on this host's cores on a bounded sample).
 """
 import argparse
 import json
@@ -345,6 +351,28 @@ def cpu_baseline_frames(gallery_rows, det_params, n_frames=4):
                       'decode/NMS/crop + reference-formula match vs %d rows, %.2fs' % (n_frames, cores, gallery_rows, dt)}
 
 
+DUMP_BYTES = 60_000_000          # --dump-outputs: the files of one run stay below 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as <path>/<name>.npy, integers and float64 as float64, other
+    floats as float32.  An array larger than its share of DUMP_BYTES is cut to a fixed sample of its rows (seed 0, sorted),
+    whose indices go to <path>/<name>_rows.npy: the same arguments give the same sample on every run."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        wide = not t.is_floating_point() or t.dtype == torch.float64
+        n = int(t.shape[0]) if t.dim() else 1
+        row_bytes = (8 if wide else 4) * (t[0].numel() if t.dim() and n else 1)
+        if t.dim() and n * row_bytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, share // (row_bytes + 8)), replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+            np.save(os.path.join(path, name + '_rows.npy'), rows.astype(np.float64))
+        a = t.cpu().numpy().astype(np.float64 if wide else np.float32)
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: this process becomes the parent of one
     torch.distributed.run job (one child per GPU) and only relays its output and exit code.  It has made
@@ -372,9 +400,16 @@ def main():
     ap.add_argument('--workload', default='r100_1m', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=0, help='per-GPU batch override')
     ap.add_argument('--gallery', type=int, default=0, help='total gallery rows override')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-throughput-mode', action='store_true', help='skip the extra split-bf16 forward timing')
-    ap.add_argument('--no-latency', action='store_true', help='skip the small-batch (1 / 8 / 12 / 32) forward latency block')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the self-check, the small-batch latency block, the batch-256 '
+                         'forward, the clock probes, the profiled forward (roofline), the split-bf16 tiers and the CPU '
+                         'baseline; a plain run only sets up, warms up, times the steps and prints the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-throughput-mode', action='store_true', help='with --full: skip the extra split-bf16 forward timing')
+    ap.add_argument('--no-latency', action='store_true',
+                    help='with --full: skip the small-batch (1 / 8 / 12 / 32) forward latency block')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='gloo = rehearsal of the N>1 path on a box with fewer GPUs than ranks (collectives staged '
                          'through the host, ranks share devices); never used for reported numbers')
@@ -382,6 +417,8 @@ def main():
                     help='N=1 only: initialise the process group (RCCL, one rank) and run both all-gathers and the packed '
                          'merge although a world of one needs none -- a rehearsal of the N>1 step on one GPU, not the headline')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -487,10 +524,13 @@ def main():
         frames = torch.randint(0, 256, (batch, 480, 640, 3), generator=g, dtype=torch.uint8).to(dev)
         det_ms = []
 
+    last = {}                                                 # what the latest step computed besides (idx, d): --dump-outputs
+
     def step_frames(i=None):
         if i is not None:
             ev[i][0].record()
-        boxes, _ = pipe.detect(frames)
+        boxes, scores = pipe.detect(frames)
+        last['boxes'], last['box_scores'] = boxes, scores
         faces = drun.crop_faces(frames, boxes, 8, 112)
         if i is not None:
             e_det = torch.cuda.Event(enable_timing=True)
@@ -513,7 +553,7 @@ def main():
         if i is not None:
             ev[i][1].record()
         if arc is not None:
-            arc.logits(emb, arc_labels)
+            last['arc_logits'] = arc.logits(emb, arc_labels)
         idx, d = shard.match(emb, 1, copy=False)
         if i is not None:
             ev[i][2].record()
@@ -540,26 +580,43 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # Self-check, after the timed region and never inside it: enrol 8 of this step's probes at known rows
-    # spread over the whole (sharded) gallery, run one more step through the same code path and require every
-    # rank to name exactly those rows.  A throughput line whose step computed something else fails here.
-    B_all = world * batch
-    emb_all = shard.all_gather_embeddings(emb_buf).clone()
-    n_plant = min(8, B_all, gallery_rows)                     # distinct probes at distinct rows
-    probe_ids = sorted({int(v) for v in np.linspace(0, B_all - 1, n_plant).round()})
-    plant_rows = sorted({int(v) for v in np.linspace(0, gallery_rows - 1, len(probe_ids)).round()})
-    probe_ids = probe_ids[:len(plant_rows)]
-    for pid, row in zip(probe_ids, plant_rows):
-        if lo <= row < hi:
-            shard.gallery.update(emb_all[pid:pid + 1], row - lo)   # O(1) per enrolment (dif_gallery_update), not a whole-gallery pass
-    idx_v, d_v = step()
-    torch.cuda.synchronize()
-    got = [int(idx_v[pid]) for pid in probe_ids]
-    dv = d_v[probe_ids].cpu().numpy()
-    verified = got == plant_rows and bool(np.all(np.isnan(dv) | (dv < 2e-3)))   # NaN: similarity rounded above 1, as in the reference
-    if not verified:
-        raise SystemExit('bench.py self-check FAILED on rank %d: planted rows %s, matched %s (dist %s)'
-                         % (rank, plant_rows, got, dv.tolist()))
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step, over all ranks, before anything below touches the gallery
+        def gathered(t):
+            if world == 1:
+                return t
+            out_t = torch.empty((world * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+            dist.all_gather_into_tensor(out_t, t.contiguous())
+            return out_t
+        outputs = {'embeddings': gathered(emb_buf), 'match_index': idx, 'match_distance': d}
+        for name in sorted(last):
+            outputs[name] = gathered(last[name])
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+        del outputs
+
+    verified = None
+    if args.full:
+        # Self-check, after the timed region and never inside it: enrol 8 of this step's probes at known rows
+        # spread over the whole (sharded) gallery, run one more step through the same code path and require every
+        # rank to name exactly those rows.  A throughput line whose step computed something else fails here.
+        B_all = world * batch
+        emb_all = shard.all_gather_embeddings(emb_buf).clone()
+        n_plant = min(8, B_all, gallery_rows)                     # distinct probes at distinct rows
+        probe_ids = sorted({int(v) for v in np.linspace(0, B_all - 1, n_plant).round()})
+        plant_rows = sorted({int(v) for v in np.linspace(0, gallery_rows - 1, len(probe_ids)).round()})
+        probe_ids = probe_ids[:len(plant_rows)]
+        for pid, row in zip(probe_ids, plant_rows):
+            if lo <= row < hi:
+                shard.gallery.update(emb_all[pid:pid + 1], row - lo)   # O(1) per enrolment (dif_gallery_update), not a whole-gallery pass
+        idx_v, d_v = step()
+        torch.cuda.synchronize()
+        got = [int(idx_v[pid]) for pid in probe_ids]
+        dv = d_v[probe_ids].cpu().numpy()
+        verified = got == plant_rows and bool(np.all(np.isnan(dv) | (dv < 2e-3)))   # NaN: similarity rounded above 1, as in the reference
+        if not verified:
+            raise SystemExit('bench.py self-check FAILED on rank %d: planted rows %s, matched %s (dist %s)'
+                             % (rank, plant_rows, got, dv.tolist()))
 
     embed_ms = float(np.mean([ev[i][0].elapsed_time(ev[i][1]) for i in range(args.steps)]))
     match_ms = float(np.mean([ev[i][1].elapsed_time(ev[i][2]) for i in range(args.steps)]))
@@ -582,7 +639,7 @@ def main():
     # the reference's own call shapes (predictions.py:152-156 embeds ONE image per call; scripts/insight_face.py:112 evaluates at
     # batch 12): forward latency at small batches, same model and weights, HIP events over back-to-back forwards
     latency = None
-    if pipe is None and compute == 'f32' and not args.no_latency:
+    if args.full and pipe is None and compute == 'f32' and not args.no_latency:
         latency = {}
         for lb in (1, 8, 12, 32):                               # 12: scripts/insight_face.py:112, the reference's evaluation batch
             if lb > batch:
@@ -611,7 +668,7 @@ def main():
     # north_star states its MFMA target "on the ResNet-100 embedding forward at batch 256": time that forward
     # too (same model, same lanes policy, HIP events on the launch stream), outside the step loop
     b256_ms = None
-    if pipe is None and arch.startswith('iresnet') and batch > 256:
+    if args.full and pipe is None and arch.startswith('iresnet') and batch > 256:
         reps = max(5, min(args.steps, 20))
         e256 = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(reps)]
         c256 = crops[:256]
@@ -624,6 +681,38 @@ def main():
         b256_ms = float(np.mean([a.elapsed_time(b) for a, b in e256]))
 
     if rank == 0:
+        out = {
+            'metric': 'faces/sec embedding+match (112x112, 512-d)' if pipe is None else
+                      'frames/sec detect+crop+embed+match (640x480 frames, one face per frame)',
+            'value': world * batch * args.steps / elapsed,
+            'unit': 'faces/s' if pipe is None else 'frames/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': elapsed / args.steps * 1e3,
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f32' if compute == 'f32' else ('bf16x3 (f32 operands split into 3 bf16 terms, 6 MFMA products, f32 accumulate)'
+                                                     if compute == 'bf16x3' else
+                                                     'bf16x2 (f32 operands split into 2 bf16 terms, 3 MFMA products, f32 accumulate)'),
+            'data': 'synthetic (uint8 crops seed 1234, He-normal weights seed 2024, unit-norm gallery seed 7)',
+            # what carried the collectives: under backend "nccl" (= RCCL on ROCm) rccl_ranks is the size of the communicator
+            'backend': (dist.get_backend() if grouped else None),
+            'rccl_ranks': (dist.get_world_size() if grouped and dist.get_backend() == 'nccl' else None),
+            'collectives_per_step': (2 if grouped else 0),
+            'config': {'workload': desc, 'arch': arch, 'head': head, 'batch_per_gpu': batch,
+                       'global_batch': world * batch, 'gallery_rows': gallery_rows,
+                       'gallery_rows_per_gpu': hi - lo, 'emd': 512, 'metric': 'cosine',
+                       'parallelism': 'dp%d + gallery row-shard' % world, 'backend': args.backend if grouped else None},
+            'forwards_in_process': {str(k): v for k, v in sorted(forwards.items())},
+            'phases_per_rank_ms': per_rank,
+            'phases_ms': (dict({'embed': embed_ms, 'match': match_ms}, **sub) if pipe is None else
+                          {'detect+crop': float(np.mean([ev[i][0].elapsed_time(det_ms[i]) for i in range(args.steps)])),
+                           'detect+crop+embed': embed_ms, 'match': match_ms}),
+            'full': args.full,      # False: no self-check, latency, roofline, split-bf16 tiers or CPU baseline (bench.py --full)
+        }
+    if rank == 0 and args.full:
         # the shader clock THIS box holds under back-to-back f32 MFMAs (boxes of the pool differ by a few percent)
         import ctypes
         from deep_insight_face import _native as N
@@ -655,37 +744,10 @@ def main():
         m_bytes = (hi - lo) * (1024.0 if filt == 1 else 2048.0) + world * batch * 2048.0
         m_roof_ms = max(m_flops / (m_ceiling * 1e12), m_bytes / (HBM_COPY_TBS * 1e12)) * 1e3
         e_roof_ms = flops_embed / (PEAK_F32_MFMA_TFLOPS * 1e12) * 1e3
-        out = {
-            'metric': 'faces/sec embedding+match (112x112, 512-d)' if pipe is None else
-                      'frames/sec detect+crop+embed+match (640x480 frames, one face per frame)',
-            'value': world * batch * args.steps / elapsed,
-            'unit': 'faces/s' if pipe is None else 'frames/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': elapsed / args.steps * 1e3,
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f32' if compute == 'f32' else ('bf16x3 (f32 operands split into 3 bf16 terms, 6 MFMA products, f32 accumulate)'
-                                                     if compute == 'bf16x3' else
-                                                     'bf16x2 (f32 operands split into 2 bf16 terms, 3 MFMA products, f32 accumulate)'),
-            'data': 'synthetic (uint8 crops seed 1234, He-normal weights seed 2024, unit-norm gallery seed 7)',
+        out.update({
             'verified': verified,       # after the timed region: 8 planted enrolments found at their rows by one more step
-            # what carried the collectives: under backend "nccl" (= RCCL on ROCm) rccl_ranks is the size of the communicator
-            'backend': (dist.get_backend() if grouped else None),
-            'rccl_ranks': (dist.get_world_size() if grouped and dist.get_backend() == 'nccl' else None),
-            'collectives_per_step': (2 if grouped else 0),
-            'config': {'workload': desc, 'arch': arch, 'head': head, 'batch_per_gpu': batch,
-                       'global_batch': world * batch, 'gallery_rows': gallery_rows,
-                       'gallery_rows_per_gpu': hi - lo, 'emd': 512, 'metric': 'cosine',
-                       'parallelism': 'dp%d + gallery row-shard' % world, 'backend': args.backend if grouped else None},
-            'forwards_in_process': {str(k): v for k, v in sorted(forwards.items())},
+            'forwards_in_process': {str(k): v for k, v in sorted(forwards.items())},   # the clock and profile forwards above included
             'latency': latency,
-            'phases_per_rank_ms': per_rank,
-            'phases_ms': (dict({'embed': embed_ms, 'match': match_ms}, **sub) if pipe is None else
-                          {'detect+crop': float(np.mean([ev[i][0].elapsed_time(det_ms[i]) for i in range(args.steps)])),
-                           'detect+crop+embed': embed_ms, 'match': match_ms}),
             'roofline': {
                 'bound': 'mfma',
                 'kernel': '%s: %.1f %% of the GPU time of one profiled (single-lane) forward over %d launches; one launch group = '
@@ -729,7 +791,7 @@ def main():
                              'frac': (e_roof_ms + m_roof_ms) / (elapsed / args.steps * 1e3),
                              'note': '(t_roof of the embedding forward at the f32-MFMA peak + t_roof of the match) / measured step'},
             },
-        }
+        })
         if compute != 'f32':
             # honest denominators: the bf16 MFMA peak, against which 6 (3) MFMA flops are spent per algorithmic flop
             nprod = 6.0 if compute == 'bf16x3' else 3.0
@@ -802,6 +864,7 @@ def main():
             out['cpu_baseline'] = (cpu_baseline(arch, head, gallery_rows) if pipe is None else
                                    (cpu_baseline_frames_mtcnn(gallery_rows, det.get_weights()) if mtcnn else
                                     cpu_baseline_frames(gallery_rows, dp)))
+    if rank == 0:
         if json_fd is None:
             print(json.dumps(out), flush=True)
         else:

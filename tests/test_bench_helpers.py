@@ -45,6 +45,28 @@ def test_layer_rooflines_and_kernel_shares():
     assert shares[0] == ('k1', 0.75, 2) and shares[1] == ('k2', 0.25, 1)
 
 
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: integers as float64, floats as float32, values unchanged; an array over its share of the budget is cut
+    to the same seeded row sample on every call, its row indices beside it; the files stay within the budget."""
+    b = _bench()
+    g = torch.Generator().manual_seed(0)
+    arrays = {'idx': torch.arange(300, dtype=torch.int64) * 3, 'dist': torch.rand(300, generator=g),
+              'logits': torch.randn(300, 1000, generator=g)}
+    monkeypatch.setattr(b, 'DUMP_BYTES', 3 * 400_000)
+    for run in ('a', 'b'):
+        b.dump_outputs(str(tmp_path / run), arrays)
+    a = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert sorted(a) == ['dist', 'idx', 'logits', 'logits_rows']
+    assert a['idx'].dtype == np.float64 and np.array_equal(a['idx'], np.arange(300) * 3.0)
+    assert a['dist'].dtype == np.float32 and np.array_equal(a['dist'], arrays['dist'].numpy())
+    rows = a['logits_rows'].astype(np.int64)
+    assert 0 < len(rows) < 300 and np.all(np.diff(rows) > 0) and np.array_equal(a['logits_rows'], rows)
+    assert a['logits'].dtype == np.float32 and np.array_equal(a['logits'], arrays['logits'].numpy()[rows])
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))) <= 3 * 400_000 + 4 * 128
+    for f in os.listdir(str(tmp_path / 'a')):
+        assert np.array_equal(np.load(str(tmp_path / 'b' / f)), a[f[:-4]]), f
+
+
 def test_area_resize_restatement_properties():
     """oracle/imageops.area_resize restates cv2's uint8 INTER_AREA paths (unpinned: cv2 is not installed).  What can be
     checked without cv2: a constant image stays constant on every path; the 2 x 2 path is (a + b + c + d + 2) >> 2; other

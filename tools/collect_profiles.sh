@@ -7,7 +7,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05
 mkdir -p $O
-prof() { local tag=$1; shift; rocprofv3 "$@" --output-format csv -d $O/$tag -o p -- python3 bench.py --gpus 1 ${ARGS} > $O/$tag.json 2> $O/$tag.err; }
+prof() { local tag=$1; shift; rocprofv3 "$@" --output-format csv -d $O/$tag -o p -- python3 bench.py --gpus 1 --full ${ARGS} > $O/$tag.json 2> $O/$tag.err; }
 # 1. the driver's command, default executor (two lanes: kernel durations of the two streams overlap)
 ARGS="--steps 20 --warmup 5" prof ks_default --kernel-trace --stats &&
 # 2. the same workload on ONE lane: kernels run back to back, so per-kernel durations add up to the forward
@@ -22,24 +22,24 @@ DIF_STREAMS=1 ARGS="--workload r50 --steps 10 --warmup 3 --no-cpu-baseline --no-
 ARGS="--workload r50 --steps 3 --warmup 1 --no-cpu-baseline --no-latency" prof pf_r50 --pmc FETCH_SIZE &&
 ARGS="--workload r50 --steps 3 --warmup 1 --no-cpu-baseline --no-latency" prof pw_r50 --pmc WRITE_SIZE &&
 # 4. un-profiled bench lines
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err &&
-DIF_STREAMS=1 python3 bench.py --no-cpu-baseline > $O/bench_default_1lane.json 2>/dev/null &&
-python3 bench.py --workload r100 > $O/bench_r100.json 2>/dev/null &&
-python3 bench.py --workload r50 > $O/bench_r50.json 2>/dev/null &&
-DIF_STREAMS=1 python3 bench.py --workload r50 --no-cpu-baseline > $O/bench_r50_1lane.json 2>/dev/null &&
-python3 bench.py --workload r100_arc --no-cpu-baseline > $O/bench_r100_arc.json 2>/dev/null &&
-python3 bench.py --workload r100_1m_bf16x3 --no-cpu-baseline > $O/bench_r100_1m_bf16x3.json 2>/dev/null &&
-python3 bench.py --workload r100_1m_bf16x2 --no-cpu-baseline > $O/bench_r100_1m_bf16x2.json 2>/dev/null &&
-python3 bench.py --force-collectives --no-cpu-baseline --no-throughput-mode > $O/bench_default_fc.json 2>/dev/null &&
-python3 bench.py --workload frames --steps 3 --warmup 1 > $O/bench_frames.json 2>/dev/null &&
-python3 bench.py --workload frames_mtcnn --steps 5 --warmup 2 > $O/bench_frames_mtcnn.json 2>/dev/null &&
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err &&
+DIF_STREAMS=1 python3 bench.py --full --no-cpu-baseline > $O/bench_default_1lane.json 2>/dev/null &&
+python3 bench.py --full --workload r100 > $O/bench_r100.json 2>/dev/null &&
+python3 bench.py --full --workload r50 > $O/bench_r50.json 2>/dev/null &&
+DIF_STREAMS=1 python3 bench.py --full --workload r50 --no-cpu-baseline > $O/bench_r50_1lane.json 2>/dev/null &&
+python3 bench.py --full --workload r100_arc --no-cpu-baseline > $O/bench_r100_arc.json 2>/dev/null &&
+python3 bench.py --full --workload r100_1m_bf16x3 --no-cpu-baseline > $O/bench_r100_1m_bf16x3.json 2>/dev/null &&
+python3 bench.py --full --workload r100_1m_bf16x2 --no-cpu-baseline > $O/bench_r100_1m_bf16x2.json 2>/dev/null &&
+python3 bench.py --full --force-collectives --no-cpu-baseline --no-throughput-mode > $O/bench_default_fc.json 2>/dev/null &&
+python3 bench.py --full --workload frames --steps 3 --warmup 1 > $O/bench_frames.json 2>/dev/null &&
+python3 bench.py --full --workload frames_mtcnn --steps 5 --warmup 2 > $O/bench_frames_mtcnn.json 2>/dev/null &&
 # 5. per-layer tables, latency
 python3 tools/layer_profile.py iresnet100 256 > $O/layers_r100.txt 2>&1 &&
 python3 tools/layer_profile.py resnet 256 > $O/layers_r50.txt 2>&1 &&
 python3 tools/layer_profile.py iresnet100 256 bf16x2 > $O/layers_r100_bf16x2.txt 2>&1 &&
 python3 tools/layer_profile.py yolov3 64 > $O/layers_yolov3.txt 2>&1 &&
 python3 tools/latency.py > $O/latency.txt 2>&1 &&
-(rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_frames_mtcnn -o p -- python3 bench.py --workload frames_mtcnn --steps 3 --warmup 1 --no-cpu-baseline > $O/ks_frames_mtcnn.json 2> $O/ks_frames_mtcnn.err && python3 tools/kstats.py $O/ks_frames_mtcnn 4 > $O/ks_frames_mtcnn.txt) &&
+(rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_frames_mtcnn -o p -- python3 bench.py --full --workload frames_mtcnn --steps 3 --warmup 1 --no-cpu-baseline > $O/ks_frames_mtcnn.json 2> $O/ks_frames_mtcnn.err && python3 tools/kstats.py $O/ks_frames_mtcnn 4 > $O/ks_frames_mtcnn.txt) &&
 # 5b. round 5: the small-batch regime -- per-layer tables, kernel-trace stats and block traces at batch 1 / 8 / 32
 (for a in iresnet100 resnet; do for b in 1 8 32; do python3 tools/layer_profile.py $a $b > $O/layers_${a}_b$b.txt 2>&1 || exit 1; done; done) &&
 (for c in "iresnet100 1" "iresnet100 8" "iresnet100 32" "resnet 1" "resnet 8"; do set -- $c; rocprofv3 --kernel-trace --stats --output-format csv -d $O/ksb_$1_$2 -o p -- python3 tools/small_batch.py $1 $2 50 > $O/ksb_$1_$2.log 2>&1 && python3 tools/kstats.py $O/ksb_$1_$2 55 > $O/ksb_$1_$2.txt || exit 1; done) &&

@@ -1,7 +1,7 @@
 #!/bin/bash
 # lanes on least-priority streams vs normal ones, with and without an RCCL process group created before the net (r04)
 out=gpurun_out/r4c; mkdir -p $out
-B="--no-cpu-baseline --no-throughput-mode --steps 15 --warmup 4"
+B="--full --no-cpu-baseline --no-throughput-mode --steps 15 --warmup 4"
 run() { # tag, env, args
   DIF_OPTIONS="$2" timeout -k 10 200 python3 bench.py $B $3 > $out/$1.json 2> $out/$1.err || return 1
   python3 - "$out/$1.json" "$1" <<'PY'

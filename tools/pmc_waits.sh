@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/waits
 mkdir -p $O
 W=${1:-r100}
-ARGS="--workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-throughput-mode"
+ARGS="--full --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-throughput-mode"
 export DIF_STREAMS=1
 p() { local tag=$1; shift; rocprofv3 --pmc "$@" --output-format csv -d $O/$tag -o p -- python3 bench.py --gpus 1 $ARGS > $O/$tag.json 2> $O/$tag.err; }
 p a SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY &&
