@@ -2417,6 +2417,8 @@ static int launch_conv_pre_impl(const ConvArgs& a, hipStream_t st) {
 // (the end of conv_run).  64x64 was measured per layer over both networks against
 // 128x128 / 128x64 / 64x128 at four waves (round 1: it wins or ties everywhere) and against 128x128 at eight waves
 // (round 2: within 1 % either way, profiles/r02_ablation.txt), so the other f32 instantiations were dropped.
+#include "conv_winograd.hpp"
+
 int conv_run(const ConvArgs& a, hipStream_t st) {
   if (a.M <= 0) return 0;
   if (a.Cin % 4 != 0) return set_error("conv: Cin must be a multiple of 4 (got %d)", a.Cin);
@@ -2439,6 +2441,8 @@ int conv_run(const ConvArgs& a, hipStream_t st) {
     if (span * a.H * a.W * a.Cin * 4 >= 0x7fffffffLL)
       return set_error("conv: a 256-pixel tile spans more than 2 GiB of input (%dx%dx%d)", a.H, a.W, a.Cin);
   }
+  // Winograd F(2x2,3x3) first: its decision reads the shape, the batch and the weights' presence only (conv_winograd.hpp)
+  if (wino_applies(a)) return launch_conv_wino(a, st);
   // (four waves of 128 x 32 with a six-set B ring, and eight waves on a 256 x 128 tile -- Tile<4, 1, 1, 4>, Tile<2, 2, 4, 2>: the
   // mainloop takes either -- measured the same as this one within 2 %)
   // (three or two bf16 terms per operand: ConvArgs::bf_terms, picked inside the kernel)

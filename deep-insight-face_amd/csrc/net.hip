@@ -944,7 +944,7 @@ static void fold(const Net* net, const BNRef& bn, int bias, int C, std::vector<f
 // every key set_option accepts (dif_net_option_name: include/dif.h documents each one, and a test holds it to that)
 const char* const* Net::option_names() {
   static const char* const names[] = {"pipe", "bdp", "stem", "patch", "patch2d", "bd", "t2", "tn", "sk2", "mt", "bf16x3",
-                                      "bf_terms", "ysub", "lane_split", "lane_prio", "dbg", nullptr};
+                                      "bf_terms", "ysub", "lane_split", "lane_prio", "wino", "dbg", nullptr};
   return names;
 }
 
@@ -966,6 +966,7 @@ int Net::set_option(const char* key, int value) {
   }
   if (!strcmp(key, "stem")) return use_stem = value != 0, 0;
   if (!strcmp(key, "dbg")) return conv_dbg = value, 0;
+  if (!strcmp(key, "wino")) return use_wino = value != 0, 0;     // on after a finalize without it: from the next finalize
   if (!strcmp(key, "patch")) return flag(CONV_OFF_PATCH);
   if (!strcmp(key, "patch2d")) return flag(CONV_OFF_PATCH2D);
   if (!strcmp(key, "bd")) return flag(CONV_OFF_BD);
@@ -1103,6 +1104,41 @@ int Net::finalize(int mb) {
         if ((uint64_t)frag.size() * 4 < 0xFFFFFFF0ull) {
           if (upload(this, frag, &op.d_w_frag)) return -1;
           op.w_frag_bytes = (uint32_t)(frag.size() * 4);
+        }
+      }
+      // Winograd F(2x2,3x3) weights for conv_wino_kernel (conv_winograd.hpp): U_c[ci][co] = (G g G^T)[i][j], c = 4 i + j,
+      // formed in double and rounded once, in the kernel's fragment order (1 KB per wave instruction).  Only for the layers
+      // its shape rule can admit (wino_applies; the batch threshold is decided per launch) and only with option "wino" on.
+      op.d_w_wino = nullptr;
+      op.w_wino_bytes = 0;
+      {
+        const TensorDesc& xd = tensors[op.x];
+        const TensorDesc& yd = tensors[op.y >= 0 ? op.y : op.y2];
+        if (use_wino && !compute_bf16x3 && op.KH == 3 && op.KW == 3 && op.stride == 1 && op.pad_t == 1 && op.pad_l == 1 &&
+            !op.pre_bn.valid() && !op.chw_flatten && !op.y_sub && op.Cin_true == op.Cin && op.Cin % BK == 0 &&
+            op.Cout % 64 == 0 && xd.H % 2 == 0 && xd.W % 2 == 0 && xd.H <= 16 && xd.W <= 16 && yd.H == xd.H && yd.W == xd.W &&
+            (uint64_t)16 * op.Cin * op.Cout * 4 < 0xFFFFFFF0ull) {
+          static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+          const int KS16 = op.Cin / 16, NTn = op.Cout / 64;
+          std::vector<float> u((size_t)16 * op.Cin * op.Cout);
+          const float* w = params[op.w].data.data();   // HWIO [3][3][Cin][Cout]
+          for (int ci = 0; ci < op.Cin; ++ci)
+            for (int co = 0; co < op.Cout; ++co) {
+              double gk[3][3], tg[4][3];
+              for (int t = 0; t < 9; ++t) gk[t / 3][t % 3] = w[((size_t)t * op.Cin + ci) * op.Cout + co];
+              for (int i = 0; i < 4; ++i)
+                for (int k = 0; k < 3; ++k) tg[i][k] = G[i][0] * gk[0][k] + G[i][1] * gk[1][k] + G[i][2] * gk[2][k];
+              const int ks = ci / 16, rem = ci % 16, ln = (rem / 8) * 32 + co % 32, q = (rem % 8) / 4, t4 = rem % 4;
+              const int nt = co / 64, nf = (co % 64) / 32;
+              for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j) {
+                  const double v = tg[i][0] * G[j][0] + tg[i][1] * G[j][1] + tg[i][2] * G[j][2];
+                  const size_t c = (size_t)(4 * i + j);
+                  u[(((((c * NTn + nt) * KS16 + ks) * 2 + nf) * 2 + q) * 64 + ln) * 4 + t4] = (float)v;
+                }
+            }
+          if (upload(this, u, &op.d_w_wino)) return -1;
+          op.w_wino_bytes = (uint32_t)(u.size() * 4);
         }
       }
       // 16-column fragment order for the one-image kernel (conv_minitile.hpp): every layer it can take -- pointwise layers
@@ -1360,6 +1396,8 @@ int Net::run_op(const Op& op, Lane& L, const void* xin, int n, int layout, int d
       a.w_frag_bytes = op.w_frag_bytes;
       a.w_f16 = op.d_w_f16;
       a.w_f16_bytes = op.w_f16_bytes;
+      a.w_wino = use_wino ? op.d_w_wino : nullptr;
+      a.w_wino_bytes = op.w_wino_bytes;
       a.bf_terms = bf_terms;
       a.y = ptr(op.y);
       a.y2 = ptr(op.y2);

@@ -234,7 +234,8 @@ int dif_net_finalize(dif_net* net, int max_batch);
 /* execution options (no reference counterpart: Keras picks its kernels by itself).  EVERY key the library accepts is
  * listed here with its default (tests/test_cabi_symbols.py compares this list with dif_net_option_name); an unknown key
  * fails.  Unless a key says "before dif_net_finalize" it may be changed between forwards.  Most keys choose between
- * kernel families that compute the same products (the parity tests run both sides); none changes what is computed.
+ * kernel families that compute the same products (the parity tests run both sides); "wino" and "bf16x3" change the
+ * products (f32 throughout with "wino"; see each).
  *   "pipe"       1 (default): short-K convolutions may take the software-pipelined kernel (conv_pipe_kernel);
  *                0: every convolution stays on the plain implicit-GEMM kernel
  *   "bdp"        1 (default): 3x3 / stride 1 layers with several tiles per resident block may take the kernel that retires
@@ -257,7 +258,12 @@ int dif_net_finalize(dif_net* net, int max_batch);
  *   "mt"         1 (default): at ONE image per call (predictions.py:152-156) a layer runs in one launch on 16 x 16 tiles,
  *                operands straight from L2 into the MFMA registers, K split over the block's waves (conv_minitile.hpp);
  *                0: the split-K pair / the large-batch kernels
- *   "bf16x3"     0 (default): float32 MFMA, a bit-exact f32 fma chain -- the reference's arithmetic;
+ *   "wino"       1 (default): 3x3 / stride 1 layers on even maps of at most 16 x 16 (IResNet's 14 x 14 stage) run as
+ *                Winograd F(2x2,3x3) from 64 images per launch up (conv_wino_kernel): 2.25x fewer MFMA multiply-adds, f32
+ *                operands, transforms and accumulation, different products -- about twice the direct path's rounding
+ *                error per layer; 0: the direct f32 fma chain everywhere (any time; turned on after a dif_net_finalize
+ *                that ran with 0, it takes effect at the next dif_net_finalize, which builds the transformed weights)
+ *   "bf16x3"     0 (default): float32 MFMA -- with "wino" = 0 a bit-exact f32 fma chain, the reference's arithmetic;
  *                1 (before dif_net_finalize): throughput mode -- every f32 operand split into bf16 terms, bf16 MFMA
  *                products accumulated in f32 (f32-level accuracy, same 1e-5 cosine gate, not bit-identical)
  *   "bf_terms"   3 (default) or 2: bf16 terms per operand in that mode (six / three MFMA products per multiply-add)
