@@ -1,5 +1,6 @@
 // conv_wino_kernel: Winograd F(2x2, 3x3) for the large-batch 3x3 / stride 1 / pad 1 layers on small even maps (IResNet's
-// 14 x 14 stage).  Included by conv.hip (inside namespace dif, after the helpers it uses).
+// 14 x 14 stage); conv_winow_kernel, further down: the same arithmetic for the wider maps (28 x 28 .. 112 x 112) in
+// half-size blocks, option "wino" = 2.  Included by conv.hip (inside namespace dif, after the helpers it uses).
 //
 // A 3x3 convolution of a 4x4 input tile d is Y = A^T [ (G g G^T) .* (B^T d B) ] A: 2x2 outputs from 16 element-wise
 // products, i.e. 16 GEMMs M_c[tile][co] = sum_ci V_c[tile][ci] U_c[ci][co] with K = Cin instead of one with K = 9 Cin --
@@ -24,6 +25,9 @@ constexpr int LDS_BYTES = 2 * STAGE * 4;       // two stages; the epilogue's M h
 // fewest Winograd tiles per launch (a pure function of the layer shape and the batch): 64 images of 14 x 14.  Below it
 // the layer stays on the direct kernels -- the split-K / one-image paths of the small batches among them
 constexpr int64_t MIN_TILES = 64 * 49;
+// the wide maps (conv_winow_kernel, level 2): map sides up to 112, and at least 128 images per launch
+constexpr int WIDE_MAX_HW = 112;
+constexpr int64_t WIDE_MIN_IMAGES = 128;
 }  // namespace wino
 
 // B^T x for one 4-vector: (x0 - x2, x1 + x2, x2 - x1, x1 - x3)
@@ -228,19 +232,239 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int
   }
 }
 
-// The layers conv_wino_kernel takes: 3x3 / stride 1 / pad 1 on an even map of at most 16 x 16 (no output shrink), whole
-// 32-channel input slices, whole 64-channel column blocks, no pre-activation, the lean epilogue's plain geometry and
-// unit-stride shortcut, 31-bit byte offsets -- and at least wino::MIN_TILES Winograd tiles.  Depends on the shape, the
-// batch of the launch and whether the net carries the transformed weights (Net option "wino") -- on nothing else.
-static bool wino_applies(const ConvArgs& a) {
-  if (!a.w_wino || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1) return false;
-  if (a.Ho != a.H || a.Wo != a.W || (a.H & 1) || (a.W & 1) || a.H > 16 || a.W > 16) return false;
-  if (a.Cin % 32 != 0 || a.Cout % wino::BN != 0 || a.pre_scale || a.y_sub) return false;
-  if (!(a.y_H == a.Ho && a.y_W == a.Wo && a.y_oy == 0 && a.y_ox == 0 && a.y_ld == a.Cout && a.y_coff == 0)) return false;
-  if (a.res && (a.res_stride != 1 || a.res_H != a.Ho || a.res_W != a.Wo)) return false;
-  if ((int64_t)a.M * a.Cout * 4 >= 0x7fffffffLL || (int64_t)a.M * a.Cin * 4 >= 0x7fffffffLL) return false;
-  if ((int64_t)16 * a.Cin * a.Cout * 4 > (int64_t)a.w_wino_bytes) return false;
-  return (int64_t)a.N * (a.H / 2) * (a.W / 2) >= wino::MIN_TILES;
+// conv_winow_kernel: the same arithmetic for the wide maps (option "wino" = 2: even maps above 16 x 16 up to 112 x 112 --
+// IResNet's 28 x 28, 56 x 56 and 112 x 112 stages).  Those layers have 128 or 64 input channels, so a block's K loop is 8 or
+// 4 steps and conv_wino_kernel's one block per CU leaves its set-up (first tile fetch, transform, barrier) and its epilogue
+// (two LDS round trips of M, output transform, stores) uncovered for a third to a half of the block's life.  This kernel's
+// default shape is half the block: TT = 32 tiles x 64 channels on four waves, wave w owning components 4w .. 4w+3 (one
+// 32-tile x two 32-channel fragments each: again 128 accumulators per lane), 64 KiB of LDS -- two blocks per CU, so one
+// block's epilogue and set-up run under the other's MFMAs and a K-step barrier holds four waves instead of eight.  The
+// price is U traffic from L2 per MFMA doubled (a B fragment feeds one row fragment, not two).  U keeps conv_wino_kernel's
+// layout; the B fragments and the A fragments of a component are fetched two components ahead into two register sets.
+// Every accumulator sums the same products in the same order as conv_wino_kernel's: the block shape changes no bit.
+// <64, 2> is conv_wino_kernel's own shape (one block per CU), kept for A/B runs [dbg bit 65536].
+template <int TT, int CPW>
+struct WinoW {
+  static constexpr int MF = TT / 32;                         // 32-tile row fragments per component
+  static constexpr int NT = 16 / CPW * 64;                   // threads per block (NT / 8 == TT: one tile x two channels each)
+  static constexpr int STAGE = 16 * TT * wino::KC;           // floats per V stage
+  static constexpr int LDS_BYTES = 2 * STAGE * 4;            // the epilogue's M half (16 x TT x 32 floats) fits the same
+  static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
+};
+
+template <int TT, int CPW>
+__global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(const ConvArgs a, int blocks_m, int nblocks) {
+  using S = WinoW<TT, CPW>;
+  constexpr int MF = S::MF, KC = wino::KC;
+  extern __shared__ __attribute__((aligned(16))) float wino_smem[];
+  const int b = xcd_remap((int)blockIdx.x, nblocks);
+  const int nt = b / blocks_m, mt = b - nt * blocks_m;   // column-slice-major: an XCD's blocks share one slice of U in its L2
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tw = a.W >> 1, tpi = (a.H >> 1) * tw, ntiles = a.N * tpi;
+  const int KS = a.Cin / KC;
+
+  // ---- this thread's tile: the input loader's (two channels) and the epilogue's (four channels) alike
+  const int ltile = tid >> 3, cp = tid & 7;
+  const int g = mt * TT + ltile;
+  const bool tile_ok = g < ntiles;
+  int pix0 = 0;                                  // first output pixel (2 ty, 2 tx) of the tile, linear over N x H x W
+  unsigned vmask = 0;                            // in-range points of the 4x4 input tile
+  if (tile_ok) {
+    const int img = g / tpi, rem = g - img * tpi, ty = rem / tw, tx = rem - ty * tw;
+    pix0 = (img * a.H + 2 * ty) * a.W + 2 * tx;
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+      const int iy = 2 * ty - 1 + (p >> 2), ix = 2 * tx - 1 + (p & 3);
+      if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) vmask |= 1u << p;
+    }
+  }
+  const int row_b = a.W * a.Cin * 4, pix_b = a.Cin * 4;
+  // byte offset of point (0, 0) of the tile (one row and column before pix0; only in-range points are ever added to it)
+  const int lbase = (pix0 - a.W - 1) * pix_b + cp * 8;
+  const __amdgpu_buffer_rsrc_t xrs = make_rsrc(a.x, (uint32_t)a.N * (uint32_t)(a.H * a.W) * (uint32_t)pix_b);
+  auto dload = [&](int ks, f32x2 (&d)[16]) {
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+      const uint32_t off = ((vmask >> p) & 1u) ? (uint32_t)(lbase + (p >> 2) * row_b + (p & 3) * pix_b + ks * (KC * 4)) : OOB;
+      d[p] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(xrs, off, 0, 0));
+    }
+  };
+  const int vdst = ltile * KC + (((cp >> 1) ^ ((ltile >> 2) & 3)) << 2) + (cp & 1) * 2;
+  auto vstore = [&](float* buf, const f32x2 (&d)[16]) {
+    float d0[16], d1[16], v0[16], v1[16];
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+      d0[p] = d[p][0];
+      d1[p] = d[p][1];
+    }
+    wino_input_transform(d0, v0);
+    wino_input_transform(d1, v1);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) *reinterpret_cast<f32x2*>(buf + c * (TT * KC) + vdst) = f32x2{v0[c], v1[c]};
+  };
+
+  // ---- operands of this wave's components: two register sets, component j in set j & 1
+  const int h = lane >> 5, r32 = lane & 31, sw = (r32 >> 2) & 3;
+  const int tiles_n = a.Cout / wino::BN;
+  const __amdgpu_buffer_rsrc_t wrs = make_rsrc(a.w_wino, a.w_wino_bytes);
+  const uint32_t boff0 = (uint32_t)((CPW * wave * tiles_n + nt) * KS) * 4096u + (uint32_t)lane * 16u;
+  const uint32_t bstep = (uint32_t)(tiles_n * KS) * 4096u;     // one component on
+  f32x4 bw[2][2][2];                             // [set][column fragment][k quad]
+  auto bload = [&](int j, int ks) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        bw[j & 1][nf][q] = buf_load4(wrs, boff0 + (uint32_t)j * bstep + (uint32_t)ks * 4096u + (uint32_t)(nf * 2 + q) * 1024u);
+  };
+  // lane half h consumes channels 8 h + 4 q + t of the K-step in sub-step s = 4 q + t (U is stored in the same order)
+  int aoff[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) aoff[q] = r32 * KC + (((2 * h + q) ^ sw) << 2);
+  f32x4 av[2][MF][2];                            // [set][row fragment][k quad]
+  auto aread = [&](const float* buf, int j) {
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        av[j & 1][mf][q] = *reinterpret_cast<const f32x4*>(buf + (CPW * wave + j) * (TT * KC) + mf * 32 * KC + aoff[q]);
+  };
+  f32x16 acc[CPW][MF][2];                        // [component][row fragment][column fragment]
+#pragma unroll
+  for (int j = 0; j < CPW; ++j)
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+      for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][mf][nf][r] = 0.f;
+  auto mfma = [&](int j) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+          for (int nf = 0; nf < 2; ++nf)
+            acc[j][mf][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j & 1][mf][q][t], bw[j & 1][nf][q][t], acc[j][mf][nf], 0, 0, 0);
+  };
+
+  // ---- main loop
+  {
+    f32x2 d[16];
+    dload(0, d);
+    bload(0, 0);
+    bload(1, 0);
+    vstore(wino_smem, d);
+    lds_barrier();
+    for (int ks = 0; ks < KS; ++ks) {
+      const float* cur = wino_smem + (ks & 1) * S::STAGE;
+      float* nxt = wino_smem + ((ks + 1) & 1) * S::STAGE;
+      const bool more = ks + 1 < KS;
+      if (more) dload(ks + 1, d);
+      aread(cur, 0);
+      aread(cur, 1);
+#pragma unroll
+      for (int j = 0; j < CPW; ++j) {
+        mfma(j);
+        if (j + 2 < CPW) {
+          aread(cur, j + 2);
+          bload(j + 2, ks);
+        } else if (more) {
+          bload(j + 2 - CPW, ks + 1);
+        }
+      }
+      if (more) vstore(nxt, d);
+      lds_barrier();
+    }
+  }
+
+  // ---- epilogue: per 32-channel half, M through LDS, Y = A^T M A, BN / activation / shortcut / second output
+  const int c4 = cp * 4;
+  const uint32_t bytes = (uint32_t)a.M * (uint32_t)a.Cout * 4u;
+  const __amdgpu_buffer_rsrc_t y_rsrc = make_rsrc(a.y, a.y ? bytes : 0u);
+  const __amdgpu_buffer_rsrc_t y2_rsrc = make_rsrc(a.y2, a.y2 ? bytes : 0u);
+  const __amdgpu_buffer_rsrc_t res_rsrc = make_rsrc(a.res, a.res ? bytes : 0u);
+  const bool has_res = a.res != nullptr;
+  const int act = a.act, act2 = a.act2;
+#pragma unroll
+  for (int nf = 0; nf < 2; ++nf) {
+#pragma unroll
+    for (int j = 0; j < CPW; ++j)
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          wino_smem[(CPW * wave + j) * (TT * 32) + (mf * 32 + frag_row(lane, r)) * 32 + r32] = acc[j][mf][nf][r];
+    lds_barrier();
+    const int c = nt * wino::BN + nf * 32 + c4;
+    f32x4 m[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = *reinterpret_cast<const f32x4*>(wino_smem + k * (TT * 32) + ltile * 32 + c4);
+    f32x4 yv[4];                                  // outputs (0,0), (0,1), (1,0), (1,1) of the tile
+    {
+      f32x4 s0[4], s1[4];
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        s0[jj] = m[jj] + m[4 + jj] + m[8 + jj];
+        s1[jj] = m[4 + jj] - m[8 + jj] - m[12 + jj];
+      }
+      yv[0] = s0[0] + s0[1] + s0[2];
+      yv[1] = s0[1] - s0[2] - s0[3];
+      yv[2] = s1[0] + s1[1] + s1[2];
+      yv[3] = s1[1] - s1[2] - s1[3];
+    }
+    const f32x4 sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
+    const f32x4 sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
+    uint32_t voff[4];
+    f32x4 rv[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int pix = pix0 + (p >> 1) * a.W + (p & 1);
+      voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+      rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      f32x4 v, v2;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float t = fmaf(yv[p][e], sc[e], sh[e]);
+        const float tr = fmaxf(t, 0.f), tp = t >= 0.f ? t : t * al[e];
+        t = act == ACT_RELU ? tr : (act == ACT_PRELU ? tp : (act == ACT_RELU6 ? fminf(tr, 6.f) : t));
+        if (has_res) t += rv[p][e];
+        v[e] = t;
+        float u = fmaf(t, sc2[e], sh2[e]);
+        const float ur = fmaxf(u, 0.f), up = u >= 0.f ? u : u * al2[e];
+        v2[e] = act2 == ACT_RELU ? ur : (act2 == ACT_PRELU ? up : (act2 == ACT_RELU6 ? fminf(ur, 6.f) : u));
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
+    }
+    lds_barrier();
+  }
+}
+
+// The layers the Winograd kernels take: 3x3 / stride 1 / pad 1 on an even map (no output shrink), whole 32-channel input
+// slices, whole 64-channel column blocks, no pre-activation, the lean epilogue's plain geometry and unit-stride shortcut,
+// 31-bit byte offsets.  Returns 1 for conv_wino_kernel: maps of at most 16 x 16 with at least wino::MIN_TILES Winograd
+// tiles (level 1 and up); 2 for conv_winow_kernel: wider maps up to 112 x 112 with the tiles of at least
+// wino::WIDE_MIN_IMAGES images (level 2); 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether
+// the net carries the transformed weights (Net option "wino") -- on nothing else.
+static int wino_applies(const ConvArgs& a) {
+  if (!a.w_wino || a.wino_level < 1 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1) return 0;
+  if (a.Ho != a.H || a.Wo != a.W || (a.H & 1) || (a.W & 1)) return 0;
+  const bool wide = a.H > 16 || a.W > 16;
+  if (wide && (a.wino_level < 2 || a.H > wino::WIDE_MAX_HW || a.W > wino::WIDE_MAX_HW)) return 0;
+  if (a.Cin % 32 != 0 || a.Cout % wino::BN != 0 || a.pre_scale || a.y_sub) return 0;
+  if (!(a.y_H == a.Ho && a.y_W == a.Wo && a.y_oy == 0 && a.y_ox == 0 && a.y_ld == a.Cout && a.y_coff == 0)) return 0;
+  if (a.res && (a.res_stride != 1 || a.res_H != a.Ho || a.res_W != a.Wo)) return 0;
+  if ((int64_t)a.M * a.Cout * 4 >= 0x7fffffffLL || (int64_t)a.M * a.Cin * 4 >= 0x7fffffffLL) return 0;
+  if ((int64_t)16 * a.Cin * a.Cout * 4 > (int64_t)a.w_wino_bytes) return 0;
+  const int64_t tpi = (int64_t)(a.H / 2) * (a.W / 2);
+  if (wide) return a.N * tpi >= wino::WIDE_MIN_IMAGES * tpi ? 2 : 0;
+  return a.N * tpi >= wino::MIN_TILES ? 1 : 0;
 }
 
 static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {
@@ -253,4 +477,23 @@ static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {
   DIF_HIP(hipGetLastError());
   g_last_kernel = "conv_wino_kernel<F(2x2,3x3),64 tiles x 64>";
   return 0;
+}
+
+template <int TT, int CPW>
+static int launch_conv_winow(const ConvArgs& a, hipStream_t st, const char* name) {
+  using S = WinoW<TT, CPW>;
+  if (allow_dynamic_lds(reinterpret_cast<const void*>(conv_winow_kernel<TT, CPW>), S::LDS_BYTES)) return -1;
+  const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
+  const int blocks_m = (int)((ntiles + TT - 1) / TT), tiles_n = a.Cout / wino::BN;
+  const int64_t nblocks = (int64_t)blocks_m * tiles_n;
+  if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
+  hipLaunchKernelGGL((conv_winow_kernel<TT, CPW>), dim3((unsigned)nblocks), dim3(S::NT), S::LDS_BYTES, st, a, blocks_m, (int)nblocks);
+  DIF_HIP(hipGetLastError());
+  g_last_kernel = name;
+  return 0;
+}
+
+static int launch_conv_winow(const ConvArgs& a, hipStream_t st) {
+  if (a.dbg & 65536) return launch_conv_winow<64, 2>(a, st, "conv_winow_kernel<F(2x2,3x3),64 tiles x 64>");
+  return launch_conv_winow<32, 4>(a, st, "conv_winow_kernel<F(2x2,3x3),32 tiles x 64>");
 }

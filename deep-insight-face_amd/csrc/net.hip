@@ -966,7 +966,10 @@ int Net::set_option(const char* key, int value) {
   }
   if (!strcmp(key, "stem")) return use_stem = value != 0, 0;
   if (!strcmp(key, "dbg")) return conv_dbg = value, 0;
-  if (!strcmp(key, "wino")) return use_wino = value != 0, 0;     // on after a finalize without it: from the next finalize
+  if (!strcmp(key, "wino")) {                              // raised after a finalize below it: from the next finalize
+    if (value < 0 || value > 2) return set_error("dif_net_set_option: 'wino' takes 0, 1 or 2");
+    return use_wino = value, 0;
+  }
   if (!strcmp(key, "patch")) return flag(CONV_OFF_PATCH);
   if (!strcmp(key, "patch2d")) return flag(CONV_OFF_PATCH2D);
   if (!strcmp(key, "bd")) return flag(CONV_OFF_BD);
@@ -1108,7 +1111,8 @@ int Net::finalize(int mb) {
       }
       // Winograd F(2x2,3x3) weights for conv_wino_kernel (conv_winograd.hpp): U_c[ci][co] = (G g G^T)[i][j], c = 4 i + j,
       // formed in double and rounded once, in the kernel's fragment order (1 KB per wave instruction).  Only for the layers
-      // its shape rule can admit (wino_applies; the batch threshold is decided per launch) and only with option "wino" on.
+      // its shape rule can admit (wino_applies; the batch threshold is decided per launch) and only with option "wino" on:
+      // maps of at most 16 x 16 at level 1, the wide maps up to 112 x 112 (conv_winow_kernel, same U layout) at level 2.
       op.d_w_wino = nullptr;
       op.w_wino_bytes = 0;
       {
@@ -1116,7 +1120,8 @@ int Net::finalize(int mb) {
         const TensorDesc& yd = tensors[op.y >= 0 ? op.y : op.y2];
         if (use_wino && !compute_bf16x3 && op.KH == 3 && op.KW == 3 && op.stride == 1 && op.pad_t == 1 && op.pad_l == 1 &&
             !op.pre_bn.valid() && !op.chw_flatten && !op.y_sub && op.Cin_true == op.Cin && op.Cin % BK == 0 &&
-            op.Cout % 64 == 0 && xd.H % 2 == 0 && xd.W % 2 == 0 && xd.H <= 16 && xd.W <= 16 && yd.H == xd.H && yd.W == xd.W &&
+            op.Cout % 64 == 0 && xd.H % 2 == 0 && xd.W % 2 == 0 && yd.H == xd.H && yd.W == xd.W &&
+            ((xd.H <= 16 && xd.W <= 16) || (use_wino >= 2 && xd.H <= 112 && xd.W <= 112)) &&
             (uint64_t)16 * op.Cin * op.Cout * 4 < 0xFFFFFFF0ull) {
           static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
           const int KS16 = op.Cin / 16, NTn = op.Cout / 64;
@@ -1398,6 +1403,7 @@ int Net::run_op(const Op& op, Lane& L, const void* xin, int n, int layout, int d
       a.w_f16_bytes = op.w_f16_bytes;
       a.w_wino = use_wino ? op.d_w_wino : nullptr;
       a.w_wino_bytes = op.w_wino_bytes;
+      a.wino_level = use_wino;
       a.bf_terms = bf_terms;
       a.y = ptr(op.y);
       a.y2 = ptr(op.y2);

@@ -258,11 +258,14 @@ int dif_net_finalize(dif_net* net, int max_batch);
  *   "mt"         1 (default): at ONE image per call (predictions.py:152-156) a layer runs in one launch on 16 x 16 tiles,
  *                operands straight from L2 into the MFMA registers, K split over the block's waves (conv_minitile.hpp);
  *                0: the split-K pair / the large-batch kernels
- *   "wino"       1 (default): 3x3 / stride 1 layers on even maps of at most 16 x 16 (IResNet's 14 x 14 stage) run as
+ *   "wino"       a level.  1: 3x3 / stride 1 layers on even maps of at most 16 x 16 (IResNet's 14 x 14 stage) run as
  *                Winograd F(2x2,3x3) from 64 images per launch up (conv_wino_kernel): 2.25x fewer MFMA multiply-adds, f32
  *                operands, transforms and accumulation, different products -- about twice the direct path's rounding
- *                error per layer; 0: the direct f32 fma chain everywhere (any time; turned on after a dif_net_finalize
- *                that ran with 0, it takes effect at the next dif_net_finalize, which builds the transformed weights)
+ *                error per layer; 2 (default): level 1 plus the same layers on the wider even maps up to 112 x 112
+ *                (IResNet's 28 x 28, 56 x 56 and 112 x 112 stages) from 128 images per launch up (conv_winow_kernel, the
+ *                same arithmetic in half-size blocks, two per CU); 0: the direct f32 fma chain everywhere.  Any time;
+ *                raised after a dif_net_finalize that ran below it, the new level takes effect at the next
+ *                dif_net_finalize, which builds the transformed weights; lowered and raised back, at the next forward
  *   "bf16x3"     0 (default): float32 MFMA -- with "wino" = 0 a bit-exact f32 fma chain, the reference's arithmetic;
  *                1 (before dif_net_finalize): throughput mode -- every f32 operand split into bf16 terms, bf16 MFMA
  *                products accumulated in f32 (f32-level accuracy, same 1e-5 cosine gate, not bit-identical)
