@@ -3,7 +3,8 @@
 
 The reference module cannot be imported (FACEM_MODEL undefined at
 def time, missing external landmark detector); only the signatures are the contract.
-Detection / landmark alignment (api.py:107-195) is outside the hot path.
+Detection / landmark alignment (api.py:107-195) is outside the hot path; `align_face` offers the
+alignment step on its own for a caller that has five landmarks (MTCNN's, detector/mtcnn.py).
 """
 import typing
 
@@ -36,6 +37,21 @@ def face_distance(face_encodings, face_to_compare):
     flat_a = np.ascontiguousarray(a.reshape(a.shape[0], -1).T)
     flat_b = np.ascontiguousarray(b.reshape(b.shape[0], -1).T)
     return np.sqrt(utility.distance(flat_a, flat_b, 0)).reshape(a.shape[1:])
+
+
+def align_face(image: np.ndarray, landmarks5, size: int = 112) -> np.ndarray:
+    """One host image [H, W, 3] uint8 and its five landmarks [5, 2] ((x, y): left eye, right eye, nose, left and right
+    mouth corner) -> the size x size crop aligned to the ArcFace five-point template, computed on the device
+    (detector/align.py).  The reference's counterpart is `create_thumbnail` (api.py:132-145), an affine map through three
+    points of a 68-point landmark model; INTEGRATION.md says how to get that from `detector.align.warp_affine`."""
+    from .detector.align import align_faces
+    image = np.asarray(image)
+    if image.ndim != 3 or image.shape[2] < 3 or image.dtype != np.uint8:
+        raise ValueError('expected a uint8 image [H,W,3], got %s %s' % (image.dtype, image.shape))
+    lm = np.asarray(landmarks5, dtype=np.float32)
+    if lm.shape != (5, 2):
+        raise ValueError('expected five (x, y) landmarks, got %s' % (lm.shape,))
+    return align_faces(np.ascontiguousarray(image[None, :, :, 0:3]), lm[None], size)[0].cpu().numpy()
 
 
 def face_encodings(face_image: np.ndarray,

@@ -11,7 +11,13 @@ The networks restate the public MTCNN definition (Zhang et al. 2016) on the libr
 per frame and stage, an empty slot has score -1 -- so that a batch of frames needs no host round trip between the
 stages.  Deviations from the published code a port of someone else's weights must know: the library's IoU for every
 suppression (continuous boxes, union), crops clamped to the frame and resampled by area coverage, sibling heads as one
-layer ``head`` = [logits 2 | box 4 | landmarks 10 | zero filters], P-Net's ``conv1`` held as 12 filters (two zero).
+layer ``head`` = [logits 2 | box 4 | landmarks 10 | zero filters], P-Net's ``conv1`` held as 12 filters (two zero),
+O-Net's landmarks (five x then five y, relative to the crop) referred to the CLAMPED rectangle the crop was cut from --
+it goes with the clamped crops; the published code refers them to the unclamped box.
+
+``detect(..., return_landmarks=True)`` returns the five landmarks of every output slot; ``MtcnnFramePipeline(...,
+align=True)`` and ``MtcnnDetection(..., align=True)`` turn them into similarity-aligned crops (detector/align.py) instead
+of axis-aligned box crops.
 """
 import ctypes
 import math
@@ -25,6 +31,7 @@ from PIL import Image
 from .. import _native as N
 from ..networks.triplet import DifEmbedder
 from ..networks import weights as W
+from .align import align_faces
 from .run import _to_rgb, filter_bounding_box
 
 STAGES = ('pnet', 'rnet', 'onet')
@@ -46,7 +53,8 @@ class MtcnnDetector:
     """P-Net over an image pyramid -> R-Net -> O-Net for batches of equally sized uint8 frames.
 
     ``detect(frames) -> (boxes [n, cap[2], 4] (x1, y1, x2, y2), scores [n, cap[2]])``: CUDA tensors, best slot first,
-    score -1 = empty slot."""
+    score -1 = empty slot.  ``return_landmarks=True`` adds ``landmarks [n, cap[2], 5, 2]`` ((x, y) in frame pixels: left
+    eye, right eye, nose, left and right mouth corner; zeros in an empty slot) after the scores, before ``stages``."""
 
     def __init__(self, frame_hw=(480, 640), max_batch: int = 16, min_face: int = 20, thresholds=(0.6, 0.7, 0.7),
                  cap=(64, 32, 16), factor: float = 0.709, streams: int = 4):
@@ -150,7 +158,7 @@ class MtcnnDetector:
                                        N.ptr(dscores), N.ptr(dreg) if dreg is not None else None, ndst, off, int(calibrate),
                                        N.stream_ptr()))
 
-    def detect(self, frames, return_stages: bool = False):
+    def detect(self, frames, return_stages: bool = False, return_landmarks: bool = False):
         dev = N.require_device()
         t = torch.from_numpy(np.ascontiguousarray(frames)) if not torch.is_tensor(frames) else frames
         if t.dim() != 4 or tuple(t.shape[1:]) != (self.h, self.w, 3) or t.dtype != torch.uint8:
@@ -205,31 +213,41 @@ class MtcnnDetector:
             reg = torch.empty((n, k, 4), **f32)
             N.check(N.lib.dif_mtcnn_rescore(N.ptr(out), n * k, out.shape[1], float(thr), N.ptr(scores), N.ptr(reg),
                                             N.ptr(boxes) if plain else None, int(plain), st))
-            return reg
+            return reg, out
 
-        r1 = refine(self.rnet, 24, b1, s1, c1, self.thresholds[1], False)
+        r1, _ = refine(self.rnet, 24, b1, s1, c1, self.thresholds[1], False)
         b2 = torch.empty((n, c2, 4), **f32)
         s2 = torch.empty((n, c2), **f32)
         keep = self._nms(b1, s1, c2, 0.7)
         self._gather(keep, c2, b1, s1, N.ptr(r1), 4, c1, b2, s2, None, c2, 0, 1)
         if return_stages:
             stages.update(stage2_boxes=b2.clone(), stage2_scores=s2.clone())
-        refine(self.onet, 48, b2, s2, c2, self.thresholds[2], True)
+        b2_in = b2.clone() if return_landmarks else None       # the boxes O-Net is shown: the regression below is in place
+        _, o3 = refine(self.onet, 48, b2, s2, c2, self.thresholds[2], True)
         b3 = torch.empty((n, c2, 4), **f32)
         s3 = torch.empty((n, c2), **f32)
         keep = self._nms(b2, s2, c2, 0.7)
         self._gather(keep, c2, b2, s2, None, 4, c2, b3, s3, None, c2, 0, 0)
-        return (b3, s3, stages) if return_stages else (b3, s3)
+        res = (b3, s3)
+        if return_landmarks:
+            lm = torch.empty((n, c2, 5, 2), **f32)
+            N.check(N.lib.dif_mtcnn_landmarks(N.ptr(o3), o3.shape[1], N.ptr(b2_in), N.ptr(keep), n, c2, c2, self.h, self.w,
+                                              N.ptr(lm), st))
+            res += (lm,)
+        return res + (stages,) if return_stages else res
 
 
 class MtcnnDetection:
     """The reference's detector call (``detector/run.py:120-173``): ``detect(img) -> (cropped_images, boxes)``, raising
     ``ValueError("Bounding box not found")`` when nothing passes.  ``model``: an MtcnnDetector built for the image's size
-    (one is created per new size otherwise, with the given weights)."""
+    (one is created per new size otherwise, with the given weights).  ``align=True``: the returned crops are the faces
+    aligned to the ArcFace template at ``size`` x ``size`` (detector/align.py) instead of the box crops; the boxes stay."""
 
-    def __init__(self, margin: int = 8, detect_multiple_faces: bool = False, **kwargs) -> None:
+    def __init__(self, margin: int = 8, detect_multiple_faces: bool = False, align: bool = False, size: int = 112,
+                 **kwargs) -> None:
         self.margin = margin
         self.detect_multiple_faces = detect_multiple_faces
+        self.align, self.size = bool(align), int(size)
         self.weights = kwargs.pop('weights', None)
         self.model = kwargs.pop('model', None)
         self.kwargs = kwargs
@@ -250,41 +268,61 @@ class MtcnnDetection:
         if img.ndim == 2:
             img = _to_rgb(img)
         img = np.ascontiguousarray(img[:, :, 0:3], dtype=np.uint8)
-        boxes, scores = self._model_for(img.shape[0], img.shape[1]).detect(img[None])
-        boxes, scores = boxes[0].cpu().numpy(), scores[0].cpu().numpy()
+        res = self._model_for(img.shape[0], img.shape[1]).detect(img[None], return_landmarks=self.align)
+        boxes, scores = res[0][0].cpu().numpy(), res[1][0].cpu().numpy()
         found = [tuple(b) for b, s in zip(boxes, scores) if s >= 0]
         if not found:
             raise ValueError("Bounding box not found")
         if not self.detect_multiple_faces:
             found = found[:1]
-        return filter_bounding_box(Image.fromarray(img), found, self.margin, self.detect_multiple_faces)
+        crops, bbs = filter_bounding_box(Image.fromarray(img), found, self.margin, self.detect_multiple_faces)
+        if self.align:
+            lm = res[2][0][res[1][0] >= 0][:len(found)]
+            aligned = align_faces(img[None], lm, self.size, k=len(found))
+            crops = list(aligned.cpu().numpy())
+        return crops, bbs
 
 
 class MtcnnFramePipeline:
     """Raw frames -> MTCNN -> best face per frame -> crop -> embedding -> top-1 gallery match on the device (BASELINE
-    configs[4] as worded; the YOLOv3-face twin is run.FramePipeline)."""
+    configs[4] as worded; the YOLOv3-face twin is run.FramePipeline).  ``align=True``: the crop is the best face aligned to
+    the ArcFace template by its five landmarks (detector/align.py) instead of the box crop with a margin."""
 
-    def __init__(self, detector: MtcnnDetector, embedder, gallery=None, margin: int = 8, distance_metric: int = 1):
+    def __init__(self, detector: MtcnnDetector, embedder, gallery=None, margin: int = 8, distance_metric: int = 1,
+                 align: bool = False):
         self.detector, self.embedder, self.gallery = detector, embedder, gallery
-        self.margin, self.metric = margin, distance_metric
+        self.margin, self.metric, self.align = margin, distance_metric, bool(align)
         self.crop_size = embedder.input_shape[0]
 
     def detect(self, frames: torch.Tensor):
-        """-> (boxes [N, 4] left, top, right, bottom of the best face; NaN where nothing passed, scores [N])."""
+        """-> (boxes [N, 4] left, top, right, bottom of the best face; NaN where nothing passed, scores [N]); with
+        ``align=True`` also its landmarks [N, 5, 2] (NaN where nothing passed)."""
         mb = self.detector.max_batch
-        parts = [self.detector.detect(frames[lo:lo + mb]) for lo in range(0, frames.shape[0], mb)]
+        parts = [self.detector.detect(frames[lo:lo + mb], return_landmarks=self.align) for lo in range(0, frames.shape[0], mb)]
         b, s = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
         best, sc = b[:, 0, :], s[:, 0]
         found = sc >= 0
-        return torch.where(found[:, None], best, torch.full_like(best, float('nan'))), torch.where(found, sc, torch.zeros_like(sc))
+        res = (torch.where(found[:, None], best, torch.full_like(best, float('nan'))), torch.where(found, sc, torch.zeros_like(sc)))
+        if self.align:
+            lm = torch.cat([p[2] for p in parts])[:, 0]
+            res += (torch.where(found[:, None, None], lm, torch.full_like(lm, float('nan'))),)
+        return res
+
+    def crops(self, frames: torch.Tensor):
+        """-> (boxes, scores, crops uint8 [N, size, size, 3] as the embedder is given them; black where nothing passed)."""
+        from .run import crop_faces
+        if self.align:
+            boxes, scores, lm = self.detect(frames)
+            return boxes, scores, align_faces(frames, lm, self.crop_size)
+        boxes, scores = self.detect(frames)
+        return boxes, scores, crop_faces(frames, boxes, self.margin, self.crop_size)
 
     def __call__(self, frames):
-        from .run import crop_faces
         dev = N.require_device()
         t = torch.from_numpy(np.ascontiguousarray(frames)) if not torch.is_tensor(frames) else frames
         t = t.to(dev).contiguous()
-        boxes, scores = self.detect(t)
-        emb = self.embedder.embed(crop_faces(t, boxes, self.margin, self.crop_size))
+        boxes, scores, crops = self.crops(t)
+        emb = self.embedder.embed(crops)
         if self.gallery is None:
             return boxes, scores, emb
         idx, dist = self.gallery.match(emb, self.metric)

@@ -137,6 +137,45 @@ int dif_mtcnn_rescore(const float* out_dev, int slots, int ld, float threshold, 
 int dif_crop_resize_multi(const uint8_t* frames_dev, int n, int h, int w, const float* boxes_ltrb_dev, const float* valid_dev,
                           int k, float margin, uint8_t* out_dev, int size, void* stream);
 
+/* ------------------------------------------------------------------ five-point landmark alignment (csrc/align.hip)
+ * O-Net's landmarks -> similarity transform onto the ArcFace five-point template -> aligned crop, on the device.  The
+ * reference aligns on the host (api.py:132-145: cv2.getAffineTransform + cv2.warpAffine).  PARITY WITH cv2.warpAffine IS
+ * UNPINNED: cv2 quantises coordinates to 1/32 pixel and weighs in 15-bit fixed point; what is pinned (and tested bit for
+ * bit against a NumPy restatement) is this float32 arithmetic, without fused multiply-add:
+ *   sx = (m00 x + m01 y) + m02, sy = (m10 x + m11 y) + m12;  x0 = floor(sx), fx = sx - x0 (y likewise);
+ *   taps p00 = pix(x0, y0), p01 = pix(x0 + 1, y0), p10 = pix(x0, y0 + 1), p11 = pix(x0 + 1, y0 + 1) as float;
+ *   top = p00 + (p01 - p00) fx, bot = p10 + (p11 - p10) fx, v = top + (bot - top) fy, out = min(max(floor(v + 0.5), 0), 255).
+ * Matrix direction: DESTINATION -> SOURCE, a row-major 2 x 3 matrix [m00 m01 m02 m10 m11 m12] takes an output pixel index
+ *   (x, y) to a frame position (cv2.warpAffine with WARP_INVERSE_MAP, or the inverse of the matrix cv2 is usually given).
+ * Pixel convention: integer pixel indices are the sample positions (cv2's), no half-pixel offset.
+ * Border: constant zero -- a tap outside the frame contributes 0.0; a pixel whose 2 x 2 footprint lies wholly outside the
+ *   frame, or whose sx / sy is not finite, is 0.
+ * NaN rule: a crop whose matrix holds a NaN (or an infinity) is black.
+ *
+ * dif_warp_affine: frames_dev uint8 [n_frames][h][w][3]; matrices_dev float [n_frames * k][6]; k crops per frame -- crop j
+ *   reads frame j / k; out_dev uint8 [n_frames * k][out_h][out_w][3].
+ * dif_align_crop: the matrix of each crop is fitted in the same launch from its five landmarks (landmarks_dev float
+ *   [n_frames * k][5][2], (x, y) in frame pixels) and five template points in output pixels (template_host: 10 floats ON
+ *   THE HOST, x0 y0 ... x4 y4; NULL = the standard ArcFace 112 x 112 template (38.2946, 51.6963), (73.5318, 51.5014),
+ *   (56.0252, 71.7366), (41.5493, 92.3655), (70.7299, 92.2041) times size / 112): the least-squares similarity (rotation,
+ *   uniform scale, translation, no reflection -- Umeyama in 2-D, closed form) landmarks -> template, inverted.  valid_dev
+ *   float [n_frames * k] or NULL: a negative value marks an empty slot.  The crop is black and its matrix six NaNs when the
+ *   slot is empty, a landmark is not finite, or the landmarks / the template coincide in one point.  out_dev uint8
+ *   [n_frames * k][size][size][3]; matrices_out_dev float [n_frames * k][6] or NULL: the matrices used (direction as above).
+ * dif_mtcnn_landmarks: the landmarks of the cascade's output slots.  out_dev: O-Net's outputs [n * n_src][ld], ld >= 16
+ *   (logits 2 | box 4 | landmark x 5 | landmark y 5: left eye, right eye, nose, left and right mouth corner, relative to
+ *   the crop the network saw); boxes_dev [n][n_src][4]: the slots' boxes as dif_crop_resize_multi was given them, i.e.
+ *   BEFORE dif_mtcnn_rescore(plain_regression = 1) regresses them in place; keep_dev [n][k]: the last dif_nms's kept slots
+ *   (< 0 = empty -> ten zeros); h, w: the frame's size.  landmarks_dev [n][k][5][2] = (l + ox cw, t + oy ch) where
+ *   (l, t, cw, ch) is the rectangle clamped to the frame and truncated that the crop was cut from -- the library's
+ *   deviation from the published code, which refers to the unclamped box and zero-pads. */
+int dif_warp_affine(const uint8_t* frames_dev, int n_frames, int h, int w, const float* matrices_dev, int k, uint8_t* out_dev,
+                    int out_h, int out_w, void* stream);
+int dif_align_crop(const uint8_t* frames_dev, int n_frames, int h, int w, const float* landmarks_dev, const float* valid_dev, int k,
+                   const float* template_host, uint8_t* out_dev, int size, float* matrices_out_dev, void* stream);
+int dif_mtcnn_landmarks(const float* out_dev, int ld, const float* boxes_dev, const int32_t* keep_dev, int n, int n_src, int k, int h,
+                        int w, float* landmarks_dev, void* stream);
+
 /* ------------------------------------------------------------------ gallery + 1:N match
  * The reference has no 1:N entry point; the semantics are utility.distance broadcast
  * over gallery rows + np.argmin (first minimum).  Housed Python-side under
