@@ -285,19 +285,28 @@ def head_sv2(feat, p, emd):
     return relu(y @ p['norm_embedding/kernel'] + p['norm_embedding/bias'])
 
 
+def _hw_pair(hw):
+    """An int (a square map) or an (h, w) pair -> (h, w)."""
+    if isinstance(hw, (tuple, list)):
+        return int(hw[0]), int(hw[1])
+    return int(hw), int(hw)
+
+
 def head_sv2_spec(cin, hw, emd):
-    h2 = -(-(-(-hw // 2)) // 2)
+    h2, w2 = [-(-(-(-s // 2)) // 2) for s in _hw_pair(hw)]
     return ([('sv2_conv1/kernel', (1, 1, cin, 128)), ('sv2_conv1/bias', (128,)),
              ('sv2_conv2/kernel', (1, 1, 128, 128)), ('sv2_conv2/bias', (128,))] +
             [('bn/' + k, (128,)) for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')] +
-            [('norm_embedding/kernel', (h2 * h2 * 128, emd)), ('norm_embedding/bias', (emd,))])
+            [('norm_embedding/kernel', (h2 * w2 * 128, emd)), ('norm_embedding/bias', (emd,))])
 
 
 def head_gdc_spec(cin, hw, emd):
+    h, w = _hw_pair(hw)
+
     def bn(name, c):
         return [(name + '/' + k, (c,)) for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
     return ([('head_conv/kernel', (1, 1, cin, 512))] + bn('head_bn1', 512) +
-            [('head_prelu/alpha', (512,)), ('head_dw/depthwise_kernel', (hw, hw, 512, 1))] +
+            [('head_prelu/alpha', (512,)), ('head_dw/depthwise_kernel', (h, w, 512, 1))] +
             bn('head_bn2', 512) +
             [('head_pw/kernel', (1, 1, 512, emd)), ('head_dense/kernel', (emd, emd))])
 
@@ -319,10 +328,10 @@ def head_v1(feat, p, emd):
 
 
 def head_v1_spec(cin, hw, emd):
-    h2 = (hw // 2) // 2
+    h2, w2 = [(s // 2) // 2 for s in _hw_pair(hw)]
     return [('v1_conv1/kernel', (2, 2, cin, 64)), ('v1_conv1/bias', (64,)),
             ('v1_conv2/kernel', (2, 2, 64, 32)), ('v1_conv2/bias', (32,)),
-            ('embeddings/kernel', (h2 * h2 * 32, emd)), ('embeddings/bias', (emd,))]
+            ('embeddings/kernel', (h2 * w2 * 32, emd)), ('embeddings/bias', (emd,))]
 
 
 # --------------------------------------------------------------------------- IResNet
@@ -410,14 +419,11 @@ def arcmargin_logits(emb, weight, labels=None, s=64.0, m=0.5):
 
 # --------------------------------------------------------------------------- whole models
 def model_spec(arch, emd=512, input_hw=112, head='v2'):
-    """Ordered (name, shape) list for a full embedding model."""
+    """Ordered (name, shape) list for a full embedding model; ``input_hw`` is an int (square input) or (h, w)."""
     if arch == 'resnet':
-        hw = input_hw
-        for _ in range(2):
-            hw = -(-hw // 2)
-        for (_, _, s) in RESNET50V2_STACKS:
-            if s == 2:
-                hw = -(-hw // 2)
+        hw = _hw_pair(input_hw)
+        for _ in range(2 + sum(s == 2 for (_, _, s) in RESNET50V2_STACKS)):
+            hw = tuple(-(-s // 2) for s in hw)
         spec = resnet50v2_spec()
         if head == 'v2':
             spec += head_gdc_spec(2048, hw, emd)
@@ -429,7 +435,7 @@ def model_spec(arch, emd=512, input_hw=112, head='v2'):
     if arch in ('vgg16', 'mobilenet'):
         spec = vgg16_spec() if arch == 'vgg16' else mobilenetv2_spec()
         cfeat = 512 if arch == 'vgg16' else 1280
-        hw = input_hw // 32 if arch == 'vgg16' else -(-input_hw // 32)
+        hw = tuple(s // 32 if arch == 'vgg16' else -(-s // 32) for s in _hw_pair(input_hw))
         if head == 'v2':
             spec += head_gdc_spec(cfeat, hw, emd)
         elif head == 'v1':
@@ -438,7 +444,7 @@ def model_spec(arch, emd=512, input_hw=112, head='v2'):
             spec += head_sv2_spec(cfeat, hw, emd)
         return spec
     if arch in IRESNET_LAYERS:
-        return iresnet_spec(arch, emd=emd, final_hw=input_hw // 16)
+        return iresnet_spec(arch, emd=emd, final_hw=_hw_pair(input_hw)[0] // 16)
     if arch == 'nn4':
         return nn4_spec(emd)
     raise ValueError(arch)

@@ -86,7 +86,8 @@ def _yolo_params(num_classes=1):
 
 
 def _frames(n, hw, seed=0):
-    return np.random.default_rng(seed).integers(0, 256, (n, hw, hw, 3), dtype=np.uint8).astype(np.float32) / np.float32(255)
+    h, w = hw if isinstance(hw, tuple) else (hw, hw)
+    return np.random.default_rng(seed).integers(0, 256, (n, h, w, 3), dtype=np.uint8).astype(np.float32) / np.float32(255)
 
 
 def test_yolov3_structure_matches_the_cfg():
@@ -112,6 +113,34 @@ def test_yolov3_oracle_vs_torch():
     assert [t.shape for t in a] == [(1, 3, 3, 18), (1, 6, 6, 18), (1, 12, 12, 18)]
     for u, v in zip(a, b):
         np.testing.assert_allclose(u, v, rtol=2e-3, atol=2e-4 * np.abs(v).max())
+
+
+@pytest.mark.parametrize('hw', [(64, 160), (160, 64)])
+def test_yolov3_oracle_vs_torch_nonsquare(hw):
+    """H != W (multiples of 32): three maps H/32 x W/32, H/16 x W/16, H/8 x W/8 through the upsample + concat routes."""
+    from oracle import torch_nets as torch_ref
+    p = _yolo_params()
+    x = _frames(2, hw, seed=4)
+    a = odet.yolov3_forward(x, p)
+    b = torch_ref.yolov3(x, p)
+    assert [t.shape for t in a] == [(2, hw[0] // s, hw[1] // s, 18) for s in (32, 16, 8)]
+    for u, v in zip(a, b):
+        np.testing.assert_allclose(u, v, rtol=2e-3, atol=2e-4 * np.abs(v).max())
+
+
+def test_yolov3_gate_rejects_one_transposed_layer():
+    """The detector maps' gate (nonsquare_gates.check_map) against the oracle with one mid-network 3x3 kernel's spatial
+    axes transposed: every one of the three maps is rejected."""
+    import nonsquare_gates as gates
+    p = _yolo_params()
+    x = _frames(1, (64, 160), seed=5)
+    want = odet.yolov3_forward(x, p)
+    name = [n for n, s in odet.yolov3_spec(1) if n.endswith('/kernel') and s[:2] == (3, 3) and s[2] == 128][2]
+    slipped = odet.yolov3_forward(x, gates.transposed(p, name))
+    for u, v in zip(slipped, want):
+        gates.check_map(v.copy(), v)
+        with pytest.raises(AssertionError):
+            gates.check_map(u, v)
 
 
 @pytest.mark.gpu
