@@ -1,6 +1,7 @@
 // conv_wino_kernel: Winograd F(2x2, 3x3) for the large-batch 3x3 / stride 1 / pad 1 layers on small even maps (IResNet's
-// 14 x 14 stage); conv_winow_kernel, further down: the same arithmetic for the wider maps (28 x 28 .. 112 x 112) in
-// half-size blocks, option "wino" = 2.  Included by conv.hip (inside namespace dif, after the helpers it uses).
+// 14 x 14 stage); conv_winow_kernel, further down: the same arithmetic in half-size blocks, two per CU -- option "wino" = 2
+// runs the wider maps (28 x 28 .. 112 x 112) AND these small maps in that shape (launch_conv_wino), level 1 keeps
+// conv_wino_kernel on the small maps.  Included by conv.hip (inside namespace dif, after the helpers it uses).
 //
 // A 3x3 convolution of a 4x4 input tile d is Y = A^T [ (G g G^T) .* (B^T d B) ] A: 2x2 outputs from 16 element-wise
 // products, i.e. 16 GEMMs M_c[tile][co] = sum_ci V_c[tile][ci] U_c[ci][co] with K = Cin instead of one with K = 9 Cin --
@@ -47,6 +48,29 @@ __device__ __forceinline__ void wino_input_transform(const float (&d)[16], float
   for (int r = 0; r < 4; ++r) wino_bt4(t[4 * r], t[4 * r + 1], t[4 * r + 2], t[4 * r + 3], v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
 }
 
+// Block trace (ConvArgs::trace, net.hip: option dbg = 256): the TRACE instantiations of both kernels stamp the block's start,
+// the first barrier, the end of the K loop and the end of each epilogue half in 100 MHz ticks; thread 0 writes the eight-word
+// record of the direct kernels with low byte 3: [K loop, set-up, epilogue half 0, epilogue half 1, HW_ID | XCC_ID << 32, start,
+// end, 3 | cycles << 8].  The launchers pick TRACE = false whenever trace is null: that code holds no stamp and no branch
+// on trace (a branch alone moved the register allocation of these kernels, which sit at the 256-VGPR limit).
+template <bool TRACE>
+__device__ __forceinline__ unsigned long long wino_stamp() {
+  if constexpr (TRACE) return __builtin_amdgcn_s_memrealtime();
+  return 0ull;
+}
+__device__ __forceinline__ void wino_trace_write(const ConvArgs& a, unsigned long long c0, const unsigned long long (&ts)[5]) {
+  unsigned long long* t = a.trace + (size_t)blockIdx.x * 8;
+  t[0] = ts[2] - ts[1];
+  t[1] = ts[1] - ts[0];
+  t[2] = ts[3] - ts[2];
+  t[3] = ts[4] - ts[3];
+  t[4] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+  t[5] = ts[0];
+  t[6] = ts[4];
+  t[7] = 3 | ((__builtin_amdgcn_s_memtime() - c0) << 8);
+}
+
+template <bool TRACE>
 __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int blocks_m, int nblocks) {
   extern __shared__ __attribute__((aligned(16))) float wino_smem[];
   const int b = xcd_remap((int)blockIdx.x, nblocks);
@@ -54,6 +78,9 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tw = a.W >> 1, tpi = (a.H >> 1) * tw, ntiles = a.N * tpi;
   const int KS = a.Cin / wino::KC;
+  unsigned long long ts[5];
+  ts[0] = wino_stamp<TRACE>();
+  const unsigned long long tr_c0 = TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
 
   // ---- this thread's tile: the input loader's (two channels) and the epilogue's (four channels) alike
   const int ltile = tid >> 3, cp = tid & 7;
@@ -150,6 +177,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int
     bload(1, 0);
     vstore(wino_smem, d);
     lds_barrier();
+    ts[1] = wino_stamp<TRACE>();
     for (int ks = 0; ks < KS; ++ks) {
       const float* cur = wino_smem + (ks & 1) * wino::STAGE;
       float* nxt = wino_smem + ((ks + 1) & 1) * wino::STAGE;
@@ -165,6 +193,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int
       lds_barrier();
     }
   }
+  ts[2] = wino_stamp<TRACE>();
 
   // ---- epilogue: per 32-channel half, M through LDS, Y = A^T M A, BN / activation / shortcut / second output
   const int c4 = cp * 4;
@@ -229,7 +258,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
     }
     lds_barrier();
+    ts[3 + nf] = wino_stamp<TRACE>();
   }
+  if constexpr (TRACE)
+    if (tid == 0) wino_trace_write(a, tr_c0, ts);
 }
 
 // conv_winow_kernel: the same arithmetic for the wide maps (option "wino" = 2: even maps above 16 x 16 up to 112 x 112 --
@@ -243,6 +275,12 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int
 // layout; the B fragments and the A fragments of a component are fetched two components ahead into two register sets.
 // Every accumulator sums the same products in the same order as conv_wino_kernel's: the block shape changes no bit.
 // <64, 2> is conv_wino_kernel's own shape (one block per CU), kept for A/B runs [dbg bit 65536].
+// At level 2 the small maps (conv_wino_kernel's rule: at most 16 x 16) take the <32, 4> shape as well: with K = 256 .. 512
+// (16 .. 32 K-steps) the fixed part is a smaller share of a block than on the wide maps, but 784 blocks of 64 tiles on 256
+// CUs are 3.06 rounds paid as 4; half blocks halve the quantum: a CU's share of 3.06 full-size blocks of work is paid as
+// 3.5 (seven half blocks) instead of 4.  The
+// epilogue requests each half's shortcut tile and BN / PReLU vectors before M goes to LDS (the operand registers of the
+// K loop are dead by then), so their latency is not paid after the staging barrier.
 template <int TT, int CPW>
 struct WinoW {
   static constexpr int MF = TT / 32;                         // 32-tile row fragments per component
@@ -252,7 +290,7 @@ struct WinoW {
   static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
 };
 
-template <int TT, int CPW>
+template <int TT, int CPW, bool TRACE>
 __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(const ConvArgs a, int blocks_m, int nblocks) {
   using S = WinoW<TT, CPW>;
   constexpr int MF = S::MF, KC = wino::KC;
@@ -262,6 +300,9 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tw = a.W >> 1, tpi = (a.H >> 1) * tw, ntiles = a.N * tpi;
   const int KS = a.Cin / KC;
+  unsigned long long ts[5];
+  ts[0] = wino_stamp<TRACE>();
+  const unsigned long long tr_c0 = TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
 
   // ---- this thread's tile: the input loader's (two channels) and the epilogue's (four channels) alike
   const int ltile = tid >> 3, cp = tid & 7;
@@ -358,6 +399,7 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
     bload(1, 0);
     vstore(wino_smem, d);
     lds_barrier();
+    ts[1] = wino_stamp<TRACE>();
     for (int ks = 0; ks < KS; ++ks) {
       const float* cur = wino_smem + (ks & 1) * S::STAGE;
       float* nxt = wino_smem + ((ks + 1) & 1) * S::STAGE;
@@ -379,6 +421,7 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
       lds_barrier();
     }
   }
+  ts[2] = wino_stamp<TRACE>();
 
   // ---- epilogue: per 32-channel half, M through LDS, Y = A^T M A, BN / activation / shortcut / second output
   const int c4 = cp * 4;
@@ -390,6 +433,20 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
   const int act = a.act, act2 = a.act2;
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
+    // the half's shortcut tile and per-channel vectors are requested first, into the registers the K loop's operands have
+    // left: their latency runs under the LDS round trip of M instead of after it
+    const int c = nt * wino::BN + nf * 32 + c4;
+    const f32x4 sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
+    const f32x4 sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
+    uint32_t voff[4];
+    f32x4 rv[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int pix = pix0 + (p >> 1) * a.W + (p & 1);
+      voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+      rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __builtin_amdgcn_sched_barrier(0);             // (the requests stay above the LDS traffic)
 #pragma unroll
     for (int j = 0; j < CPW; ++j)
 #pragma unroll
@@ -398,7 +455,6 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
         for (int r = 0; r < 16; ++r)
           wino_smem[(CPW * wave + j) * (TT * 32) + (mf * 32 + frag_row(lane, r)) * 32 + r32] = acc[j][mf][nf][r];
     lds_barrier();
-    const int c = nt * wino::BN + nf * 32 + c4;
     f32x4 m[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) m[k] = *reinterpret_cast<const f32x4*>(wino_smem + k * (TT * 32) + ltile * 32 + c4);
@@ -414,16 +470,6 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
       yv[1] = s0[1] - s0[2] - s0[3];
       yv[2] = s1[0] + s1[1] + s1[2];
       yv[3] = s1[1] - s1[2] - s1[3];
-    }
-    const f32x4 sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
-    const f32x4 sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
-    uint32_t voff[4];
-    f32x4 rv[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-      voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-      rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -443,14 +489,18 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
     }
     lds_barrier();
+    ts[3 + nf] = wino_stamp<TRACE>();
   }
+  if constexpr (TRACE)
+    if (tid == 0) wino_trace_write(a, tr_c0, ts);
 }
 
 // The layers the Winograd kernels take: 3x3 / stride 1 / pad 1 on an even map (no output shrink), whole 32-channel input
 // slices, whole 64-channel column blocks, no pre-activation, the lean epilogue's plain geometry and unit-stride shortcut,
-// 31-bit byte offsets.  Returns 1 for conv_wino_kernel: maps of at most 16 x 16 with at least wino::MIN_TILES Winograd
-// tiles (level 1 and up); 2 for conv_winow_kernel: wider maps up to 112 x 112 with the tiles of at least
-// wino::WIDE_MIN_IMAGES images (level 2); 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether
+// 31-bit byte offsets.  Returns 1 for the narrow maps: at most 16 x 16 with at least wino::MIN_TILES Winograd tiles (level 1
+// and up; launch_conv_wino runs them on conv_wino_kernel at level 1 and on conv_winow_kernel<32, 4> at level 2, the same
+// bits); 2 for the wide maps on conv_winow_kernel: up to 112 x 112 with the tiles of at least wino::WIDE_MIN_IMAGES images
+// (level 2); 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether
 // the net carries the transformed weights (Net option "wino") -- on nothing else.
 static int wino_applies(const ConvArgs& a) {
   if (!a.w_wino || a.wino_level < 1 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1) return 0;
@@ -467,29 +517,35 @@ static int wino_applies(const ConvArgs& a) {
   return a.N * tpi >= wino::MIN_TILES ? 1 : 0;
 }
 
-static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {
-  if (allow_dynamic_lds(reinterpret_cast<const void*>(conv_wino_kernel), wino::LDS_BYTES)) return -1;
-  const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
-  const int blocks_m = (int)((ntiles + wino::TT - 1) / wino::TT), tiles_n = a.Cout / wino::BN;
-  const int64_t nblocks = (int64_t)blocks_m * tiles_n;
-  if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
-  hipLaunchKernelGGL(conv_wino_kernel, dim3((unsigned)nblocks), dim3(wino::NT), wino::LDS_BYTES, st, a, blocks_m, (int)nblocks);
-  DIF_HIP(hipGetLastError());
-  g_last_kernel = "conv_wino_kernel<F(2x2,3x3),64 tiles x 64>";
-  return 0;
-}
-
 template <int TT, int CPW>
 static int launch_conv_winow(const ConvArgs& a, hipStream_t st, const char* name) {
   using S = WinoW<TT, CPW>;
-  if (allow_dynamic_lds(reinterpret_cast<const void*>(conv_winow_kernel<TT, CPW>), S::LDS_BYTES)) return -1;
+  const auto kern = a.trace ? conv_winow_kernel<TT, CPW, true> : conv_winow_kernel<TT, CPW, false>;
+  if (allow_dynamic_lds(reinterpret_cast<const void*>(kern), S::LDS_BYTES)) return -1;
   const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
   const int blocks_m = (int)((ntiles + TT - 1) / TT), tiles_n = a.Cout / wino::BN;
   const int64_t nblocks = (int64_t)blocks_m * tiles_n;
   if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
-  hipLaunchKernelGGL((conv_winow_kernel<TT, CPW>), dim3((unsigned)nblocks), dim3(S::NT), S::LDS_BYTES, st, a, blocks_m, (int)nblocks);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(S::NT), S::LDS_BYTES, st, a, blocks_m, (int)nblocks);
   DIF_HIP(hipGetLastError());
   g_last_kernel = name;
+  return 0;
+}
+
+static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {
+  // Level 2 runs the narrow maps in conv_winow_kernel's half-block shape too (the same bits).  The launch is reported
+  // under conv_wino_kernel's name, although the template is conv_winow_kernel: op_table()'s readers tell the narrow-map
+  // layers (level 1's list) from the wide ones by the name's beginning.  [dbg bit 16777216: conv_wino_kernel at level 2, A/B]
+  if (a.wino_level >= 2 && !(a.dbg & 16777216)) return launch_conv_winow<32, 4>(a, st, "conv_wino_kernel<F(2x2,3x3),32 tiles x 64>");
+  const auto kern = a.trace ? conv_wino_kernel<true> : conv_wino_kernel<false>;
+  if (allow_dynamic_lds(reinterpret_cast<const void*>(kern), wino::LDS_BYTES)) return -1;
+  const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
+  const int blocks_m = (int)((ntiles + wino::TT - 1) / wino::TT), tiles_n = a.Cout / wino::BN;
+  const int64_t nblocks = (int64_t)blocks_m * tiles_n;
+  if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(wino::NT), wino::LDS_BYTES, st, a, blocks_m, (int)nblocks);
+  DIF_HIP(hipGetLastError());
+  g_last_kernel = "conv_wino_kernel<F(2x2,3x3),64 tiles x 64>";
   return 0;
 }
 

@@ -1684,13 +1684,16 @@ int Net::embed_clock(const void* xin, int n, int layout, int dtype, float* out, 
   if (rc) return rc;
   if (conv_dbg & 256) {
     // development aid: per convolution, what its blocks did (100 MHz ticks -> us): the launch's span, the blocks' lifetimes,
-    // and for conv_igemm_kernel records the time in mainloops / partial-tile hand-over / epilogues
+    // and for conv_igemm_kernel records the time in mainloops / partial-tile hand-over / epilogues (the Winograd kernels' records:
+    // K loop / set-up / epilogue, one tile per block)
     for (size_t i = 0; i < ops.size(); ++i) {
       if (ops[i].kind != OP_CONV) continue;
       const size_t end = i + 1 < ops.size() ? trace_off[i + 1] : total;
       unsigned long long t_lo = ~0ull, t_hi = 0;
       double life = 0, mn = 1e30, mx = 0, m = 0, f = 0, e = 0, steps = 0, tiles = 0;
       double p_set = 0, p_pro = 0, p_steps = 0, p_hand = 0, p_tiles = 0;
+      double w_e0 = 0, w_e1 = 0;
+      std::map<unsigned long long, std::vector<const unsigned long long*>> w_cu;     // Winograd records by the CU they ran on
       int nb = 0;
       for (size_t b = trace_off[i]; b < end; ++b) {
         const unsigned long long* t = &h[b * 8];
@@ -1716,11 +1719,37 @@ int Net::embed_clock(const void* xin, int n, int layout, int dtype, float* out, 
           steps += (double)t[3];
           tiles += (double)t[4];
         }
+        if ((t[7] & 0xff) == 3) {                          // conv_wino_kernel / conv_winow_kernel: K loop, set-up, the two epilogue halves
+          m += (double)t[0];
+          f += (double)t[1];
+          e += (double)(t[2] + t[3]);
+          w_e0 += (double)t[2];
+          w_e1 += (double)t[3];
+          tiles += 1;
+          w_cu[((t[4] >> 32) & 0xf) << 16 | (t[4] & 0xff00)].push_back(t);        // XCC_ID, SE_ID / SH_ID / CU_ID
+        }
       }
       if (nb)
         fprintf(stderr, "trace %-22s blocks %5d span %7.1f us | life mean %7.1f min %7.1f max %7.1f | main %6.1f fix %6.1f epi %6.1f us/block | "
                         "steps/block %.1f tiles/block %.2f\n", ops[i].name.c_str(), nb, (double)(t_hi - t_lo) / 100.0, life / nb / 100.0,
                 mn / 100.0, mx / 100.0, m / nb / 100.0, f / nb / 100.0, e / nb / 100.0, steps / nb, tiles / nb);
+      if (nb && !w_cu.empty()) {
+        // a block that starts while another of its CU is alive: how far into that block's life it starts (0.5 = the two
+        // co-resident blocks are in opposite phase, 0 = they started together)
+        double ph = 0, lag = 0;
+        int pairs = 0;
+        for (auto& kv : w_cu)
+          for (const unsigned long long* u : kv.second)
+            for (const unsigned long long* v : kv.second)
+              if (v != u && v[5] <= u[5] && u[5] < v[6] && (v[5] < u[5] || v < u)) {
+                ph += (double)(u[5] - v[5]) / (double)(v[6] - v[5]);
+                lag += (double)(u[5] - v[5]);
+                ++pairs;
+              }
+        fprintf(stderr, "      winograd: epilogue halves %.1f + %.1f us/block | %zu CUs, %.2f blocks/CU | blocks starting beside a resident one: %d, "
+                        "%.1f us = %.2f of its life after it\n", w_e0 / nb / 100.0, w_e1 / nb / 100.0, w_cu.size(), (double)nb / w_cu.size(), pairs,
+                pairs ? lag / pairs / 100.0 : 0.0, pairs ? ph / pairs : 0.0);
+      }
       if (nb && p_tiles > 0)
         fprintf(stderr, "      pipelined: %.2f tiles/block | per tile: set-up %.2f prologue %.2f K-steps %.2f hand-over %.2f us\n", p_tiles / nb,
                 p_set / p_tiles / 100.0, p_pro / p_tiles / 100.0, p_steps / p_tiles / 100.0, p_hand / p_tiles / 100.0);
@@ -1791,7 +1820,7 @@ int Net::embed_clock(const void* xin, int n, int layout, int dtype, float* out, 
   for (size_t b = 0; b < total; ++b) {
     const unsigned long long* t = &h[b * 8];
     const unsigned kind = (unsigned)(t[7] & 0xff);
-    if ((kind == 1 || kind == 2) && t[6] > t[5]) {
+    if ((kind == 1 || kind == 2) && t[6] > t[5]) {     // (not the Winograd records, kind 3: the figure keeps its meaning across rounds)
       cyc += (double)(t[7] >> 8);
       ticks += (double)(t[6] - t[5]);
     }
