@@ -98,7 +98,8 @@ int dif_gallery_destroy(dif_gallery* h) {
   if (g.ninv) (void)hipFree(g.ninv);
   for (void* p : {(void*)g.part_key, (void*)g.part_cnt, (void*)g.part_idx, (void*)g.eps, (void*)g.eps32, (void*)g.best,
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
-                  (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags})
+                  (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
+                  (void*)g.within_thr})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -305,6 +306,21 @@ int dif_match(dif_gallery* h, const float* probes_dev, int n, int metric, int64_
   if (n == 0) return 0;
   if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match: null pointer");
   return match_run(&h->g, probes_dev, n, metric, idx_out_dev, dist_out_dev, key_out_dev, (hipStream_t)stream);
+}
+
+int dif_match_within(dif_gallery* h, const float* probes_dev, int n, int metric, float tolerance, int max_hits,
+                     int64_t* count_out_dev, int64_t* idx_out_dev, float* dist_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_within: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_within: negative probe count");
+  if (max_hits < 0 || max_hits > DIF_WITHIN_MAX_HITS)
+    return set_error("dif_match_within: max_hits %d outside [0, %d]", max_hits, DIF_WITHIN_MAX_HITS);
+  if (tolerance != tolerance) return set_error("dif_match_within: the tolerance is NaN");
+  if (n == 0) return 0;
+  if (!probes_dev || !count_out_dev) return set_error("dif_match_within: null pointer");
+  if (max_hits > 0 && (!idx_out_dev || !dist_out_dev)) return set_error("dif_match_within: null list pointer with max_hits > 0");
+  return within_run(&h->g, probes_dev, n, metric, tolerance, max_hits, count_out_dev, idx_out_dev, dist_out_dev,
+                    (hipStream_t)stream);
 }
 
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,

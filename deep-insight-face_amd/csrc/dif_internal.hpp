@@ -59,6 +59,11 @@ struct Gallery {
   int bd_fill = 1;                 // "bd_fill": blocks of match_bd_kernel per resident slot (development: no effect measured, r04)
   bool no_bd = false;              // dif_gallery_set_option "bd" = 0: the split-bf16 filter stays on match_tile_kernel for every batch
   bool clamp_nan = false;          // report distance 0 / 1 instead of the reference's NaN (dif_gallery_set_option)
+  // range-search workspace (csrc/match_within.hip), apart from dif_match's; every buffer grows against a capacity of its own
+  unsigned short* within_census = nullptr;   // [gallery tile][probe]: rows surely within the tolerance | borderline rows << 8
+  size_t within_census_cap = 0;              // ... in 16-bit words
+  float* within_thr = nullptr;               // per probe: {key <= [0]: sure, key > [1]: out, |key| >= [2]: borderline, [3] != 0: resolve all}
+  size_t within_thr_cap = 0;                 // ... in probes
 };
 
 int gallery_norms(Gallery* g, const float* src, hipStream_t st);   // src: the caller's rows (copied into g->rows in the same pass), or null
@@ -66,6 +71,8 @@ int gallery_split_copy(Gallery* g, hipStream_t st);   // (re)builds rows2 when t
 int gallery_update_rows(Gallery* g, const float* src, int64_t first, int64_t count, int64_t old_n, hipStream_t st);   // rows [first, first+count) <- src
 int match_run(Gallery* g, const float* probes, int B, int metric, int64_t* idx_out, float* dist_out,
               float* key_out, hipStream_t st);
+int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
+               int64_t* idx_out, float* dist_out, hipStream_t st);
 int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D, int metric, float* out,
                  hipStream_t st);
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,

@@ -1,0 +1,311 @@
+// Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within).
+// hipcc-flags: -ffp-contract=off
+// (the resolve stage restates the reference's float32 operations one by one, as match.hip's re-rank does)
+//
+// Semantics, per probe q (evaluation/utility.py:52-66 broadcast over the gallery rows, then three lines of NumPy):
+//   dist = distance(q[None, :], gallery, metric);  hits = np.flatnonzero(dist <= t)      (NaN <= t is False)
+//   count = len(hits);  idx = hits[:K] + index_base;  dist = dist[hits[:K]];  unused slots: idx -1, dist NaN
+// The B x G distances are never materialised.  The tolerance is known before the first tile, so -- unlike the arg-min -- there
+// is no running state: two stages, no atomics on global memory, no lists, no overflow path, deterministic by construction.
+//
+//  1. within_census_kernel -- a sibling of match_tile_kernel<T, false>: the same tiles, the same f32 MFMA main loop on the
+//     rows themselves, the same XCD-aware block order, the same search key in the epilogue
+//        metric 1: key = -dot / |g|        metric 0: key = |g|^2 - 2 dot
+//     -- classifies every key against two per-probe thresholds (within_prep_kernel):
+//        SURE        key <= T - E  and |key| < H      the reference's distance is <= t whatever the rounding
+//        OUT         key >  T + E                     ... is > t (or NaN) whatever the rounding
+//        BORDERLINE  everything else, a NaN key included (rows kept out of the filter carry a NaN ingredient: zero-norm,
+//                    tiny, huge and non-finite rows reach the reference arithmetic this way; GalleryFlags is not needed)
+//     and stores, per (gallery tile of 128 rows, probe), one 16-bit word  sure | borderline << 8.  Every tile belongs to
+//     exactly one block: nothing is accumulated in global memory.
+//  2. within_resolve_kernel -- one block per probe walks that probe's words in ascending tile order.  A tile with a
+//     borderline row, or with any sure row while the list still has room, is evaluated row by row with ref_distance
+//     (match_ref.hpp: bit-identical to the reference for metric 0; metric 1 up to the arccos caveat of dif_match) and
+//     `dist <= t` decides; its hits are counted and appended in row order.  Any other tile adds its sure count, no memory
+//     touched.  A probe outside the bound's validity resolves every tile.
+//
+// The thresholds (u = 2^-24; E_key = match_ref.hpp's bound on |key - exact key| with c = D u for the f32 MFMA):
+//   metric 1.  The reference's similarity s_ref = fl(dot / fl(|q| |g|)) -- float32 products, NumPy's pairwise sums (at most
+//     25 roundings on a term's way into a sum of up to 8192 terms: 18 in its leaf of <= 128, 6 levels of the tree, 1 for the
+//     product), two square roots, a product, a quotient -- lies within (25 + 2 (12.5 + 1) + 2) u = 54 u of the exact
+//     s = q.g / (|q| |g|).  The reported distance fl(fl(acos(s_ref)) / fl(pi)) is a non-increasing function of s_ref with
+//     at most 3 u of relative error, so `dist <= t` holds iff s_ref >= s* for an s* within pi 3 u < 10 u of cos(pi t).
+//     T = -|q| cos(pi t) is formed in double from |q|^2 summed as an fma chain over 64 lanes (relative error of |q| below
+//     (D / 128 + 4) u) and rounded once (u).  Hence  W1 = (96 + D / 64) u |q|  covers reference, arccos and T together, and
+//        E = (c + 8 u) |q| + W1.
+//     t >= 1: every distance that is not NaN is <= 1 <= t: T = +inf;  t < 0: no distance is: T = -inf.
+//     A similarity within 54 u of +-1 may round beyond it and is NaN in the reference (not a hit; with "clamp_nan" 0 or 1 is
+//     compared instead): a key with |key| >= H = |q| (1 - anti), anti = 2e-4 + 1.01 (c + 136 u) -- match.hip's net around
+//     -1, widened by the key's own error and used on both sides -- is never SURE.  (OUT needs no such care: NaN is not a
+//     hit, and a clamped distance of 1 is a hit only for t >= 1, where nothing is OUT.)
+//   metric 0.  dist_ref = pairwise sum of fl(fl(q - g)^2): each term within 3 u, the sum within 25 u more:
+//     |dist_ref - |q - g|^2| <= 28 u (|q| + |g|)^2.  T = t - |q|^2 with |q|^2 and the rows' |g|^2 each summed over 64 lanes
+//     ((D / 64 + 8) u relative) and T rounded once:
+//        E = u 18 gmax^2 + (2 c + 2 u) |q| gmax  +  32 u (|q| + gmax)^2 + (D / 64 + 8) u (|q|^2 + gmax^2) + u (|t| + |q|^2).
+//   |q| enters as sqrt(sum) * 1.0001 as in probe_eps_one.  Deliberately generous: a wider E only costs resolved tiles.
+//   Probes whose |q|^2 leaves [NORM_LO, NORM_HI] (metric 0: exceeds NORM_HI) or is not finite: every tile is resolved.
+#include "gemm_core.hpp"
+#include "dif_internal.hpp"
+#include "match_ref.hpp"
+
+namespace dif {
+
+constexpr int WITHIN_BM = 128;          // gallery rows per census word: every f32 tile shape of the match has 128-row tiles
+constexpr int WITHIN_NW = 8;            // waves of a resolve block
+constexpr size_t WITHIN_CENSUS_MAX = (size_t)128 << 20;   // census words per launch (256 MB); more probes go in several rounds
+
+__global__ __launch_bounds__(256) void within_prep_kernel(const float* __restrict__ probes, int B, int D, int metric, float t,
+                                                          float cdot, const unsigned* __restrict__ sqmax_bits,
+                                                          f32x4* __restrict__ thr) {
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (p >= B) return;
+  float s = 0.f;
+  for (int k = lane; k < D; k += 64) {
+    const float x = probes[(int64_t)p * D + k];
+    s = fmaf(x, x, s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane != 0) return;
+  const float u = U24, qn = sqrtf(s) * 1.0001f, inf = __builtin_inff();
+  float T, E, H;
+  bool odd;
+  if (metric == 1) {
+    odd = !(s >= NORM_LO && s <= NORM_HI);
+    E = key_err1_rel(cdot) * qn + (96.f + (float)(D / 64)) * u * qn;
+    T = t >= 1.f ? inf : (t < 0.f ? -inf : (float)(-sqrt((double)s) * cos(3.14159265358979323846 * (double)t)));
+    H = sqrtf(s) * (1.f - (2e-4f + 1.01f * (cdot + 136.f * u)));
+  } else {
+    odd = !(s <= NORM_HI);
+    const float gmax = sqrtf(__builtin_bit_cast(float, *sqmax_bits)) * 1.0001f;
+    E = key_err0(cdot, qn, gmax) + 32.f * u * (qn + gmax) * (qn + gmax) +
+        ((float)(D / 64) + 8.f) * u * (qn * qn + gmax * gmax) + u * (fabsf(t) + qn * qn);
+    T = t - s;
+    H = inf;
+  }
+  // (an infinite tolerance under metric 0 makes T - E a NaN: no key is SURE, none is OUT, every tile is resolved)
+  thr[p] = odd ? f32x4{-inf, inf, H, 1.f} : f32x4{T - E, T + E, H, 0.f};
+}
+
+template <class T>
+__global__ __launch_bounds__(T::NT, 2) void within_census_kernel(const float* __restrict__ gallery, int64_t G,
+                                                               const float* __restrict__ probes, int B, int D,
+                                                               const float* __restrict__ aux, int metric,
+                                                               const f32x4* __restrict__ thr,
+                                                               unsigned short* __restrict__ census, int nparts) {
+  constexpr int WM = T::WM, WN = T::WN;
+  static_assert(T::BM == WITHIN_BM, "one census word per 128 gallery rows");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  // block -> (gallery part, probe block) as match_tile_kernel: the probe blocks of one part share an XCD
+  const int cblocks = (B + T::BN - 1) / T::BN;
+  const int grp = (int)blockIdx.x / (8 * cblocks), rem = (int)blockIdx.x % (8 * cblocks);
+  const int part = grp * 8 + (rem & 7), cblk = rem >> 3;
+  if (part >= nparts) return;
+  int* s_cnt = reinterpret_cast<int*>(smem + T::LDS_FLOATS);   // [WGM][BN]: sure | not out << 16, per wave row
+  const int tid = threadIdx.x;
+  const int wc = T::wave_col();
+  const int p0 = cblk * T::BN;
+  const int ksteps = D / BK;
+  const int64_t gtiles = (G + T::BM - 1) / T::BM;
+
+  float ts[WN], tm[WN], hk[WN];
+  int col[WN];
+#pragma unroll
+  for (int n = 0; n < WN; ++n) {
+    col[n] = (wc * WN + n) * 32 + (tid & 31);
+    // (a column that pads the probe block: its words are not stored)
+    const f32x4 v = (p0 + col[n] < B) ? thr[p0 + col[n]] : f32x4{0.f, 0.f, 0.f, 0.f};
+    ts[n] = v[0];
+    tm[n] = v[1];
+    hk[n] = v[2];
+  }
+
+  for (int64_t gt = part; gt < gtiles; gt += nparts) {
+    const int64_t g0 = gt * T::BM;
+    f32x16 acc[WM][WN];
+    zero_acc<T>(acc);
+    RowLoader<T::NA, T::RP> al(gallery + g0 * D, G - g0, D);
+    RowLoader<T::NB, T::RP> bl(probes + (int64_t)p0 * D, (int64_t)B - p0, D);
+    gemm_mainloop<T>(al, bl, 0, ksteps, smem, acc);
+
+    // dots -> keys -> two counts per probe column.  aux[g] = -1/|g| (metric 1) or |g|^2 (metric 0), NaN for the rows kept
+    // out of the filter: a NaN key is neither SURE nor OUT.  Rows past G are OUT (key +inf; where T + E is +inf as well
+    // they count as borderline, and the resolve stage, which stops at G, finds nothing in them).
+    int lane = tid & 63;
+    asm volatile("" : "+v"(lane));                           // opaque per tile, as in match_tile_epilogue: no row index is hoisted
+    const int wr = T::wave_row();
+    const int64_t rows_left = G - g0;
+    const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(aux + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 4));
+    int cs[WN], cn[WN];
+#pragma unroll
+    for (int n = 0; n < WN; ++n) cs[n] = cn[n] = 0;
+#pragma unroll
+    for (int m = 0; m < WM; ++m) {
+      const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {                          // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
+        const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool ok = rbase + 8 * q + j < rows_left;
+#pragma unroll
+          for (int n = 0; n < WN; ++n) {
+            const float dot = acc[m][n][4 * q + j];
+            float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
+            key = ok ? key : __builtin_inff();
+            cs[n] += (key <= ts[n] && fabsf(key) < hk[n]) ? 1 : 0;
+            cn[n] += !(key > tm[n]) ? 1 : 0;
+          }
+        }
+      }
+    }
+    // lanes l and l + 32 hold different rows of the same probe column; the WGM waves stacked on M meet in LDS
+#pragma unroll
+    for (int n = 0; n < WN; ++n) {
+      int v = cs[n] | (cn[n] << 16);
+      v += __shfl_xor(v, 32);
+      if (lane < 32) s_cnt[wr * T::BN + col[n]] = v;
+    }
+    lds_barrier();
+    for (int c = tid; c < T::BN; c += T::NT) {
+      int v = 0;
+#pragma unroll
+      for (int w = 0; w < T::WGM; ++w) v += s_cnt[w * T::BN + c];
+      const int sure = v & 0xffff, bord = (v >> 16) - sure;   // SURE implies not OUT (T - E <= T + E)
+      if (p0 + c < B) census[gt * B + p0 + c] = (unsigned short)(sure | (bord << 8));
+    }
+    // (s_cnt is written again only after the next tile's main loop, i.e. behind several barriers)
+  }
+}
+
+// One block per probe; `census` rows are B words apart.  All control flow is block-uniform: every wave derives the same
+// counts from the same LDS words.
+__global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const unsigned short* __restrict__ census, int64_t G,
+                                                                      int B, const f32x4* __restrict__ thr,
+                                                                      const float* __restrict__ probes,
+                                                                      const float* __restrict__ gallery, int D, int metric,
+                                                                      float t, int clamp, const SumPlan plan, int K,
+                                                                      int64_t index_base, int64_t* __restrict__ count_out,
+                                                                      int64_t* __restrict__ idx_out,
+                                                                      float* __restrict__ dist_out) {
+  constexpr int NT = 64 * WITHIN_NW;
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned short s_word[NT];
+  __shared__ float s_dist[WITHIN_BM];
+  __shared__ unsigned char s_hit[WITHIN_BM];
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* q = probes + (int64_t)p * D;
+  const int64_t gtiles = (G + WITHIN_BM - 1) / WITHIN_BM;
+  const bool all = gtiles > 0 && thr[p][3] != 0.f;
+  int64_t count = 0;                                          // hits so far; the list holds the first min(count, K) of them
+  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
+    s_word[tid] = w;
+    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
+    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
+    for (int j = 0; j < nw; ++j) {
+      const int sure = s_word[j] & 0xff, bord = s_word[j] >> 8;
+      if (!(all || bord > 0 || (sure > 0 && count < K))) {
+        count += sure;
+        continue;
+      }
+      const int64_t g0 = (t0 + j) * WITHIN_BM;
+      const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
+      for (int r = wave; r < rows; r += WITHIN_NW) {
+        float d;
+        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+        if (lane == 0) {
+          s_dist[r] = d;
+          s_hit[r] = d <= t ? 1 : 0;                          // NaN: not a hit
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int h = 0; h < WITHIN_BM / 64; ++h) {
+        const int r = h * 64 + lane;
+        const bool hit = r < rows && s_hit[r] != 0;
+        const unsigned long long mask = __ballot(hit);
+        const int64_t pos = count + __popcll(mask & ((1ull << lane) - 1ull));
+        if (hit && wave == 0 && pos < K) {
+          idx_out[(int64_t)p * K + pos] = g0 + r + index_base;
+          dist_out[(int64_t)p * K + pos] = s_dist[r];
+        }
+        count += __popcll(mask);
+      }
+      __syncthreads();                                        // s_dist / s_hit are rewritten by the next resolved tile
+    }
+    __syncthreads();                                          // s_word is rewritten by the next round
+  }
+  if (tid == 0) count_out[p] = count;
+  for (int64_t i = (count < K ? count : K) + tid; i < K; i += NT) {
+    idx_out[(int64_t)p * K + i] = -1;
+    dist_out[(int64_t)p * K + i] = __builtin_nanf("");
+  }
+}
+
+template <class T>
+static int launch_census(const Gallery* g, const float* probes, int B, int metric, hipStream_t st) {
+  auto kern = within_census_kernel<T>;
+  constexpr int lds = T::LDS_BYTES + T::WGM * T::BN * 4;
+  static bool done[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!done[dev]) {
+    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    done[dev] = true;
+  }
+  const int nparts = match_plan_parts(g, B, false);
+  const int cblocks = (B + T::BN - 1) / T::BN;
+  dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
+  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, g->n, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
+                     reinterpret_cast<const f32x4*>(g->within_thr), g->within_census, nparts);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
+               int64_t* idx_out, float* dist_out, hipStream_t st) {
+  if (B <= 0) return 0;
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  const int clamp = g->clamp_nan ? 1 : 0;
+  if (g->n <= 0) {                                           // np.flatnonzero of an empty array: counts 0, lists all padding
+    hipLaunchKernelGGL(within_resolve_kernel, dim3(B), dim3(64 * WITHIN_NW), 0, st, nullptr, (int64_t)0, B, nullptr, probes,
+                       nullptr, g->d, metric, tolerance, clamp, plan, max_hits, g->index_base, count_out, idx_out, dist_out);
+    DIF_HIP(hipGetLastError());
+    return 0;
+  }
+  const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
+  // probes per round: whole 128-probe blocks whose census stays below WITHIN_CENSUS_MAX words
+  int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
+  if (per < 128) per = 128;
+  if (per > B) per = B;
+  const size_t need_c = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
+  if (need_c > g->within_census_cap || need_t > g->within_thr_cap) {
+    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
+    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
+    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
+  }
+  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int nb = (int)(B - b0 < per ? B - b0 : per);
+    const float* pr = probes + b0 * g->d;
+    hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
+                       g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
+    DIF_HIP(hipGetLastError());
+    const int kind = match_tile_kind(nb);
+    int rc;
+    if (kind == 4 && nb <= 32) rc = launch_census<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st);
+    else if (kind == 1 || nb <= 64) rc = launch_census<Tile<2, 1>>(g, pr, nb, metric, st);
+    else rc = launch_census<Tile<2, 2>>(g, pr, nb, metric, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(within_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
+                       reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
+                       max_hits, g->index_base, count_out + b0, max_hits ? idx_out + b0 * max_hits : nullptr,
+                       max_hits ? dist_out + b0 * max_hits : nullptr);
+    DIF_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+}  // namespace dif

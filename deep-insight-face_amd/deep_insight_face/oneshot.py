@@ -14,6 +14,9 @@ import torch
 from . import _native as N
 
 
+MAX_HITS = 8192   # DIF_WITHIN_MAX_HITS (include/dif.h): the longest list `within` returns per probe
+
+
 class Gallery:
     """Device-resident gallery of enrolled embeddings, [G, d] float32.
 
@@ -141,6 +144,63 @@ class Gallery:
             idx, dist, key = idx.cpu().numpy(), dist.cpu().numpy(), key.cpu().numpy()
         return (idx, dist, key) if return_key else (idx, dist)
 
+    def within_into(self, probes, tolerance, distance_metric, count, idx, dist):
+        """Allocation-free form of `within`: `probes` [B, d] float32 CUDA, results written into the caller's CUDA tensors
+        count [B] int64, idx [B, K] int64 and dist [B, K] float32 (K = max_hits, taken from idx; K may be 0)."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        tolerance = float(tolerance)
+        if tolerance != tolerance:
+            raise ValueError('within: the tolerance is NaN')
+        if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
+            raise ValueError('probes must be a [B, %d] tensor, got %s' % (
+                self.emd_size, tuple(probes.shape) if hasattr(probes, 'shape') else type(probes).__name__))
+        B = probes.shape[0]
+        for name, t, dt in (('probes', probes, torch.float32), ('count', count, torch.int64), ('idx', idx, torch.int64),
+                            ('dist', dist, torch.float32)):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('within_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
+        if count.dim() != 1 or count.shape[0] != B:
+            raise ValueError('within_into: count must have shape [%d], got %s' % (B, tuple(count.shape)))
+        if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] > MAX_HITS:
+            raise ValueError('within_into: idx must have shape [%d, K] with K <= %d, got %s' % (B, MAX_HITS, tuple(idx.shape)))
+        if tuple(dist.shape) != tuple(idx.shape):
+            raise ValueError('within_into: dist must have shape %s, got %s' % (tuple(idx.shape), tuple(dist.shape)))
+        K = idx.shape[1]
+        if B:
+            N.check(N.lib.dif_match_within(self._h, N.ptr(probes), B, distance_metric, tolerance, K, N.ptr(count),
+                                           N.ptr(idx) if K else None, N.ptr(dist) if K else None, N.stream_ptr()))
+
+    def within(self, probes, tolerance, distance_metric=1, max_hits=64):
+        """Range search: every enrolled row whose distance to a probe is <= `tolerance`, exact.
+        -> (count[B] int64, idx[B, K] int64, dist[B, K] float32) with K = max_hits; NumPy in -> NumPy out.
+
+        Per probe q: ``d = evaluation.utility.distance(q[None, :], gallery, metric)``, ``hits = np.flatnonzero(d <= tolerance)``;
+        count = len(hits) (exact, however large), idx = the K lowest hit rows in ascending order (+ index_base), dist their
+        distances; unused slots hold idx -1 and dist NaN.  max_hits=0 returns the counts alone ([B, 0] lists).
+        The tolerance is in the units of utility.distance: metric 0 is the SQUARED L2 distance, metric 1 arccos(sim)/pi.
+        A NaN distance is never a hit: with the default 'clamp_nan' 0 a similarity that rounding pushes beyond +-1 is NaN in
+        the reference -- a probe identical to an enrolled row can miss it this way; set_option('clamp_nan', 1) compares
+        the clamped distance (0 or 1) instead.  An empty gallery gives counts of 0."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        max_hits = int(max_hits)
+        if max_hits < 0 or max_hits > MAX_HITS:
+            raise ValueError('max_hits %d outside [0, %d]' % (max_hits, MAX_HITS))
+        p, was_np = N.to_device_f32(probes, self._dev)
+        if p.dim() == 1:
+            p = p[None, :]
+        if p.dim() != 2 or p.shape[1] != self.emd_size:
+            raise ValueError('probes must be [B, %d], got %s' % (self.emd_size, tuple(p.shape)))
+        B = p.shape[0]
+        count = torch.empty((B,), dtype=torch.int64, device=self._dev)
+        idx = torch.empty((B, max_hits), dtype=torch.int64, device=self._dev)
+        dist = torch.empty((B, max_hits), dtype=torch.float32, device=self._dev)
+        self.within_into(p, tolerance, distance_metric, count, idx, dist)
+        if was_np:
+            count, idx, dist = count.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
+        return count, idx, dist
+
     def close(self):
         if self._h:
             N.lib.dif_gallery_destroy(self._h)
@@ -158,6 +218,17 @@ def match(probes, gallery, distance_metric=1):
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
         return g.match(probes, distance_metric)
+    finally:
+        if g is not gallery:
+            g.close()
+
+
+def within(probes, gallery, tolerance, distance_metric=1, max_hits=64):
+    """One-call form of Gallery.within: per probe, how many gallery rows lie within `tolerance` and the first
+    `max_hits` of them -> (count[B], idx[B, K], dist[B, K])."""
+    g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
+    try:
+        return g.within(probes, tolerance, distance_metric, max_hits)
     finally:
         if g is not gallery:
             g.close()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag" */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within (an addition: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -234,6 +234,31 @@ int dif_gallery_get_stat(dif_gallery* g, const char* key, int64_t* out, void* st
  * key: the reference distance itself, -inf for NaN; comparable across gallery shards. */
 int dif_match(dif_gallery* g, const float* probes_dev, int n, int metric, int64_t* idx_out_dev,
               float* dist_out_dev, float* key_out_dev, void* stream);
+/* range search of n probes [n][d]: every enrolled row within `tolerance` of each probe, exact.  Per probe q
+ *     dist  = utility.distance(q[None, :], gallery, metric)        the reference's float32 values
+ *     hits  = np.flatnonzero(dist <= tolerance)                    inclusive; NaN <= t is False: a NaN distance is never a hit
+ *     count_out_dev[p] = len(hits)                                 exact, however large
+ *     idx_out_dev[p][0 .. K)  = hits[:K] + index_base              the K = max_hits LOWEST rows, ascending (dif_gallery_set's
+ *     dist_out_dev[p][0 .. K) = dist[hits[:K]]                     index_base: global indices, so shard lists concatenate in rank order)
+ *   unused slots hold idx -1 and dist NaN.  max_hits in [0, DIF_WITHIN_MAX_HITS]; with 0 only the counts are produced and the
+ *   two list pointers may be NULL.  An empty gallery gives counts of 0 (not an error); n = 0 is a no-op; a NaN tolerance, a
+ *   max_hits outside the range or a metric other than 0 / 1 fails.
+ * Units: the tolerance is in the units of utility.distance -- metric 0 is the SQUARED L2 distance (a face_distance tolerance
+ *   of 0.6 is 0.36 here), metric 1 is arccos(similarity) / pi in [0, 1].
+ * The distance compared and reported is exactly the one dif_match / dif_pairwise report for that pair: metric 0 bit-identical
+ *   to the reference; metric 1 up to the arccos (evaluated in double and rounded once; NumPy's float32 arccos is within 2 ulp),
+ *   so against NumPy a pair whose distance lies within ~2e-6 of the tolerance may fall on the other side.
+ * NaN rule: with "clamp_nan" 0 (default) a similarity that rounding pushes beyond +-1 is NaN in the reference and NOT a hit --
+ *   that includes a probe identical to an enrolled row whose similarity rounds above 1; with "clamp_nan" 1 the clamped distance
+ *   (0 or 1) is compared and reported.  Zero-norm and non-finite rows or probes follow the same rule: whatever IEEE arithmetic
+ *   gives the reference, and NaN is never a hit.
+ * Costs one pass of the f32 MFMA over the gallery (the stage of dif_match with "filter" = 0) plus the reference arithmetic on
+ *   the 128-row tiles that hold a hit among the first max_hits or a row too close to the tolerance to call; no host
+ *   synchronisation in steady state; its workspace (2 bytes per probe and 128 rows) is apart from dif_match's. */
+#define DIF_WITHIN_MAX_HITS 8192
+int dif_match_within(dif_gallery* g, const float* probes_dev, int n, int metric, float tolerance, int max_hits,
+                     int64_t* count_out_dev /* [n] */, int64_t* idx_out_dev /* [n][max_hits], or NULL when max_hits == 0 */,
+                     float* dist_out_dev /* same shape */, void* stream);
 /* merge R per-shard results laid out [R][n] (after an all-gather): lowest key, then
  * lowest global index -- equals np.argmin over the concatenated gallery */
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,

@@ -1,0 +1,117 @@
+"""Times the gallery range search (Gallery.within) next to the top-1 match on the f32 filter (Gallery.match, "filter" = 0 --
+the same f32 MFMA main loop over the same rows), with HIP events, and writes profiles/within_bench.json.
+
+    python tools/within_bench.py [--out profiles/within_bench.json] [--shape all|big|small] [--repeats 5] [--iters N]
+
+Shapes: 512 probes x 1 M rows x 512-d and 1 probe x 100 k rows x 512-d, metric 1, max_hits 64.  Gallery: identities of four
+near-duplicate rows (centre + 0.05 noise), probes drawn the same way.  Two tolerances: SPARSE (0.2: a probe's own identity,
+a handful of hits) and DENSE (the median distance of a sample: half the gallery hits, the list fills in the first tile and
+every tile with a row too close to the tolerance to call is resolved on the reference arithmetic).  The three calls are timed
+in alternation, `repeats` windows of `iters` calls each after a warm-up of the same calls; median / min / max per call.
+Under `rocprofv3 --kernel-trace --stats -- python tools/within_bench.py --shape big --repeats 1 --iters 3` the per-kernel
+split (within_census_kernel / within_resolve_kernel) comes from the profiler."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'deep-insight-face_amd'))
+from deep_insight_face import oneshot  # noqa: E402
+
+D, K = 512, 64
+
+
+def make(G, B, seed):
+    gen = torch.Generator(device='cuda').manual_seed(seed)
+    nid = max(1, G // 4)
+    centres = torch.randn(nid, D, device='cuda', generator=gen)
+    gal = centres[torch.arange(G, device='cuda') % nid] + 0.05 * torch.randn(G, D, device='cuda', generator=gen)
+    pick = torch.randint(0, nid, (B,), device='cuda', generator=gen)
+    probes = centres[pick] + 0.05 * torch.randn(B, D, device='cuda', generator=gen)
+    return probes.contiguous(), gal.contiguous()
+
+
+def median_distance(probes, gal):
+    p = torch.nn.functional.normalize(probes[:64], dim=1)
+    g = torch.nn.functional.normalize(gal[:20000], dim=1)
+    return float(torch.median(torch.acos((p @ g.T).clamp(-1, 1)) / torch.pi))
+
+
+def window(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def stats(v):
+    v = sorted(v)
+    return {'median_ms': v[len(v) // 2], 'min_ms': v[0], 'max_ms': v[-1]}
+
+
+def run_shape(B, G, repeats, iters):
+    probes, gal_rows = make(G, B, seed=G + B)
+    dense_t = median_distance(probes, gal_rows)
+    gal = oneshot.Gallery(gal_rows)
+    del gal_rows
+    gal.set_option('filter', 0)
+    count = torch.empty(B, dtype=torch.int64, device='cuda')
+    idx = torch.empty((B, K), dtype=torch.int64, device='cuda')
+    dist = torch.empty((B, K), dtype=torch.float32, device='cuda')
+    mi = torch.empty(B, dtype=torch.int64, device='cuda')
+    md = torch.empty(B, dtype=torch.float32, device='cuda')
+    calls = {
+        'match_filter0': lambda: gal.match_into(probes, 1, mi, md),
+        'within_sparse': lambda: gal.within_into(probes, 0.2, 1, count, idx, dist),
+        'within_dense': lambda: gal.within_into(probes, dense_t, 1, count, idx, dist),
+    }
+    hits = {}
+    for name, fn in calls.items():                                   # warm-up: every shape the timed windows use
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        if name != 'match_filter0':
+            hits[name] = {'mean': float(count.double().mean()), 'min': int(count.min()), 'max': int(count.max())}
+    times = {name: [] for name in calls}
+    for _ in range(repeats):
+        for name, fn in calls.items():                               # alternated: drifts of clock and neighbours hit all three
+            times[name].append(window(fn, iters))
+    gal.close()
+    out = {'probes': B, 'rows': G, 'd': D, 'metric': 1, 'max_hits': K, 'iters_per_window': iters, 'windows': repeats,
+           'tolerance': {'within_sparse': 0.2, 'within_dense': dense_t}, 'hits_per_probe': hits}
+    for name in calls:
+        out[name] = stats(times[name])
+    for name in ('within_sparse', 'within_dense'):
+        out[name]['ratio_to_match_filter0'] = out[name]['median_ms'] / out['match_filter0']['median_ms']
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'within_bench.json'))
+    ap.add_argument('--shape', default='all', choices=('all', 'big', 'small'))
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=0, help='calls per window (default: 20 at 1 M rows, 500 at 100 k)')
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'within_bench needs a HIP device'
+    res = {'device': torch.cuda.get_device_name(0), 'shapes': []}
+    if a.shape in ('all', 'big'):
+        res['shapes'].append(run_shape(512, 1_000_000, a.repeats, a.iters or 20))
+    if a.shape in ('all', 'small'):
+        res['shapes'].append(run_shape(1, 100_000, a.repeats, a.iters or 500))
+    for s in res['shapes']:
+        print(json.dumps(s), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+
+
+if __name__ == '__main__':
+    main()
