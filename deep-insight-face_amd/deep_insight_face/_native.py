@@ -50,6 +50,12 @@ SIGNATURES = {
     'dif_align_crop': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, P(c_float), c_void_p, c_int, c_void_p,
                                c_void_p]),
     'dif_mtcnn_landmarks': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'dif_faces_compact': (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dif_crop_resize_list': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int,
+                                     c_void_p]),
+    'dif_align_crop_list': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, P(c_float), c_void_p, c_int,
+                                    c_void_p, c_void_p]),
+    'dif_faces_gather': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'dif_gallery_create': (c_int, [P(c_void_p), c_int]),
     'dif_gallery_destroy': (c_int, [c_void_p]),
     'dif_gallery_set': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),

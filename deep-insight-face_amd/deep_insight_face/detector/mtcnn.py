@@ -286,7 +286,8 @@ class MtcnnDetection:
 class MtcnnFramePipeline:
     """Raw frames -> MTCNN -> best face per frame -> crop -> embedding -> top-1 gallery match on the device (BASELINE
     configs[4] as worded; the YOLOv3-face twin is run.FramePipeline).  ``align=True``: the crop is the best face aligned to
-    the ArcFace template by its five landmarks (detector/align.py) instead of the box crop with a margin."""
+    the ArcFace template by its five landmarks (detector/align.py) instead of the box crop with a margin.  ``faces(frames)``
+    is the same chain for EVERY face of every frame (detector/faces.py)."""
 
     def __init__(self, detector: MtcnnDetector, embedder, gallery=None, margin: int = 8, distance_metric: int = 1,
                  align: bool = False):
@@ -316,6 +317,23 @@ class MtcnnFramePipeline:
             return boxes, scores, align_faces(frames, lm, self.crop_size)
         boxes, scores = self.detect(frames)
         return boxes, scores, crop_faces(frames, boxes, self.margin, self.crop_size)
+
+    def faces(self, frames):
+        """EVERY face of every frame -> ``faces.FrameFaces``: the cascade's slots with score >= 0, frame-major and best
+        first inside a frame, their crops (aligned with ``align=True``), embeddings and -- with a gallery -- top-1 matches.
+        Row ``offsets[f]`` of a frame that holds a face is the face ``__call__`` reports for it.  One host read per call
+        (the number of faces: ``faces.gather_faces``)."""
+        from .faces import gather_faces, embed_and_match
+        dev = N.require_device()
+        t = torch.from_numpy(np.ascontiguousarray(frames)) if not torch.is_tensor(frames) else frames
+        t = t.to(dev).contiguous()
+        mb = self.detector.max_batch
+        parts = [self.detector.detect(t[lo:lo + mb], return_landmarks=self.align) for lo in range(0, t.shape[0], mb)]
+        c2 = self.detector.cap[2]
+        cat = lambda i, tail: torch.cat([p[i] for p in parts]) if parts else torch.empty((0, c2) + tail, dtype=torch.float32, device=dev)
+        found = gather_faces(t, cat(0, (4,)), cat(1, ()), cat(2, (5, 2)) if self.align else None, min_score=0.0, margin=self.margin,
+                             size=self.crop_size, align=self.align)
+        return embed_and_match(found, self.embedder, self.gallery, self.metric)
 
     def __call__(self, frames):
         dev = N.require_device()

@@ -120,7 +120,8 @@ class FramePipeline:
     host: run.py:149-173 -> predictions.py:150-158 -> oneshot).
 
     ``detector``: yolo_v3_face(); ``embedder``: a DifEmbedder whose input transform expects uint8
-    crops; ``gallery``: oneshot.Gallery or None."""
+    crops; ``gallery``: oneshot.Gallery or None.  ``faces(frames)`` is the same chain for EVERY face of every frame
+    (detector/faces.py)."""
 
     def __init__(self, detector, embedder, gallery=None, margin: int = 8, score: float = 0.4, anchors=ANCHORS,
                  num_classes: int = 1, distance_metric: int = 1):
@@ -150,6 +151,42 @@ class FramePipeline:
         best = torch.where(found[:, None], best, torch.full_like(best, float('nan')))
         sc = torch.where(found, scores[torch.arange(n, device=dev), idx, 0], torch.zeros((), device=dev))
         return best, sc
+
+    def detect_slots(self, frames: torch.Tensor, k: int):
+        """Up to ``k`` faces per frame as slots -> (boxes [N, k, 4] left, top, right, bottom, scores [N, k]); the
+        suppression's pick order (best first), -1 where nothing was kept."""
+        n, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+        maps = self.detector.embed(yolo.letterbox_batch(frames, self.det_size))
+        boxes, scores = yolo._decode(maps, self.anchors, self.num_classes, (h, w))
+        ntot = boxes.shape[1]
+        dev = boxes.device
+        keep = torch.empty((n, self.num_classes, k), dtype=torch.int32, device=dev)
+        cnt = torch.empty((n, self.num_classes), dtype=torch.int32, device=dev)
+        ws = torch.empty((n * self.num_classes * ntot,), dtype=torch.uint8, device=dev)
+        N.check(N.lib.dif_nms(N.ptr(boxes), N.ptr(scores), n, ntot, self.num_classes, k, float(self.score), 0.5,
+                              N.ptr(ws), N.ptr(keep), N.ptr(cnt), N.stream_ptr()))
+        kept = keep[:, 0, :]                                    # class 0, as detect
+        found = kept >= 0
+        idx = kept.clamp(min=0).long()
+        sb = torch.gather(boxes, 1, idx[:, :, None].expand(n, k, 4))[:, :, [1, 0, 3, 2]]
+        ss = torch.gather(scores[:, :, 0], 1, idx)
+        return torch.where(found[:, :, None], sb, torch.full_like(sb, -1.0)), torch.where(found, ss, torch.full_like(ss, -1.0))
+
+    def faces(self, frames, max_faces_per_frame: int = 16):
+        """EVERY face of every frame, up to ``max_faces_per_frame`` each -> ``faces.FrameFaces``: frame-major, best first
+        inside a frame, with crops, embeddings and -- with a gallery -- top-1 matches.  Row ``offsets[f]`` of a frame that
+        holds a face is the face ``__call__`` reports for it.  One host read per call (the number of faces:
+        ``faces.gather_faces``)."""
+        from .faces import gather_faces, embed_and_match
+        k = int(max_faces_per_frame)
+        if k < 1:
+            raise ValueError('max_faces_per_frame must be positive')
+        dev = N.require_device()
+        t = torch.from_numpy(np.ascontiguousarray(frames)) if not torch.is_tensor(frames) else frames
+        t = t.to(dev).contiguous()
+        boxes, scores = self.detect_slots(t, k)
+        found = gather_faces(t, boxes, scores, min_score=0.0, margin=self.margin, size=self.crop_size)
+        return embed_and_match(found, self.embedder, self.gallery, self.metric)
 
     def __call__(self, frames):
         dev = N.require_device()

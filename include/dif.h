@@ -176,6 +176,41 @@ int dif_align_crop(const uint8_t* frames_dev, int n_frames, int h, int w, const 
 int dif_mtcnn_landmarks(const float* out_dev, int ld, const float* boxes_dev, const int32_t* keep_dev, int n, int n_src, int k, int h,
                         int w, float* landmarks_dev, void* stream);
 
+/* ------------------------------------------------------------------ every face in a frame (csrc/faces.hip)
+ * The detectors fill a fixed number of slots per frame (k; score -1 = an empty slot).  These entry points turn the slots
+ * of a batch into one dense list of faces, so that the crop, the embedder and the match run on the M faces that are
+ * there and not on n * k slots (deep_insight_face.detector.faces: gather_faces, FramePipeline.faces,
+ * MtcnnFramePipeline.faces).  The reference's counterpart is detect_multiple_faces (detector/run.py:63-87), per image
+ * on the host.
+ * dif_faces_compact: scores_dev float [n][k] -> the slots with score >= min_score (inclusive; a NaN score is no face).
+ *   ORDER: frame-major, and inside a frame in slot order -- the detector's pick order, best score first -- so the list
+ *   is deterministic (one block scans the slots; no atomics).  offsets_dev int32 [n + 1]: exclusive prefix sum of the
+ *   faces per frame (CSR: the faces of frame f are entries offsets[f] .. offsets[f + 1] - 1), never truncated;
+ *   count_dev int32 [1] = offsets[n], the exact total; frame_dev / slot_dev int32 [max_faces]: frame and slot of the
+ *   first max_faces faces, the entries after them -1 (both may be NULL when max_faces = 0).  n = 0 writes count = 0 and
+ *   offsets[0] = 0 (scores_dev may be NULL).  Nothing comes back to the host: a caller that sizes its buffers by the
+ *   total reads count_dev once (4 bytes, ONE synchronisation per batch -- the only one of the path); a caller that
+ *   cannot wait passes max_faces = n * k buffers and runs the list forms below over all of them (-1 entries are inert).
+ *   k < 1, max_faces < 0, n * k >= 2^31 - 1024 or a NULL pointer fail.
+ * In the list forms below, frame_dev / slot_dev int32 [m] name one slot per output row; an entry outside [0, n) x
+ *   [0, k) (-1 by convention) reads nothing.  m = 0 is a no-op.
+ * dif_crop_resize_list: out_dev uint8 [m][size][size][3]; crop j is bit-identical to crop frame[j] * k + slot[j] of
+ *   dif_crop_resize_multi(frames, n, h, w, boxes [n][k][4], NULL, k, margin, ...); a -1 entry gives a black crop.
+ * dif_align_crop_list: crop j and matrix j (matrices_out_dev float [m][6] or NULL) are bit-identical to those of slot
+ *   frame[j] * k + slot[j] of dif_align_crop(frames, n, h, w, landmarks [n][k][5][2], NULL, k, template_host, ...); a
+ *   -1 entry gives a black crop and six NaNs.
+ * dif_faces_gather: dst_dev float [m][row_floats] <- row frame[j] * k + slot[j] of src_dev float [n][k][row_floats]
+ *   (boxes: 4, scores: 1, landmarks: 10); a -1 entry gives zeros. */
+int dif_faces_compact(const float* scores_dev, int n, int k, float min_score, int max_faces, int32_t* count_dev, int32_t* offsets_dev,
+                      int32_t* frame_dev, int32_t* slot_dev, void* stream);
+int dif_crop_resize_list(const uint8_t* frames_dev, int n, int h, int w, const float* boxes_ltrb_dev, int k, const int32_t* frame_dev,
+                         const int32_t* slot_dev, int m, float margin, uint8_t* out_dev, int size, void* stream);
+int dif_align_crop_list(const uint8_t* frames_dev, int n, int h, int w, const float* landmarks_dev, int k, const int32_t* frame_dev,
+                        const int32_t* slot_dev, int m, const float* template_host, uint8_t* out_dev, int size, float* matrices_out_dev,
+                        void* stream);
+int dif_faces_gather(const float* src_dev, int row_floats, int n, int k, const int32_t* frame_dev, const int32_t* slot_dev, int m,
+                     float* dst_dev, void* stream);
+
 /* ------------------------------------------------------------------ gallery + 1:N match
  * The reference has no 1:N entry point; the semantics are utility.distance broadcast
  * over gallery rows + np.argmin (first minimum).  Housed Python-side under
