@@ -1,3 +1,5 @@
+// hipcc-flags: -ffp-contract=fast-honor-pragmas
+// (build.py compiles with -ffp-contract=fast, which disregards `#pragma clang fp contract(off)`; box_iou below needs it)
 // YOLOv3-face post-processing on the device: the box decode of
 // deep_insight_face/detector/yolov3.py:36-106 (yolo_head, correct_boxes, boxes_and_scores) and
 // the per-class score filter + greedy non-max suppression of :122-172 (get_yolo_output, which
@@ -62,8 +64,12 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const YoloArgs a) {
   }
 }
 
-// IoU with the corner normalisation of tf.image.non_max_suppression
+// IoU with the corner normalisation of tf.image.non_max_suppression, every product rounded to float32 before it is added:
+// contracted, the union became fma(-ih, iw, ap + aq), one rounding fewer than the float32 statement the tests compare
+// with, and an IoU that lands exactly on the threshold was suppressed.  The pragma holds because this file is compiled with
+// -ffp-contract=fast-honor-pragmas (first line); everything else in it contracts as before.
 __device__ __forceinline__ float box_iou(const float* p, const float* q) {
+#pragma clang fp contract(off)
   const float py0 = fminf(p[0], p[2]), py1 = fmaxf(p[0], p[2]), px0 = fminf(p[1], p[3]), px1 = fmaxf(p[1], p[3]);
   const float qy0 = fminf(q[0], q[2]), qy1 = fmaxf(q[0], q[2]), qx0 = fminf(q[1], q[3]), qx1 = fmaxf(q[1], q[3]);
   const float ap = (py1 - py0) * (px1 - px0), aq = (qy1 - qy0) * (qx1 - qx0);
@@ -92,7 +98,10 @@ __global__ __launch_bounds__(NT) void nms_kernel(const float* __restrict__ boxes
   const float* sc = scores + (int64_t)n * ntot * C + c;
   uint8_t* al = alive + ((int64_t)n * C + c) * ntot;
   int* out = keep_idx + ((int64_t)n * C + c) * max_boxes;
-  for (int i = tid; i < ntot; i += NT) al[i] = sc[(int64_t)i * C] >= score_thr ? 1 : 0;   // mask = box_scores >= thr
+  for (int i = tid; i < ntot; i += NT) {   // mask = box_scores >= thr; NaN and -inf never take part (nms_reg_kernel's rule)
+    const float v = sc[(int64_t)i * C];
+    al[i] = (v >= score_thr && v > -__builtin_inff()) ? 1 : 0;
+  }
   for (int i = tid; i < max_boxes; i += NT) out[i] = -1;
   __syncthreads();
   int kept = 0;
@@ -176,7 +185,7 @@ __global__ __launch_bounds__(NT) void nms_reg_kernel(const float* __restrict__ b
     b[j][0] = b[j][1] = b[j][2] = b[j][3] = 0.f;
     if (i < ntot) {
       const float v = sc[i];
-      if (v >= score_thr) S(j) = v;                        // NaN scores never take part, as in nms_kernel
+      if (v >= score_thr) S(j) = v;                        // NaN scores never take part, as in nms_kernel; -inf is the dead mark
       const f32x4 q = *reinterpret_cast<const f32x4*>(bx + (int64_t)i * 4);
       b[j][0] = q[0];
       b[j][1] = q[1];

@@ -84,7 +84,9 @@ int dif_threshold_counts(const float* dist_dev, const uint8_t* issame_dev, const
  * dif_nms: per (image, class) keep boxes with score >= score_threshold and run the greedy
  * suppression of tf.image.non_max_suppression (get_yolo_output :149-160): keep_idx_dev
  * [n_images][n_classes][max_boxes] (box indices in pick order, -1 padded), keep_count_dev
- * [n_images][n_classes]; alive_ws_dev = n_images*n_classes*n_boxes bytes of scratch. */
+ * [n_images][n_classes]; alive_ws_dev = n_images*n_classes*n_boxes bytes of scratch.  A box whose score is NaN or
+ * -inf never takes part, whatever score_threshold is (-inf included), as tf.image.non_max_suppression admits only
+ * score > score_threshold.  boxes_dev must be 16-byte aligned (a box is read as one 4-float vector). */
 int dif_yolo_decode(const float* const* feats_dev, const int32_t* grid_hw_host, const float* anchors_host,
                     int n_layers, int n_images, int n_classes, int input_h, int input_w,
                     const float* image_shape_dev, float* boxes_dev, float* scores_dev, void* stream);

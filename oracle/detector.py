@@ -73,8 +73,8 @@ def _iou(a, b):
 def non_max_suppression(boxes, scores, max_output_size, iou_threshold):
     """Greedy NMS with tf.image.non_max_suppression's ordering: highest score first, equal
     scores by lower index; a candidate is dropped when its IoU with an already selected box is
-    > iou_threshold."""
-    order = sorted(range(len(scores)), key=lambda i: (-float(scores[i]), i))
+    > iou_threshold.  A NaN or -inf score never takes part (TF admits only score > score_threshold; dif_nms: the same)."""
+    order = sorted((i for i in range(len(scores)) if scores[i] > -np.inf), key=lambda i: (-float(scores[i]), i))
     keep = []
     for i in order:
         if len(keep) >= max_output_size:
