@@ -810,6 +810,23 @@ __device__ __forceinline__ f32x4 load4_or(const float* p, int c, float dflt) {
   return f32x4{dflt, dflt, dflt, dflt};
 }
 
+// The lean epilogues' arithmetic on four channels of one pixel: v = act(x * sc + sh) (+ res), v2 = act2(v * sc2 + sh2).
+// The activations are selects between values computed unconditionally: act / act2 are uniform, no branch per element.
+__device__ __forceinline__ void epilogue4(f32x4 x, f32x4 sc, f32x4 sh, f32x4 al, int act, bool has_res, f32x4 res,
+                                          f32x4 sc2, f32x4 sh2, f32x4 al2, int act2, f32x4& v, f32x4& v2) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float t = fmaf(x[e], sc[e], sh[e]);
+    const float tr = fmaxf(t, 0.f), tp = t >= 0.f ? t : t * al[e];
+    t = act == ACT_RELU ? tr : (act == ACT_PRELU ? tp : (act == ACT_RELU6 ? fminf(tr, 6.f) : t));
+    if (has_res) t += res[e];
+    v[e] = t;
+    float u = fmaf(t, sc2[e], sh2[e]);
+    const float ur = fmaxf(u, 0.f), up = u >= 0.f ? u : u * al2[e];
+    v2[e] = act2 == ACT_RELU ? ur : (act2 == ACT_PRELU ? up : (act2 == ACT_RELU6 ? fminf(ur, 6.f) : u));
+  }
+}
+
 // The shortcut tile of one output tile, in the epilogue's thread mapping (16 bytes per lane along
 // the channel axis).  Loaded either from the mainloop's tail hook (latency hidden behind the last
 // K-step) or at the start of the epilogue.
@@ -1028,17 +1045,7 @@ __device__ __forceinline__ void conv_epilogue_fast(const ConvArgs& a, f32x16 (&a
     for (int j = 0; j < CH; ++j) {
       const f32x4 av = *reinterpret_cast<const f32x4*>(srow + (i0 + j) * RPP * CS);
       f32x4 v, v2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float t = fmaf(av[e], sc[e], sh[e]);
-        const float tr = fmaxf(t, 0.f), tp = t >= 0.f ? t : t * al[e];
-        t = act == ACT_RELU ? tr : (act == ACT_PRELU ? tp : (act == ACT_RELU6 ? fminf(tr, 6.f) : t));
-        if (has_res) t += rv[j][e];
-        v[e] = t;
-        float u = fmaf(t, sc2[e], sh2[e]);
-        const float ur = fmaxf(u, 0.f), up = u >= 0.f ? u : u * al2[e];
-        v2[e] = act2 == ACT_RELU ? ur : (act2 == ACT_PRELU ? up : (act2 == ACT_RELU6 ? fminf(ur, 6.f) : u));
-      }
+      epilogue4(av, sc, sh, al, act, has_res, rv[j], sc2, sh2, al2, act2, v, v2);
       if constexpr (YSUB) {
         int img, rr, ho, wo;
         a.fd_howo.divmod(voff[j] == OOB ? 0 : prow[j], img, rr);
@@ -2110,7 +2117,9 @@ static int sk2_plan(const ConvArgs& a) {
   const int KS = a.Kpad / BK;
   const int64_t cus = num_cus();
   if (tiles >= 2 * cus || KS < 2 * SK2_MIN_KS) return 0;
-  if (const int force = (a.dbg >> 16) & 63) return force == 1 ? 0 : (force <= KS / SK2_MIN_KS ? force : 0);   // (dbg bits 16..21: S for every candidate layer, 1 = no split: the S sweep)
+  // (dbg bits 16..21: S >= 2 for every candidate layer, the S sweep.  The value 1 -- bit 65536 alone -- is not read here: it
+  // is the Winograd block-shape A/B (conv_winograd.hpp) and must change no bit; option "sk2" = 0 is the "no split" switch)
+  if (const int force = (a.dbg >> 16) & 63; force >= 2) return force <= KS / SK2_MIN_KS ? force : 0;
   const int64_t cap = (int64_t)a.sk_max_blocks * (int64_t)conv_slab_floats() / 4096;   // slabs the workspace holds
   // S minimising  rounds(S) x share(S) + 0.1 S  in K-steps: rounds = blocks on the busiest CU (blocks are dealt evenly --
   // sk_item -- and co-resident blocks share the CU's matrix pipes, so their K-steps add up), share = K-steps per block, and

@@ -1,7 +1,5 @@
-// conv_wino_kernel: Winograd F(2x2, 3x3) for the large-batch 3x3 / stride 1 / pad 1 layers on small even maps (IResNet's
-// 14 x 14 stage); conv_winow_kernel, further down: the same arithmetic in half-size blocks, two per CU -- option "wino" = 2
-// runs the wider maps (28 x 28 .. 112 x 112) AND these small maps in that shape (launch_conv_wino), level 1 keeps
-// conv_wino_kernel on the small maps.  Included by conv.hip (inside namespace dif, after the helpers it uses).
+// conv_wino_kernel: Winograd F(2x2, 3x3) for the large-batch 3x3 / stride 1 / pad 1 layers on even maps -- one kernel
+// template in three block shapes (WinoW, below).  Included by conv.hip (inside namespace dif, after the helpers it uses).
 //
 // A 3x3 convolution of a 4x4 input tile d is Y = A^T [ (G g G^T) .* (B^T d B) ] A: 2x2 outputs from 16 element-wise
 // products, i.e. 16 GEMMs M_c[tile][co] = sum_ci V_c[tile][ci] U_c[ci][co] with K = Cin instead of one with K = 9 Cin --
@@ -9,27 +7,54 @@
 // the host in double and rounded once (net.hip: finalize, ConvArgs::w_wino).  The products differ from the direct fma
 // chain: the per-layer error is about twice the direct path's (tools/winograd_error.py, profiles/r06_winograd_error.txt).
 //
-// Block: 64 Winograd tiles (numbered linearly over image x tile grid, so a block may span images) x 64 output channels
-// x all 16 components, eight waves; wave w owns components 2w and 2w+1 (two 32-tile x two 32-channel fragments each:
-// 128 accumulators per lane).  Per K-step of 16 input channels every thread fetches one 4x4 input tile of two channels
-// (zero halo from out-of-range buffer loads), forms its 16 V values and writes them to LDS ([component][tile][16 ch],
-// 16-byte chunks XOR-swizzled by tile); two such stages alternate, one barrier per K-step.  A operands come from LDS, B
-// operands (U in fragment order: 1 KB per wave instruction) straight from L2 into registers, one K-step ahead.  The
-// epilogue stages M in LDS one 32-channel half at a time, applies A^T M A and conv_epilogue_fast's arithmetic.
+// Block: TT Winograd tiles (numbered linearly over image x tile grid, so a block may span images) x 64 output channels
+// x all 16 components on 16 / CPW waves; wave w owns components CPW w .. CPW w + CPW - 1 (TT / 32 row fragments x two
+// 32-channel column fragments each: 128 accumulators per lane in every shape).  Per K-step of 16 input channels every
+// thread fetches one 4x4 input tile of two channels (zero halo from out-of-range buffer loads), forms its 16 V values and
+// writes them to LDS ([component][tile][16 ch], 16-byte chunks XOR-swizzled by tile); two such stages alternate, one
+// barrier per K-step.  A operands come from LDS, B operands (U in fragment order: 1 KB per wave instruction) straight
+// from L2; both sit in two register sets, component j in set j & 1, fetched two components ahead (B across the K-step
+// boundary).  The epilogue stages M in LDS one 32-channel half at a time, applies A^T M A and epilogue4 (conv.hip).
+// Every accumulator sums the same products in the same order in every shape: the block shape changes no bit.
 namespace wino {
-constexpr int TT = 64;                         // Winograd tiles per block
 constexpr int BN = 64;                         // output channels per block
 constexpr int KC = 16;                         // input channels per K-step
-constexpr int NT = 512;                        // threads per block
-constexpr int STAGE = 16 * TT * KC;            // floats per V stage (64 KiB)
-constexpr int LDS_BYTES = 2 * STAGE * 4;       // two stages; the epilogue's M half (16 x 64 x 32 floats) fits the same
 // fewest Winograd tiles per launch (a pure function of the layer shape and the batch): 64 images of 14 x 14.  Below it
 // the layer stays on the direct kernels -- the split-K / one-image paths of the small batches among them
 constexpr int64_t MIN_TILES = 64 * 49;
-// the wide maps (conv_winow_kernel, level 2): map sides up to 112, and at least 128 images per launch
+// the wide maps (level 2): map sides up to 112, and at least 128 images per launch
 constexpr int WIDE_MAX_HW = 112;
 constexpr int64_t WIDE_MIN_IMAGES = 128;
 }  // namespace wino
+
+// The block shapes.
+// <64, 2, 1, false>: 64 tiles on eight waves, 128 KiB of LDS, one block per CU -- the narrow maps (at most 16 x 16: IResNet's
+//   14 x 14 stage) at option "wino" = 1 [and at level 2 under dbg bit 16777216, A/B].  K = 256 .. 512 is 16 .. 32 K-steps,
+//   which cover the fixed part of a block (set-up: first tile fetch, transform, barrier; epilogue: two LDS round trips of
+//   M, output transform, stores).
+// <32, 4, 2, true>: half the block, 32 tiles on four waves, 64 KiB -- two blocks per CU, so one block's epilogue and set-up
+//   run under the other's MFMAs and a K-step barrier holds four waves instead of eight.  The price is U traffic from L2
+//   per MFMA doubled (a B fragment feeds one row fragment, not two).  Level 2 runs everything in this shape.  The wide
+//   maps (above 16 x 16 up to 112 x 112: IResNet's 28 x 28, 56 x 56 and 112 x 112 stages) have 128 or 64 input channels: a
+//   K loop of 8 or 4 steps leaves set-up and epilogue uncovered for a third to a half of a full-size block's life.  On the
+//   narrow maps the fixed part is a smaller share, but 784 blocks of 64 tiles on 256 CUs are 3.06 rounds paid as 4; half
+//   blocks halve the quantum: a CU's share of 3.06 full-size blocks of work is paid as 3.5 (seven half blocks).
+// <64, 2, 2, true>: the full-size block on the wide maps, kept for A/B runs [dbg bit 65536].
+// EARLY_REQ: the epilogue requests each half's shortcut tile and BN / PReLU vectors before M goes to LDS (the operand
+// registers of the K loop are dead by then), so their latency is not paid after the staging barrier; the level 1 shape
+// requests them after the output transform, as it always has.
+template <int TT_, int CPW_, int MIN_BLOCKS_, bool EARLY_REQ_>
+struct WinoW {
+  static constexpr int TT = TT_;                             // Winograd tiles per block
+  static constexpr int CPW = CPW_;                           // components per wave
+  static constexpr int MIN_BLOCKS = MIN_BLOCKS_;             // blocks per CU the launch bound asks for
+  static constexpr bool EARLY_REQ = EARLY_REQ_;
+  static constexpr int MF = TT / 32;                         // 32-tile row fragments per component
+  static constexpr int NT = 16 / CPW * 64;                   // threads per block (NT / 8 == TT: one tile x two channels each)
+  static constexpr int STAGE = 16 * TT * wino::KC;           // floats per V stage
+  static constexpr int LDS_BYTES = 2 * STAGE * 4;            // the epilogue's M half (16 x TT x 32 floats) fits the same
+  static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
+};
 
 // B^T x for one 4-vector: (x0 - x2, x1 + x2, x2 - x1, x1 - x3)
 __device__ __forceinline__ void wino_bt4(float x0, float x1, float x2, float x3, float& o0, float& o1, float& o2, float& o3) {
@@ -48,10 +73,10 @@ __device__ __forceinline__ void wino_input_transform(const float (&d)[16], float
   for (int r = 0; r < 4; ++r) wino_bt4(t[4 * r], t[4 * r + 1], t[4 * r + 2], t[4 * r + 3], v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
 }
 
-// Block trace (ConvArgs::trace, net.hip: option dbg = 256): the TRACE instantiations of both kernels stamp the block's start,
-// the first barrier, the end of the K loop and the end of each epilogue half in 100 MHz ticks; thread 0 writes the eight-word
-// record of the direct kernels with low byte 3: [K loop, set-up, epilogue half 0, epilogue half 1, HW_ID | XCC_ID << 32, start,
-// end, 3 | cycles << 8].  The launchers pick TRACE = false whenever trace is null: that code holds no stamp and no branch
+// Block trace (ConvArgs::trace, net.hip: option dbg = 256): the TRACE instantiations stamp the block's start, the first
+// barrier, the end of the K loop and the end of each epilogue half in 100 MHz ticks; thread 0 writes the eight-word record
+// of the direct kernels with low byte 3: [K loop, set-up, epilogue half 0, epilogue half 1, HW_ID | XCC_ID << 32, start,
+// end, 3 | cycles << 8].  The launcher picks TRACE = false whenever trace is null: that code holds no stamp and no branch
 // on trace (a branch alone moved the register allocation of these kernels, which sit at the 256-VGPR limit).
 template <bool TRACE>
 __device__ __forceinline__ unsigned long long wino_stamp() {
@@ -70,230 +95,9 @@ __device__ __forceinline__ void wino_trace_write(const ConvArgs& a, unsigned lon
   t[7] = 3 | ((__builtin_amdgcn_s_memtime() - c0) << 8);
 }
 
-template <bool TRACE>
-__global__ __launch_bounds__(512, 1) void conv_wino_kernel(const ConvArgs a, int blocks_m, int nblocks) {
-  extern __shared__ __attribute__((aligned(16))) float wino_smem[];
-  const int b = xcd_remap((int)blockIdx.x, nblocks);
-  const int nt = b / blocks_m, mt = b - nt * blocks_m;   // column-slice-major: an XCD's blocks share one slice of U in its L2
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tw = a.W >> 1, tpi = (a.H >> 1) * tw, ntiles = a.N * tpi;
-  const int KS = a.Cin / wino::KC;
-  unsigned long long ts[5];
-  ts[0] = wino_stamp<TRACE>();
-  const unsigned long long tr_c0 = TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
-
-  // ---- this thread's tile: the input loader's (two channels) and the epilogue's (four channels) alike
-  const int ltile = tid >> 3, cp = tid & 7;
-  const int g = mt * wino::TT + ltile;
-  const bool tile_ok = g < ntiles;
-  int pix0 = 0;                                  // first output pixel (2 ty, 2 tx) of the tile, linear over N x H x W
-  unsigned vmask = 0;                            // in-range points of the 4x4 input tile
-  if (tile_ok) {
-    const int img = g / tpi, rem = g - img * tpi, ty = rem / tw, tx = rem - ty * tw;
-    pix0 = (img * a.H + 2 * ty) * a.W + 2 * tx;
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      const int iy = 2 * ty - 1 + (p >> 2), ix = 2 * tx - 1 + (p & 3);
-      if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) vmask |= 1u << p;
-    }
-  }
-  const int row_b = a.W * a.Cin * 4, pix_b = a.Cin * 4;
-  // byte offset of point (0, 0) of the tile (one row and column before pix0; only in-range points are ever added to it)
-  const int lbase = (pix0 - a.W - 1) * pix_b + cp * 8;
-  const __amdgpu_buffer_rsrc_t xrs = make_rsrc(a.x, (uint32_t)a.N * (uint32_t)(a.H * a.W) * (uint32_t)pix_b);
-  auto dload = [&](int ks, f32x2 (&d)[16]) {
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      const uint32_t off = ((vmask >> p) & 1u) ? (uint32_t)(lbase + (p >> 2) * row_b + (p & 3) * pix_b + ks * (wino::KC * 4)) : OOB;
-      d[p] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(xrs, off, 0, 0));
-    }
-  };
-  const int vdst = ltile * wino::KC + (((cp >> 1) ^ ((ltile >> 2) & 3)) << 2) + (cp & 1) * 2;
-  auto vstore = [&](float* buf, const f32x2 (&d)[16]) {
-    float d0[16], d1[16], v0[16], v1[16];
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      d0[p] = d[p][0];
-      d1[p] = d[p][1];
-    }
-    wino_input_transform(d0, v0);
-    wino_input_transform(d1, v1);
-#pragma unroll
-    for (int c = 0; c < 16; ++c) *reinterpret_cast<f32x2*>(buf + c * (wino::TT * wino::KC) + vdst) = f32x2{v0[c], v1[c]};
-  };
-
-  // ---- operands of this wave's two components
-  const int h = lane >> 5, r32 = lane & 31, sw = (r32 >> 2) & 3;
-  const int tiles_n = a.Cout / wino::BN;
-  const __amdgpu_buffer_rsrc_t wrs = make_rsrc(a.w_wino, a.w_wino_bytes);
-  uint32_t boff[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) boff[j] = (uint32_t)(((2 * wave + j) * tiles_n + nt) * KS) * 4096u + (uint32_t)lane * 16u;
-  f32x4 bw[2][2][2];                             // [component][column fragment][k quad]
-  auto bload = [&](int j, int ks) {
-#pragma unroll
-    for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) bw[j][nf][q] = buf_load4(wrs, boff[j] + (uint32_t)ks * 4096u + (uint32_t)(nf * 2 + q) * 1024u);
-  };
-  // lane half h consumes channels 8 h + 4 q + t of the K-step in sub-step s = 4 q + t (U is stored in the same order)
-  int aoff[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) aoff[q] = r32 * wino::KC + (((2 * h + q) ^ sw) << 2);
-  f32x4 av[2][2][2];                             // [component][row fragment][k quad]
-  auto aread = [&](const float* buf, int j) {
-#pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        av[j][mf][q] = *reinterpret_cast<const f32x4*>(buf + (2 * wave + j) * (wino::TT * wino::KC) + mf * 32 * wino::KC + aoff[q]);
-  };
-  f32x16 acc[2][2][2];                           // [component][row fragment][column fragment]
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-      for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][mf][nf][r] = 0.f;
-  auto mfma = [&](int j) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-          for (int nf = 0; nf < 2; ++nf)
-            acc[j][mf][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j][mf][q][t], bw[j][nf][q][t], acc[j][mf][nf], 0, 0, 0);
-  };
-
-  // ---- main loop
-  {
-    f32x2 d[16];
-    dload(0, d);
-    bload(0, 0);
-    bload(1, 0);
-    vstore(wino_smem, d);
-    lds_barrier();
-    ts[1] = wino_stamp<TRACE>();
-    for (int ks = 0; ks < KS; ++ks) {
-      const float* cur = wino_smem + (ks & 1) * wino::STAGE;
-      float* nxt = wino_smem + ((ks + 1) & 1) * wino::STAGE;
-      const bool more = ks + 1 < KS;
-      if (more) dload(ks + 1, d);
-      aread(cur, 0);
-      aread(cur, 1);
-      mfma(0);
-      if (more) bload(0, ks + 1);
-      mfma(1);
-      if (more) bload(1, ks + 1);
-      if (more) vstore(nxt, d);
-      lds_barrier();
-    }
-  }
-  ts[2] = wino_stamp<TRACE>();
-
-  // ---- epilogue: per 32-channel half, M through LDS, Y = A^T M A, BN / activation / shortcut / second output
-  const int c4 = cp * 4;
-  const uint32_t bytes = (uint32_t)a.M * (uint32_t)a.Cout * 4u;
-  const __amdgpu_buffer_rsrc_t y_rsrc = make_rsrc(a.y, a.y ? bytes : 0u);
-  const __amdgpu_buffer_rsrc_t y2_rsrc = make_rsrc(a.y2, a.y2 ? bytes : 0u);
-  const __amdgpu_buffer_rsrc_t res_rsrc = make_rsrc(a.res, a.res ? bytes : 0u);
-  const bool has_res = a.res != nullptr;
-  const int act = a.act, act2 = a.act2;
-#pragma unroll
-  for (int nf = 0; nf < 2; ++nf) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          wino_smem[(2 * wave + j) * (wino::TT * 32) + (mf * 32 + frag_row(lane, r)) * 32 + r32] = acc[j][mf][nf][r];
-    lds_barrier();
-    const int c = nt * wino::BN + nf * 32 + c4;
-    f32x4 m[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m[k] = *reinterpret_cast<const f32x4*>(wino_smem + k * (wino::TT * 32) + ltile * 32 + c4);
-    f32x4 yv[4];                                  // outputs (0,0), (0,1), (1,0), (1,1) of the tile
-    {
-      f32x4 s0[4], s1[4];
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        s0[jj] = m[jj] + m[4 + jj] + m[8 + jj];
-        s1[jj] = m[4 + jj] - m[8 + jj] - m[12 + jj];
-      }
-      yv[0] = s0[0] + s0[1] + s0[2];
-      yv[1] = s0[1] - s0[2] - s0[3];
-      yv[2] = s1[0] + s1[1] + s1[2];
-      yv[3] = s1[1] - s1[2] - s1[3];
-    }
-    const f32x4 sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
-    const f32x4 sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
-    uint32_t voff[4];
-    f32x4 rv[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-      voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-      rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      f32x4 v, v2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float t = fmaf(yv[p][e], sc[e], sh[e]);
-        const float tr = fmaxf(t, 0.f), tp = t >= 0.f ? t : t * al[e];
-        t = act == ACT_RELU ? tr : (act == ACT_PRELU ? tp : (act == ACT_RELU6 ? fminf(tr, 6.f) : t));
-        if (has_res) t += rv[p][e];
-        v[e] = t;
-        float u = fmaf(t, sc2[e], sh2[e]);
-        const float ur = fmaxf(u, 0.f), up = u >= 0.f ? u : u * al2[e];
-        v2[e] = act2 == ACT_RELU ? ur : (act2 == ACT_PRELU ? up : (act2 == ACT_RELU6 ? fminf(ur, 6.f) : u));
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
-    }
-    lds_barrier();
-    ts[3 + nf] = wino_stamp<TRACE>();
-  }
-  if constexpr (TRACE)
-    if (tid == 0) wino_trace_write(a, tr_c0, ts);
-}
-
-// conv_winow_kernel: the same arithmetic for the wide maps (option "wino" = 2: even maps above 16 x 16 up to 112 x 112 --
-// IResNet's 28 x 28, 56 x 56 and 112 x 112 stages).  Those layers have 128 or 64 input channels, so a block's K loop is 8 or
-// 4 steps and conv_wino_kernel's one block per CU leaves its set-up (first tile fetch, transform, barrier) and its epilogue
-// (two LDS round trips of M, output transform, stores) uncovered for a third to a half of the block's life.  This kernel's
-// default shape is half the block: TT = 32 tiles x 64 channels on four waves, wave w owning components 4w .. 4w+3 (one
-// 32-tile x two 32-channel fragments each: again 128 accumulators per lane), 64 KiB of LDS -- two blocks per CU, so one
-// block's epilogue and set-up run under the other's MFMAs and a K-step barrier holds four waves instead of eight.  The
-// price is U traffic from L2 per MFMA doubled (a B fragment feeds one row fragment, not two).  U keeps conv_wino_kernel's
-// layout; the B fragments and the A fragments of a component are fetched two components ahead into two register sets.
-// Every accumulator sums the same products in the same order as conv_wino_kernel's: the block shape changes no bit.
-// <64, 2> is conv_wino_kernel's own shape (one block per CU), kept for A/B runs [dbg bit 65536].
-// At level 2 the small maps (conv_wino_kernel's rule: at most 16 x 16) take the <32, 4> shape as well: with K = 256 .. 512
-// (16 .. 32 K-steps) the fixed part is a smaller share of a block than on the wide maps, but 784 blocks of 64 tiles on 256
-// CUs are 3.06 rounds paid as 4; half blocks halve the quantum: a CU's share of 3.06 full-size blocks of work is paid as
-// 3.5 (seven half blocks) instead of 4.  The
-// epilogue requests each half's shortcut tile and BN / PReLU vectors before M goes to LDS (the operand registers of the
-// K loop are dead by then), so their latency is not paid after the staging barrier.
-template <int TT, int CPW>
-struct WinoW {
-  static constexpr int MF = TT / 32;                         // 32-tile row fragments per component
-  static constexpr int NT = 16 / CPW * 64;                   // threads per block (NT / 8 == TT: one tile x two channels each)
-  static constexpr int STAGE = 16 * TT * wino::KC;           // floats per V stage
-  static constexpr int LDS_BYTES = 2 * STAGE * 4;            // the epilogue's M half (16 x TT x 32 floats) fits the same
-  static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
-};
-
-template <int TT, int CPW, bool TRACE>
-__global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(const ConvArgs a, int blocks_m, int nblocks) {
-  using S = WinoW<TT, CPW>;
-  constexpr int MF = S::MF, KC = wino::KC;
+template <class S, bool TRACE>
+__global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const ConvArgs a, int blocks_m, int nblocks) {
+  constexpr int TT = S::TT, CPW = S::CPW, MF = S::MF, KC = wino::KC;
   extern __shared__ __attribute__((aligned(16))) float wino_smem[];
   const int b = xcd_remap((int)blockIdx.x, nblocks);
   const int nt = b / blocks_m, mt = b - nt * blocks_m;   // column-slice-major: an XCD's blocks share one slice of U in its L2
@@ -433,20 +237,24 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
   const int act = a.act, act2 = a.act2;
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
-    // the half's shortcut tile and per-channel vectors are requested first, into the registers the K loop's operands have
-    // left: their latency runs under the LDS round trip of M instead of after it
     const int c = nt * wino::BN + nf * 32 + c4;
-    const f32x4 sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
-    const f32x4 sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
+    // The half's per-channel vectors and shortcut tile are requested in one of two places (S::EARLY_REQ).  The requests are
+    // written out at both: behind a lambda, a member or a free function the 32-tile shape spilled to scratch and the traced
+    // 64-tile kernels went from 254 to 256 VGPRs (profiles/r09_wino_unified_isa.txt).
+    f32x4 sc, sh, al, sc2, sh2, al2, rv[4];
     uint32_t voff[4];
-    f32x4 rv[4];
+    if constexpr (S::EARLY_REQ) {
+      // into the registers the K loop's operands have left: the latency runs under the LDS round trip of M, not after it
+      sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
+      sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-      voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-      rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int p = 0; p < 4; ++p) {
+        const int pix = pix0 + (p >> 1) * a.W + (p & 1);
+        voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+        rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      __builtin_amdgcn_sched_barrier(0);           // (the requests stay above the LDS traffic)
     }
-    __builtin_amdgcn_sched_barrier(0);             // (the requests stay above the LDS traffic)
 #pragma unroll
     for (int j = 0; j < CPW; ++j)
 #pragma unroll
@@ -471,20 +279,20 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
       yv[2] = s1[0] + s1[1] + s1[2];
       yv[3] = s1[1] - s1[2] - s1[3];
     }
+    if constexpr (!S::EARLY_REQ) {
+      sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
+      sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int pix = pix0 + (p >> 1) * a.W + (p & 1);
+        voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+        rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       f32x4 v, v2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float t = fmaf(yv[p][e], sc[e], sh[e]);
-        const float tr = fmaxf(t, 0.f), tp = t >= 0.f ? t : t * al[e];
-        t = act == ACT_RELU ? tr : (act == ACT_PRELU ? tp : (act == ACT_RELU6 ? fminf(tr, 6.f) : t));
-        if (has_res) t += rv[p][e];
-        v[e] = t;
-        float u = fmaf(t, sc2[e], sh2[e]);
-        const float ur = fmaxf(u, 0.f), up = u >= 0.f ? u : u * al2[e];
-        v2[e] = act2 == ACT_RELU ? ur : (act2 == ACT_PRELU ? up : (act2 == ACT_RELU6 ? fminf(ur, 6.f) : u));
-      }
+      epilogue4(yv[p], sc, sh, al, act, has_res, rv[p], sc2, sh2, al2, act2, v, v2);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
     }
@@ -498,10 +306,10 @@ __global__ __launch_bounds__((WinoW<TT, CPW>::NT), 2) void conv_winow_kernel(con
 // The layers the Winograd kernels take: 3x3 / stride 1 / pad 1 on an even map (no output shrink), whole 32-channel input
 // slices, whole 64-channel column blocks, no pre-activation, the lean epilogue's plain geometry and unit-stride shortcut,
 // 31-bit byte offsets.  Returns 1 for the narrow maps: at most 16 x 16 with at least wino::MIN_TILES Winograd tiles (level 1
-// and up; launch_conv_wino runs them on conv_wino_kernel at level 1 and on conv_winow_kernel<32, 4> at level 2, the same
-// bits); 2 for the wide maps on conv_winow_kernel: up to 112 x 112 with the tiles of at least wino::WIDE_MIN_IMAGES images
-// (level 2); 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether
-// the net carries the transformed weights (Net option "wino") -- on nothing else.
+// and up; launch_conv_wino runs them in 64-tile blocks at level 1 and in 32-tile blocks at level 2, the same bits); 2 for
+// the wide maps (launch_conv_winow): up to 112 x 112 with the tiles of at least wino::WIDE_MIN_IMAGES images (level 2);
+// 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether the net carries the transformed
+// weights (Net option "wino") -- on nothing else.
 static int wino_applies(const ConvArgs& a) {
   if (!a.w_wino || a.wino_level < 1 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1) return 0;
   if (a.Ho != a.H || a.Wo != a.W || (a.H & 1) || (a.W & 1)) return 0;
@@ -517,13 +325,12 @@ static int wino_applies(const ConvArgs& a) {
   return a.N * tpi >= wino::MIN_TILES ? 1 : 0;
 }
 
-template <int TT, int CPW>
-static int launch_conv_winow(const ConvArgs& a, hipStream_t st, const char* name) {
-  using S = WinoW<TT, CPW>;
-  const auto kern = a.trace ? conv_winow_kernel<TT, CPW, true> : conv_winow_kernel<TT, CPW, false>;
+template <class S>
+static int launch_wino(const ConvArgs& a, hipStream_t st, const char* name) {
+  const auto kern = a.trace ? conv_wino_kernel<S, true> : conv_wino_kernel<S, false>;
   if (allow_dynamic_lds(reinterpret_cast<const void*>(kern), S::LDS_BYTES)) return -1;
   const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
-  const int blocks_m = (int)((ntiles + TT - 1) / TT), tiles_n = a.Cout / wino::BN;
+  const int blocks_m = (int)((ntiles + S::TT - 1) / S::TT), tiles_n = a.Cout / wino::BN;
   const int64_t nblocks = (int64_t)blocks_m * tiles_n;
   if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(S::NT), S::LDS_BYTES, st, a, blocks_m, (int)nblocks);
@@ -532,24 +339,14 @@ static int launch_conv_winow(const ConvArgs& a, hipStream_t st, const char* name
   return 0;
 }
 
-static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {
-  // Level 2 runs the narrow maps in conv_winow_kernel's half-block shape too (the same bits).  The launch is reported
-  // under conv_wino_kernel's name, although the template is conv_winow_kernel: op_table()'s readers tell the narrow-map
-  // layers (level 1's list) from the wide ones by the name's beginning.  [dbg bit 16777216: conv_wino_kernel at level 2, A/B]
-  if (a.wino_level >= 2 && !(a.dbg & 16777216)) return launch_conv_winow<32, 4>(a, st, "conv_wino_kernel<F(2x2,3x3),32 tiles x 64>");
-  const auto kern = a.trace ? conv_wino_kernel<true> : conv_wino_kernel<false>;
-  if (allow_dynamic_lds(reinterpret_cast<const void*>(kern), wino::LDS_BYTES)) return -1;
-  const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
-  const int blocks_m = (int)((ntiles + wino::TT - 1) / wino::TT), tiles_n = a.Cout / wino::BN;
-  const int64_t nblocks = (int64_t)blocks_m * tiles_n;
-  if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(wino::NT), wino::LDS_BYTES, st, a, blocks_m, (int)nblocks);
-  DIF_HIP(hipGetLastError());
-  g_last_kernel = "conv_wino_kernel<F(2x2,3x3),64 tiles x 64>";
-  return 0;
+// The reported names keep the map class in their beginning, whatever the shape: op_table()'s readers tell the narrow-map
+// layers (level 1's list, conv_wino_kernel) from the wide ones (conv_winow_kernel) by it.
+static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {             // narrow maps (wino_applies: 1)
+  if (a.wino_level >= 2 && !(a.dbg & 16777216)) return launch_wino<WinoW<32, 4, 2, true>>(a, st, "conv_wino_kernel<F(2x2,3x3),32 tiles x 64>");
+  return launch_wino<WinoW<64, 2, 1, false>>(a, st, "conv_wino_kernel<F(2x2,3x3),64 tiles x 64>");
 }
 
-static int launch_conv_winow(const ConvArgs& a, hipStream_t st) {
-  if (a.dbg & 65536) return launch_conv_winow<64, 2>(a, st, "conv_winow_kernel<F(2x2,3x3),64 tiles x 64>");
-  return launch_conv_winow<32, 4>(a, st, "conv_winow_kernel<F(2x2,3x3),32 tiles x 64>");
+static int launch_conv_winow(const ConvArgs& a, hipStream_t st) {            // wide maps (wino_applies: 2)
+  if (a.dbg & 65536) return launch_wino<WinoW<64, 2, 2, true>>(a, st, "conv_winow_kernel<F(2x2,3x3),64 tiles x 64>");
+  return launch_wino<WinoW<32, 4, 2, true>>(a, st, "conv_winow_kernel<F(2x2,3x3),32 tiles x 64>");
 }

@@ -1112,7 +1112,7 @@ int Net::finalize(int mb) {
       // Winograd F(2x2,3x3) weights for conv_wino_kernel (conv_winograd.hpp): U_c[ci][co] = (G g G^T)[i][j], c = 4 i + j,
       // formed in double and rounded once, in the kernel's fragment order (1 KB per wave instruction).  Only for the layers
       // its shape rule can admit (wino_applies; the batch threshold is decided per launch) and only with option "wino" on:
-      // maps of at most 16 x 16 at level 1, the wide maps up to 112 x 112 (conv_winow_kernel, same U layout) at level 2.
+      // maps of at most 16 x 16 at level 1, the wide maps up to 112 x 112 (same kernel, same U layout) at level 2.
       op.d_w_wino = nullptr;
       op.w_wino_bytes = 0;
       {
@@ -1719,7 +1719,7 @@ int Net::embed_clock(const void* xin, int n, int layout, int dtype, float* out, 
           steps += (double)t[3];
           tiles += (double)t[4];
         }
-        if ((t[7] & 0xff) == 3) {                          // conv_wino_kernel / conv_winow_kernel: K loop, set-up, the two epilogue halves
+        if ((t[7] & 0xff) == 3) {                          // conv_wino_kernel (every shape): K loop, set-up, the two epilogue halves
           m += (double)t[0];
           f += (double)t[1];
           e += (double)(t[2] + t[3]);

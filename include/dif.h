@@ -363,8 +363,8 @@ int dif_net_finalize(dif_net* net, int max_batch);
  *                Winograd F(2x2,3x3) from 64 images per launch up (conv_wino_kernel): 2.25x fewer MFMA multiply-adds, f32
  *                operands, transforms and accumulation, different products -- about twice the direct path's rounding
  *                error per layer; 2 (default): level 1 plus the same layers on the wider even maps up to 112 x 112
- *                (IResNet's 28 x 28, 56 x 56 and 112 x 112 stages) from 128 images per launch up (conv_winow_kernel, the
- *                same arithmetic in half-size blocks, two per CU); 0: the direct f32 fma chain everywhere.  Any time;
+ *                (IResNet's 28 x 28, 56 x 56 and 112 x 112 stages) from 128 images per launch up, all of them by the same
+ *                kernel in half-size blocks, two per CU (the same bits); 0: the direct f32 fma chain everywhere.  Any time;
  *                raised after a dif_net_finalize that ran below it, the new level takes effect at the next
  *                dif_net_finalize, which builds the transformed weights; lowered and raised back, at the next forward
  *   "bf16x3"     0 (default): float32 MFMA -- with "wino" = 0 a bit-exact f32 fma chain, the reference's arithmetic;

@@ -80,6 +80,26 @@ def test_iresnet100_levels(r100, batch):
     assert cosine_gap(out[2][rows], want).max() < 1e-5
 
 
+def test_wide_maps_in_64_tile_blocks_equal_32_tile_blocks(r100):
+    """`dbg` bit 65536 runs the wide maps in the 64-tile block shape: the same layers, the same bits."""
+    model, _ = r100
+    dev = torch.from_numpy(crops_u8(256, seed=77)).cuda()
+    try:
+        model.set_option('wino', 2)
+        half = model.embed(dev)
+        tab_half = [(name, kern) for name, kern, _ in model.op_table() if kern.startswith(WIDE)]
+        model.set_option('dbg', 65536)
+        full = model.embed(dev)
+        tab_full = [(name, kern) for name, kern, _ in model.op_table() if kern.startswith(WIDE)]
+    finally:
+        model.set_option('dbg', 0)
+        model.set_option('wino', 2)
+    assert [name for name, _ in tab_half] == R100_WIDE and [name for name, _ in tab_full] == R100_WIDE
+    assert all(kern == WIDE + '<F(2x2,3x3),32 tiles x 64>' for _, kern in tab_half), tab_half
+    assert all(kern == WIDE + '<F(2x2,3x3),64 tiles x 64>' for _, kern in tab_full), tab_full
+    assert torch.equal(half, full)
+
+
 @pytest.mark.parametrize('arch,batch,wide', [
     ('iresnet50', 258, True),     # lanes of 129: just above the threshold; 129 x 196 tiles, blocks span images, last one partial
     ('iresnet50', 254, False),    # lanes of 127: just below it, the wide layers stay direct
