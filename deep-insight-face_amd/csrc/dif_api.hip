@@ -99,7 +99,7 @@ int dif_gallery_destroy(dif_gallery* h) {
   for (void* p : {(void*)g.part_key, (void*)g.part_cnt, (void*)g.part_idx, (void*)g.eps, (void*)g.eps32, (void*)g.best,
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
-                  (void*)g.within_thr})
+                  (void*)g.within_thr, (void*)g.rank_mate})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -321,6 +321,16 @@ int dif_match_within(dif_gallery* h, const float* probes_dev, int n, int metric,
   if (max_hits > 0 && (!idx_out_dev || !dist_out_dev)) return set_error("dif_match_within: null list pointer with max_hits > 0");
   return within_run(&h->g, probes_dev, n, metric, tolerance, max_hits, count_out_dev, idx_out_dev, dist_out_dev,
                     (hipStream_t)stream);
+}
+
+int dif_match_rank(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev,
+                   int64_t* rank_out_dev, float* mate_dist_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_rank: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_rank: negative probe count");
+  if (n == 0) return 0;
+  if (!probes_dev || !mate_idx_dev || !rank_out_dev) return set_error("dif_match_rank: null pointer");
+  return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, rank_out_dev, mate_dist_out_dev, (hipStream_t)stream);
 }
 
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,

@@ -64,6 +64,9 @@ struct Gallery {
   size_t within_census_cap = 0;              // ... in 16-bit words
   float* within_thr = nullptr;               // per probe: {key <= [0]: sure, key > [1]: out, |key| >= [2]: borderline, [3] != 0: resolve all}
   size_t within_thr_cap = 0;                 // ... in probes
+  // dif_match_rank shares the two above (stream-ordered calls) and adds, per probe, the mate's distance and local row
+  struct RankMate* rank_mate = nullptr;
+  size_t rank_mate_cap = 0;                  // ... in probes
 };
 
 int gallery_norms(Gallery* g, const float* src, hipStream_t st);   // src: the caller's rows (copied into g->rows in the same pass), or null
@@ -73,6 +76,8 @@ int match_run(Gallery* g, const float* probes, int B, int metric, int64_t* idx_o
               float* key_out, hipStream_t st);
 int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
                int64_t* idx_out, float* dist_out, hipStream_t st);
+int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
+             float* mate_dist_out, hipStream_t st);
 int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D, int metric, float* out,
                  hipStream_t st);
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,

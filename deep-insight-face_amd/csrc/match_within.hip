@@ -1,4 +1,5 @@
-// Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within).
+// Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), and the rank of
+// one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel).
 // hipcc-flags: -ffp-contract=off
 // (the resolve stage restates the reference's float32 operations one by one, as match.hip's re-rank does)
 //
@@ -54,37 +55,107 @@ constexpr int WITHIN_BM = 128;          // gallery rows per census word: every f
 constexpr int WITHIN_NW = 8;            // waves of a resolve block
 constexpr size_t WITHIN_CENSUS_MAX = (size_t)128 << 20;   // census words per launch (256 MB); more probes go in several rounds
 
+// The band of one probe at tolerance t (the formulas of the header comment); s = |q|^2 summed as an fma chain over 64 lanes.
+struct Band {
+  float T, E, H;
+  bool odd;                                                   // outside the bound's validity: every tile is resolved
+};
+__device__ __forceinline__ Band within_band(int metric, float t, float s, int D, float cdot,
+                                            const unsigned* __restrict__ sqmax_bits) {
+  const float u = U24, qn = sqrtf(s) * 1.0001f, inf = __builtin_inff();
+  Band b;
+  if (metric == 1) {
+    b.odd = !(s >= NORM_LO && s <= NORM_HI);
+    b.E = key_err1_rel(cdot) * qn + (96.f + (float)(D / 64)) * u * qn;
+    b.T = t >= 1.f ? inf : (t < 0.f ? -inf : (float)(-sqrt((double)s) * cos(3.14159265358979323846 * (double)t)));
+    b.H = sqrtf(s) * (1.f - (2e-4f + 1.01f * (cdot + 136.f * u)));
+  } else {
+    b.odd = !(s <= NORM_HI);
+    const float gmax = sqrtf(__builtin_bit_cast(float, *sqmax_bits)) * 1.0001f;
+    b.E = key_err0(cdot, qn, gmax) + 32.f * u * (qn + gmax) * (qn + gmax) +
+          ((float)(D / 64) + 8.f) * u * (qn * qn + gmax * gmax) + u * (fabsf(t) + qn * qn);
+    b.T = t - s;
+    b.H = inf;
+  }
+  return b;
+}
+
+// |q|^2 of one probe row by one wave: an fma chain per lane, then the butterfly (every lane returns the sum)
+__device__ __forceinline__ float probe_sq(const float* __restrict__ q, int D, int lane) {
+  float s = 0.f;
+  for (int k = lane; k < D; k += 64) {
+    const float x = q[k];
+    s = fmaf(x, x, s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  return s;
+}
+
 __global__ __launch_bounds__(256) void within_prep_kernel(const float* __restrict__ probes, int B, int D, int metric, float t,
                                                           float cdot, const unsigned* __restrict__ sqmax_bits,
                                                           f32x4* __restrict__ thr) {
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (p >= B) return;
-  float s = 0.f;
-  for (int k = lane; k < D; k += 64) {
-    const float x = probes[(int64_t)p * D + k];
-    s = fmaf(x, x, s);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const float s = probe_sq(probes + (int64_t)p * D, D, lane);
   if (lane != 0) return;
-  const float u = U24, qn = sqrtf(s) * 1.0001f, inf = __builtin_inff();
-  float T, E, H;
-  bool odd;
-  if (metric == 1) {
-    odd = !(s >= NORM_LO && s <= NORM_HI);
-    E = key_err1_rel(cdot) * qn + (96.f + (float)(D / 64)) * u * qn;
-    T = t >= 1.f ? inf : (t < 0.f ? -inf : (float)(-sqrt((double)s) * cos(3.14159265358979323846 * (double)t)));
-    H = sqrtf(s) * (1.f - (2e-4f + 1.01f * (cdot + 136.f * u)));
-  } else {
-    odd = !(s <= NORM_HI);
-    const float gmax = sqrtf(__builtin_bit_cast(float, *sqmax_bits)) * 1.0001f;
-    E = key_err0(cdot, qn, gmax) + 32.f * u * (qn + gmax) * (qn + gmax) +
-        ((float)(D / 64) + 8.f) * u * (qn * qn + gmax * gmax) + u * (fabsf(t) + qn * qn);
-    T = t - s;
-    H = inf;
-  }
+  const float inf = __builtin_inff();
+  const Band b = within_band(metric, t, s, D, cdot, sqmax_bits);
   // (an infinite tolerance under metric 0 makes T - E a NaN: no key is SURE, none is OUT, every tile is resolved)
-  thr[p] = odd ? f32x4{-inf, inf, H, 1.f} : f32x4{T - E, T + E, H, 0.f};
+  thr[p] = b.odd ? f32x4{-inf, inf, b.H, 1.f} : f32x4{b.T - b.E, b.T + b.E, b.H, 0.f};
+}
+
+// ---------------------------------------------------------------------------------------------
+// Rank of the mate (dif_match_rank): where does row m rank among all rows by distance to the probe?
+//   dm = d[m];  rank = count(d < dm) + count(d[:m] == dm)            (NaN compares False: a NaN distance is never closer)
+// Once dm is known this is the range search with the tolerance taken per probe and nothing listed:
+//   rank_prep_kernel     dm on the reference arithmetic, and the census thresholds from it
+//   within_census_kernel unchanged
+//   rank_resolve_kernel  SURE counts of the tiles without a borderline row + the rows of the other tiles one by one
+// SURE has to mean STRICTLY closer.  The bound of the header comment is not re-derived; it is used twice:
+//   thr[0] = T(t') - E(t'),  t' = nextafterf(dm, -inf):  key <= thr[0] (and |key| < H)  =>  d <= t' < dm
+//   thr[1] = T(dm) + E(dm):                              key >  thr[1]  =>  d > dm or NaN: neither closer nor tied
+// thr[0] <= thr[1], which the census needs for bord = not out - sure: T is the rounding of a non-decreasing function of t
+// (metric 1: -|q| cos(pi t) on [0, 1], -inf below 0, +inf from 1; cos in double is monotone up to 1e-16, far inside 2 E >=
+// 192 u |q|; metric 0: the float subtraction t - |q|^2), E >= 0, and t' < dm.  Where E is not finite thr[0] is NaN or -inf
+// and nothing is SURE.  dm = 0 gives t' < 0: T = -inf under metric 1, below every possible key minus E under metric 0 --
+// nothing is closer than 0 and nothing is SURE.
+struct RankMate {
+  float dm;                                                   // the mate's distance (NaN: a miss at every rank)
+  int row;                                                    // its local row, or -1: unmated
+};
+
+__global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict__ probes, int B, int D, int metric, float cdot,
+                                                        const unsigned* __restrict__ sqmax_bits,
+                                                        const float* __restrict__ gallery, int64_t G, int64_t index_base,
+                                                        const int64_t* __restrict__ mates, int clamp, const SumPlan plan,
+                                                        f32x4* __restrict__ thr, RankMate* __restrict__ mate,
+                                                        float* __restrict__ mate_dist_out) {
+  __shared__ float scratch[4][NP_SCRATCH];
+  const int wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
+  if (p >= B) return;                                         // (wave-uniform, like everything below)
+  const float* q = probes + (int64_t)p * D;
+  const int64_t m = mates[p];
+  // (unsigned: one comparison covers both sides and cannot overflow, whatever the sign of index_base; a shard holds fewer
+  // than 2^31 rows -- dif_gallery_set -- so the local row fits an int)
+  const uint64_t ml = (uint64_t)m - (uint64_t)index_base;
+  const bool mated = ml < (uint64_t)G;
+  const float inf = __builtin_inff();
+  float dm = __builtin_nanf("");
+  if (mated) (void)ref_distance(plan, scratch[wave], q, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
+  const float s = probe_sq(q, D, lane);
+  if (lane != 0) return;
+  mate[p] = RankMate{dm, mated ? (int)ml : -1};
+  if (mate_dist_out) mate_dist_out[p] = dm;
+  // unmated, or a NaN distance: every row OUT, nothing to resolve (the third word, H, only ever vetoes SURE, and with
+  // thr[0] = -inf nothing is: its value does not matter here)
+  if (!(dm == dm)) {
+    thr[p] = f32x4{-inf, -inf, inf, 0.f};
+    return;
+  }
+  const Band lo = within_band(metric, nextafterf(dm, -inf), s, D, cdot, sqmax_bits);
+  const Band hi = within_band(metric, dm, s, D, cdot, sqmax_bits);
+  thr[p] = hi.odd ? f32x4{-inf, inf, hi.H, 1.f} : f32x4{lo.T - lo.E, hi.T + hi.E, hi.H, 0.f};
 }
 
 template <class T>
@@ -243,6 +314,64 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const un
   }
 }
 
+// One block per probe, as within_resolve_kernel without the lists: a tile without a borderline row adds its SURE count (no
+// memory touched), any other tile -- every tile under the "resolve everything" flag -- is evaluated row by row, a wave per
+// row, and a row counts when it is closer than the mate or ties with it from a lower index.  Every wave keeps the count of
+// its own rows; they meet once, in LDS, at the end.  Which tiles are evaluated is block-uniform (the same LDS words).
+__global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsigned short* __restrict__ census, int64_t G,
+                                                                    int B, const f32x4* __restrict__ thr,
+                                                                    const RankMate* __restrict__ mate,
+                                                                    const float* __restrict__ probes,
+                                                                    const float* __restrict__ gallery, int D, int metric,
+                                                                    int clamp, const SumPlan plan,
+                                                                    int64_t* __restrict__ rank_out) {
+  constexpr int NT = 64 * WITHIN_NW;
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned short s_word[NT];
+  __shared__ int s_part[WITHIN_NW];
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const RankMate mt = mate[p];
+  if (mt.row < 0 || !(mt.dm == mt.dm)) {                      // unmated: -1; the mate's distance is NaN: behind every row
+    if (tid == 0) rank_out[p] = mt.row < 0 ? -1 : G;
+    return;
+  }
+  const float dm = mt.dm;
+  const float* q = probes + (int64_t)p * D;
+  const int64_t gtiles = (G + WITHIN_BM - 1) / WITHIN_BM;
+  const bool all = thr[p][3] != 0.f;
+  int64_t sure_rows = 0;                                      // the same in every thread
+  int mine = 0;                                               // rows this wave evaluated and counted (G < 2^31)
+  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
+    s_word[tid] = w;
+    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
+    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
+    for (int j = 0; j < nw; ++j) {
+      const int sure = s_word[j] & 0xff, bord = s_word[j] >> 8;
+      if (!(all || bord > 0)) {
+        sure_rows += sure;
+        continue;
+      }
+      const int64_t g0 = (t0 + j) * WITHIN_BM;
+      const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
+      for (int r = wave; r < rows; r += WITHIN_NW) {
+        float d;
+        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+        mine += (d < dm || (d == dm && g0 + r < mt.row)) ? 1 : 0;   // NaN: neither
+      }
+    }
+    __syncthreads();                                          // s_word is rewritten by the next round
+  }
+  if (lane == 0) s_part[wave] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    int64_t rank = sure_rows;
+#pragma unroll
+    for (int w = 0; w < WITHIN_NW; ++w) rank += s_part[w];
+    rank_out[p] = rank;
+  }
+}
+
 template <class T>
 static int launch_census(const Gallery* g, const float* probes, int B, int metric, hipStream_t st) {
   auto kern = within_census_kernel<T>;
@@ -303,6 +432,48 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
                        reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
                        max_hits, g->index_base, count_out + b0, max_hits ? idx_out + b0 * max_hits : nullptr,
                        max_hits ? dist_out + b0 * max_hits : nullptr);
+    DIF_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
+             float* mate_dist_out, hipStream_t st) {
+  if (B <= 0) return 0;
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  const int clamp = g->clamp_nan ? 1 : 0;
+  const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
+  // probes per round as in within_run (an empty gallery has no census: one round, every probe unmated)
+  int64_t per = gtiles > 0 ? (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128 : B;
+  if (per < 128) per = 128;
+  if (per > B) per = B;
+  const size_t need_c = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
+  if (need_c > g->within_census_cap || need_t > g->within_thr_cap || need_t > g->rank_mate_cap) {
+    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
+    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
+    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
+    if (grow(&g->rank_mate, &g->rank_mate_cap, need_t, sizeof(RankMate))) return -1;
+  }
+  const float cdot = g->d * U24;
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int nb = (int)(B - b0 < per ? B - b0 : per);
+    const float* pr = probes + b0 * g->d;
+    hipLaunchKernelGGL(rank_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits,
+                       g->rows, g->n, g->index_base, mates + b0, clamp, plan, reinterpret_cast<f32x4*>(g->within_thr),
+                       g->rank_mate, mate_dist_out ? mate_dist_out + b0 : nullptr);
+    DIF_HIP(hipGetLastError());
+    if (gtiles > 0) {
+      const int kind = match_tile_kind(nb);
+      int rc;
+      if (kind == 4 && nb <= 32) rc = launch_census<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st);
+      else if (kind == 1 || nb <= 64) rc = launch_census<Tile<2, 1>>(g, pr, nb, metric, st);
+      else rc = launch_census<Tile<2, 2>>(g, pr, nb, metric, st);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(rank_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
+                       reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
+                       rank_out + b0);
     DIF_HIP(hipGetLastError());
   }
   return 0;

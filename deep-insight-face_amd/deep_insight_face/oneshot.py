@@ -9,6 +9,7 @@ probe row q, ``np.argmin(evaluation.utility.distance(q[None, :], gallery, metric
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -201,6 +202,66 @@ class Gallery:
             count, idx, dist = count.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
         return count, idx, dist
 
+    def rank_into(self, probes, mates, distance_metric, rank, mate_dist):
+        """Allocation-free form of `rank`: `probes` [B, d] float32 and `mates` [B] int64 CUDA, results written into the
+        caller's CUDA tensors rank [B] int64 and mate_dist [B] float32."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
+            raise ValueError('probes must be a [B, %d] tensor, got %s' % (
+                self.emd_size, tuple(probes.shape) if hasattr(probes, 'shape') else type(probes).__name__))
+        B = probes.shape[0]
+        for name, t, dt in (('probes', probes, torch.float32), ('mates', mates, torch.int64), ('rank', rank, torch.int64),
+                            ('mate_dist', mate_dist, torch.float32)):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('rank_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
+            if name != 'probes' and (t.dim() != 1 or t.shape[0] != B):
+                raise ValueError('rank_into: %s must have shape [%d], got %s' % (name, B, tuple(t.shape)))
+        if B:
+            N.check(N.lib.dif_match_rank(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(rank),
+                                         N.ptr(mate_dist), N.stream_ptr()))
+
+    def rank(self, probes, mates, distance_metric=1):
+        """Rank of the mate: where row `mates[b]` (global index, any integer dtype, shape [B]) ranks among ALL enrolled rows
+        by distance to probe b, exact.  -> (rank[B] int64, mate_dist[B] float32); NumPy in -> NumPy out.
+
+        Per probe q: ``d = evaluation.utility.distance(q[None, :], gallery, metric)``, ``dm = d[m - index_base]``,
+        ``rank = count(d < dm) + count(d[:m - index_base] == dm)`` -- 0-based, the mate's position in
+        ``np.argsort(d, kind='stable')`` when no distance is NaN; ``mate_dist = dm``.  A NaN distance is never closer.
+        A mate of -1 (or any index outside the gallery) marks an unmated probe: rank -1, mate_dist NaN.  A mate whose own
+        distance is NaN gets rank len(self), a miss at every k.  Without NaNs rank == 0 exactly when `match` returns the mate.
+        Rows of the mate's identity count like any other row."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        p, was_np = N.to_device_f32(probes, self._dev)
+        if p.dim() == 1:
+            p = p[None, :]
+        if p.dim() != 2 or p.shape[1] != self.emd_size:
+            raise ValueError('probes must be [B, %d], got %s' % (self.emd_size, tuple(p.shape)))
+        B = p.shape[0]
+        if torch.is_tensor(mates):
+            m = mates
+            if m.dtype.is_floating_point or m.dtype.is_complex or m.dtype == torch.bool:
+                raise ValueError('mates must be integers, got %s' % m.dtype)
+        else:
+            m = np.asarray(mates)
+            if m.size == 0 and m.dtype.kind == 'f':          # np.asarray([]) is float64: an empty list names no row
+                m = m.astype(np.int64)
+            if m.dtype.kind not in 'iu':
+                raise ValueError('mates must be integers, got %s' % m.dtype)
+            if m.dtype.kind == 'u' and m.size and int(m.max()) > np.iinfo(np.int64).max:
+                raise ValueError('mates must fit int64')
+            m = torch.from_numpy(np.ascontiguousarray(m.astype(np.int64)))
+        if tuple(m.shape) != (B,):
+            raise ValueError('mates must have shape [%d], got %s' % (B, tuple(m.shape)))
+        m = m.to(device=self._dev, dtype=torch.int64).contiguous()
+        rank = torch.empty((B,), dtype=torch.int64, device=self._dev)
+        mate_dist = torch.empty((B,), dtype=torch.float32, device=self._dev)
+        self.rank_into(p, m, distance_metric, rank, mate_dist)
+        if was_np:
+            rank, mate_dist = rank.cpu().numpy(), mate_dist.cpu().numpy()
+        return rank, mate_dist
+
     def close(self):
         if self._h:
             N.lib.dif_gallery_destroy(self._h)
@@ -229,6 +290,17 @@ def within(probes, gallery, tolerance, distance_metric=1, max_hits=64):
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
         return g.within(probes, tolerance, distance_metric, max_hits)
+    finally:
+        if g is not gallery:
+            g.close()
+
+
+def rank(probes, gallery, mates, distance_metric=1):
+    """One-call form of Gallery.rank: per probe, the rank of its mate row among all gallery rows and the mate's distance
+    -> (rank[B], mate_dist[B])."""
+    g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
+    try:
+        return g.rank(probes, mates, distance_metric)
     finally:
         if g is not gallery:
             g.close()

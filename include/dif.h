@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within (an addition: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -296,6 +296,33 @@ int dif_match(dif_gallery* g, const float* probes_dev, int n, int metric, int64_
 int dif_match_within(dif_gallery* g, const float* probes_dev, int n, int metric, float tolerance, int max_hits,
                      int64_t* count_out_dev /* [n] */, int64_t* idx_out_dev /* [n][max_hits], or NULL when max_hits == 0 */,
                      float* dist_out_dev /* same shape */, void* stream);
+/* rank of the mate: where does one given enrolled row rank among ALL enrolled rows by distance to the probe?  The quantity
+ * behind rank-k identification rates, the CMC curve and open-set DIR / FAR (deep_insight_face/evaluation/identification.py).
+ * Per probe q with mate row m = mate_idx_dev[p] (int64 GLOBAL index: dif_gallery_set's index_base is subtracted):
+ *     d  = utility.distance(q[None, :], gallery, metric)           the reference's float32 values
+ *     dm = d[m - index_base]
+ *     rank_out_dev[p]      = count(d < dm) + count(d[:m - index_base] == dm)     0-based; exact ties go to the lower index
+ *     mate_dist_out_dev[p] = dm                                    (optional, may be NULL)
+ *   For a row of distances without NaN this is the mate's position in np.argsort(d, kind='stable').  Rows of the mate's own
+ *   identity count like any other row: with several rows per identity the caller passes the row they mean.
+ *   Unmated probe -- m == -1 or anywhere outside [index_base, index_base + size): rank -1, mate_dist NaN, no gallery row is
+ *   read for it.  An empty gallery makes every probe unmated.  n = 0 is a no-op; a metric other than 0 / 1 or a NULL
+ *   handle, probes, mate_idx or rank_out fails.
+ * Units: mate_dist is in the units of utility.distance -- metric 0 the SQUARED L2 distance, metric 1 arccos(similarity) / pi.
+ * The distances compared are exactly the ones dif_match / dif_match_within / dif_pairwise report for the pair, under the
+ *   handle's "clamp_nan": metric 0 bit-identical to the reference; metric 1 up to the arccos (evaluated in double and rounded
+ *   once; NumPy's float32 arccos is within 2 ulp), so against NumPy a row whose distance lies within ~2e-6 of dm may fall on
+ *   the other side of it.  mate_dist is bit-identical to dif_pairwise's value for (q, gallery[m]).
+ * NaN rule: NaN compares False -- a row whose distance is NaN is never "closer" (dif_match_within's "NaN is never a hit").  A
+ *   mate whose own distance is NaN (a similarity rounded beyond +-1 with "clamp_nan" 0, a zero-norm or non-finite row or probe)
+ *   gives rank = dif_gallery_size ("behind every row": a miss at every k, distinct from unmated) and mate_dist NaN.
+ * Relation to dif_match: where no distance of the probe's row is NaN, rank == 0 exactly when dif_match returns m.  They differ
+ *   where there are NaNs: np.argmin ranks a NaN first, the rank never counts one.
+ * Costs one pass of the f32 MFMA over the gallery (dif_match_within's census) plus the reference arithmetic on the 128-row
+ *   tiles that hold a row too close to dm to call -- the mate's own tile is always one; no host synchronisation in steady state;
+ *   shares dif_match_within's workspace (calls on one stream are ordered) plus 8 bytes per probe. */
+int dif_match_rank(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
+                   int64_t* rank_out_dev /* [n] */, float* mate_dist_out_dev /* [n], may be NULL */, void* stream);
 /* merge R per-shard results laid out [R][n] (after an all-gather): lowest key, then
  * lowest global index -- equals np.argmin over the concatenated gallery */
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,
