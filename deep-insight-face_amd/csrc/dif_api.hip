@@ -99,7 +99,7 @@ int dif_gallery_destroy(dif_gallery* h) {
   for (void* p : {(void*)g.part_key, (void*)g.part_cnt, (void*)g.part_idx, (void*)g.eps, (void*)g.eps32, (void*)g.best,
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
-                  (void*)g.within_thr, (void*)g.rank_mate})
+                  (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -200,6 +200,20 @@ int dif_gallery_update(dif_gallery* h, const float* rows_dev, int64_t n, int64_t
   const int64_t old_n = g.n;
   if (first_row + n > g.n) g.n = first_row + n;
   return gallery_update_rows(&g, rows_dev, first_row, n, old_n, st);
+}
+
+int dif_gallery_remove(dif_gallery* h, const int64_t* rows_dev, int64_t k, int64_t* moved_from_dev, int64_t* moved_to_dev,
+                       int64_t* n_moved_out, void* stream) {
+  if (!h) return set_error("dif_gallery_remove: null handle");
+  if (k < 0) return set_error("dif_gallery_remove: negative row count");
+  if (n_moved_out) *n_moved_out = 0;
+  if (k == 0) return 0;
+  if (!rows_dev) return set_error("dif_gallery_remove: null rows");
+  Gallery& g = h->g;
+  if (k > g.n)
+    return set_error("dif_gallery_remove: %lld rows named, the gallery holds %lld (the list must be distinct)", (long long)k,
+                     (long long)g.n);
+  return gallery_remove_rows(&g, rows_dev, k, moved_from_dev, moved_to_dev, n_moved_out, (hipStream_t)stream);
 }
 
 int64_t dif_gallery_size(const dif_gallery* h) { return h ? h->g.n : 0; }

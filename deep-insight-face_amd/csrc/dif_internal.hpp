@@ -67,11 +67,16 @@ struct Gallery {
   // dif_match_rank shares the two above (stream-ordered calls) and adds, per probe, the mate's distance and local row
   struct RankMate* rank_mate = nullptr;
   size_t rank_mate_cap = 0;                  // ... in probes
+  // dif_gallery_remove's plan (csrc/match.hip): the record the host reads, then one destination per tail slot
+  int64_t* remove_ws = nullptr;
+  size_t remove_ws_cap = 0;                  // ... in 8-byte words
 };
 
 int gallery_norms(Gallery* g, const float* src, hipStream_t st);   // src: the caller's rows (copied into g->rows in the same pass), or null
 int gallery_split_copy(Gallery* g, hipStream_t st);   // (re)builds rows2 when the option asks for it; never fatal
 int gallery_update_rows(Gallery* g, const float* src, int64_t first, int64_t count, int64_t old_n, hipStream_t st);   // rows [first, first+count) <- src
+int gallery_remove_rows(Gallery* g, const int64_t* rows_dev, int64_t k, int64_t* moved_from, int64_t* moved_to, int64_t* n_moved,
+                        hipStream_t st);   // swap-remove of the k rows listed (global indices, strictly ascending; k <= g->n)
 int match_run(Gallery* g, const float* probes, int B, int metric, int64_t* idx_out, float* dist_out,
               float* key_out, hipStream_t st);
 int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,

@@ -67,6 +67,47 @@ class Gallery:
         N.check(N.lib.dif_gallery_update(self._h, N.ptr(g), g.shape[0], first_row, N.stream_ptr()), ValueError)
         torch.cuda.current_stream().synchronize()   # g may be a temporary: the copy must have landed
 
+    def remove(self, rows):
+        """Un-enrol: take the rows named in `rows` (global indices, any integer dtype, shape [k], any order; duplicates
+        collapse as in np.delete) out of the gallery -- O(k) on the device, the capacity stays.
+        -> (moved_from[m], moved_to[m]) int64, m <= k; NumPy in -> NumPy out, tensor in -> tensors on the device.
+
+        Swap-remove: with new_n = len(self) - k, rows below new_n that are not named keep their indices; the surviving rows of
+        the tail [new_n, len) fill the holes the named rows leave below new_n, the i-th survivor the i-th hole, both in
+        ascending order: row moved_from[i] is now row moved_to[i] (fix the name table with it).  Afterwards `match`, `within`
+        and `rank` answer exactly as a gallery `set` with the resulting rows; the removed rows' slots are zeroed on the device.
+        An index outside the gallery raises ValueError and leaves the gallery as it was."""
+        was_np = not torch.is_tensor(rows)
+        if was_np:
+            r = np.asarray(rows)
+            if r.size == 0 and r.dtype.kind == 'f':          # np.asarray([]) is float64: an empty list names no row
+                r = r.astype(np.int64)
+            if r.dtype.kind not in 'iu':
+                raise ValueError('rows must be integers, got %s' % r.dtype)
+            if r.dtype.kind == 'u' and r.size and int(r.max()) > np.iinfo(np.int64).max:
+                raise ValueError('rows must fit int64')
+            if r.ndim != 1:
+                raise ValueError('rows must have shape [k], got %s' % (r.shape,))
+            r = torch.from_numpy(np.ascontiguousarray(r.astype(np.int64)))
+        else:
+            r = rows
+            if r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool:
+                raise ValueError('rows must be integers, got %s' % r.dtype)
+            if r.dim() != 1:
+                raise ValueError('rows must have shape [k], got %s' % (tuple(r.shape),))
+        r = torch.unique(r.to(device=self._dev, dtype=torch.int64))   # sorted, distinct: what dif_gallery_remove takes
+        k = r.shape[0]
+        moved_from = torch.empty((k,), dtype=torch.int64, device=self._dev)
+        moved_to = torch.empty((k,), dtype=torch.int64, device=self._dev)
+        m = ctypes.c_int64(0)
+        if k:
+            N.check(N.lib.dif_gallery_remove(self._h, N.ptr(r), k, N.ptr(moved_from), N.ptr(moved_to), ctypes.byref(m),
+                                             N.stream_ptr()), ValueError)
+        moved_from, moved_to = moved_from[:m.value], moved_to[:m.value]
+        if was_np:
+            moved_from, moved_to = moved_from.cpu().numpy(), moved_to.cpu().numpy()
+        return moved_from, moved_to
+
     def reserve(self, capacity):
         N.check(N.lib.dif_gallery_reserve(self._h, int(capacity), N.stream_ptr()))
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -232,6 +232,20 @@ int64_t dif_gallery_size(const dif_gallery* g);
  * dif_gallery_reserve: grow the capacity (rows are kept; never shrinks); dif_gallery_set sizes it to its `n`.
  * dif_gallery_capacity: rows the handle can hold without reallocating. */
 int dif_gallery_update(dif_gallery* g, const float* rows_dev, int64_t n, int64_t first_row, void* stream);
+/* dif_gallery_remove: un-enrol the `k` rows listed in rows_dev (device memory: GLOBAL indices, index_base included, strictly
+ *   ascending, every one inside [index_base, index_base + dif_gallery_size)).  Swap-remove: the size drops to new_n = size - k;
+ *   rows below new_n that are not listed keep their indices, the listed ones below new_n are holes, and the i-th surviving row of
+ *   the tail [new_n, size) moves into the i-th hole (both ascending).  The moves are reported so the caller can fix its name
+ *   table: moved_from_dev[i] -> moved_to_dev[i] (global indices, device memory, `k` slots each or NULL), i < *n_moved_out <= k
+ *   (host; may be NULL); slots beyond hold -1, as dif_match_within's unused list slots do.  Afterwards every answer of dif_match /
+ *   dif_match_within / dif_match_rank is exactly that of a dif_gallery_set with the resulting rows; the capacity stays.
+ *   Costs O(k), no pass over the gallery (unless a listed or moved row was one the filter cannot rank: then the special-row lists
+ *   are rebuilt as after dif_gallery_update, 8 bytes per row read).  The filter's copy is moved with the rows, not recomputed.
+ *   The vacated slots [new_n, size) are overwritten with zeros in every device form of the rows: a removed template does not stay in
+ *   device memory.  The call SYNCHRONISES the stream (it reads the number of moves, and the input's validity, before it touches
+ *   the gallery): an unsorted, duplicated or out-of-range list fails and leaves the gallery as it was. */
+int dif_gallery_remove(dif_gallery* g, const int64_t* rows_dev, int64_t k, int64_t* moved_from_dev, int64_t* moved_to_dev,
+                       int64_t* n_moved_out, void* stream);
 int dif_gallery_reserve(dif_gallery* g, int64_t capacity, void* stream);
 int64_t dif_gallery_capacity(const dif_gallery* g);
 /* options.  "filter": what the MFMA stage of dif_match -- a candidate filter with a proven error bound; the winner
