@@ -99,7 +99,7 @@ int dif_gallery_destroy(dif_gallery* h) {
   for (void* p : {(void*)g.part_key, (void*)g.part_cnt, (void*)g.part_idx, (void*)g.eps, (void*)g.eps32, (void*)g.best,
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
-                  (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws})
+                  (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -219,7 +219,7 @@ int dif_gallery_remove(dif_gallery* h, const int64_t* rows_dev, int64_t k, int64
 int64_t dif_gallery_size(const dif_gallery* h) { return h ? h->g.n : 0; }
 int64_t dif_gallery_capacity(const dif_gallery* h) { return h ? h->g.cap : 0; }
 
-static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", nullptr};
+static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", nullptr};
 
 const char* dif_gallery_option_name(int i) {
   int n = 0;
@@ -236,6 +236,12 @@ int dif_gallery_set_option(dif_gallery* h, const char* key, int value) {
   }
   if (std::string(key) == "clamp_nan") {
     h->g.clamp_nan = value != 0;
+    return 0;
+  }
+  if (std::string(key) == "topk_seed") {
+    // tiles the seed stage of dif_match_topk evaluates per probe (0: k of them).  Same answers: the sweep completes the list
+    if (value < 0) return set_error("dif_gallery_set_option: 'topk_seed' takes 0 or a positive tile count");
+    h->g.topk_seed = value;
     return 0;
   }
   if (std::string(key) == "bd_fill") {
@@ -345,6 +351,17 @@ int dif_match_rank(dif_gallery* h, const float* probes_dev, int n, int metric, c
   if (n == 0) return 0;
   if (!probes_dev || !mate_idx_dev || !rank_out_dev) return set_error("dif_match_rank: null pointer");
   return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, rank_out_dev, mate_dist_out_dev, (hipStream_t)stream);
+}
+
+int dif_match_topk(dif_gallery* h, const float* probes_dev, int n, int metric, int k, int64_t* idx_out_dev,
+                   float* dist_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_topk: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_topk: negative probe count");
+  if (k < 1 || k > DIF_TOPK_MAX) return set_error("dif_match_topk: k %d outside [1, %d]", k, DIF_TOPK_MAX);
+  if (n == 0) return 0;
+  if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match_topk: null pointer");
+  return topk_run(&h->g, probes_dev, n, metric, k, idx_out_dev, dist_out_dev, (hipStream_t)stream);
 }
 
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,

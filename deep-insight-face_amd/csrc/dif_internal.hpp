@@ -67,6 +67,10 @@ struct Gallery {
   // dif_match_rank shares the two above (stream-ordered calls) and adds, per probe, the mate's distance and local row
   struct RankMate* rank_mate = nullptr;
   size_t rank_mate_cap = 0;                  // ... in probes
+  // dif_match_topk's workspace, its own: per (gallery tile of 128 rows, probe) the minimum search key of the tile
+  float* topk_min = nullptr;
+  size_t topk_min_cap = 0;                   // ... in floats
+  int topk_seed = 0;                         // "topk_seed": tiles the seed of dif_match_topk evaluates per probe (0: k of them)
   // dif_gallery_remove's plan (csrc/match.hip): the record the host reads, then one destination per tail slot
   int64_t* remove_ws = nullptr;
   size_t remove_ws_cap = 0;                  // ... in 8-byte words
@@ -83,6 +87,7 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
                int64_t* idx_out, float* dist_out, hipStream_t st);
 int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
              float* mate_dist_out, hipStream_t st);
+int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
 int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D, int metric, float* out,
                  hipStream_t st);
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,

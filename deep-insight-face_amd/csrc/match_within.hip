@@ -1,5 +1,6 @@
-// Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), and the rank of
-// one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel).
+// Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), the rank of
+// one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel), and the k nearest rows in order
+// (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel).
 // hipcc-flags: -ffp-contract=off
 // (the resolve stage restates the reference's float32 operations one by one, as match.hip's re-rank does)
 //
@@ -474,6 +475,320 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
     hipLaunchKernelGGL(rank_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
                        reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
                        rank_out + b0);
+    DIF_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The k nearest rows, in order (dif_match_topk).  Per probe q:
+//   d = distance(q[None, :], gallery, metric);  order = np.argsort(d, kind='stable');  keep = order[~isnan(d[order])][:k]
+//   idx = keep + index_base;  dist = d[keep];  unused slots: idx -1, dist NaN
+// Built on ONE fact, the OUT bound of the header comment: for a tolerance t, a row whose search key is > T(t) + E(t) has a
+// reference distance > t, or NaN.  No inverse of T, no SURE bound, no lists in the MFMA stage, no atomics on global memory.
+//   topk_tilemin_kernel  a sibling of within_census_kernel: the same tiles, main loop, block order and keys; per (gallery tile
+//                        of 128 rows, probe) it stores ONE float, the minimum key of the tile ("word"): -inf when a key of
+//                        the tile is NaN (a row kept out of the filter), rows past G count as +inf.  It takes no thresholds.
+//   topk_select_kernel   one block per probe (|q|^2 and the band are formed here: there is no prep kernel).
+//     seed    kappa = the s-th smallest word of the probe (s = k, or "topk_seed"; every tile when there are no more than s),
+//             by a radix select on the order-preserving integer image of the float.  Every tile with word <= kappa is
+//             evaluated row by row with ref_distance, a wave per row; a NaN distance is dropped.
+//     list    candidates are 64-bit words  ordered(dist) << 32 | local row: unique, so their order is total, and it is the
+//             stable argsort's (distances are >= +0).  After each evaluated tile its at most 128 words are merged with the
+//             at most k kept ones by a bitonic sort in LDS and the smallest k are kept.  No overflow path: the kept set is
+//             the k smallest seen, whatever the tile order.
+//     t       the k-th smallest kept distance -- an actual reference distance -- or +inf when fewer than k were found;
+//             thr_out = T(t) + E(t) from within_band, unchanged.
+//     sweep   every tile not yet evaluated (word > kappa) whose word is not > thr_out is evaluated and merged the same way:
+//             a -inf word, and every tile when the probe is outside the bound's validity or thr_out is +inf or NaN.
+//     output  the kept words in ascending order, then the padding.
+// Why it is exact.  Let d_k be the k-th smallest distance that is not NaN (the list is short otherwise and t = +inf: every
+// tile is evaluated).  After the seed the list holds k actual distances, so t >= d_k.  Every true top-k row has d <= d_k <= t,
+// so its key is not OUT at t, so the word of its tile -- the minimum of the tile's keys, or -inf -- is <= thr_out or -inf, so
+// its tile is evaluated, in the seed or in the sweep.  A tile with word > thr_out holds only rows with d > t >= d_k or NaN.
+// Correctness never depends on kappa: kappa only decides how tight t is.  (Under "clamp_nan" a similarity rounded above 1 is
+// reported as 0: its key lies within E of -|q| <= T(t) for every t >= 0, so it is not OUT; one rounded below -1 is reported
+// as 1 and can be listed only when t >= 1, where T = +inf and nothing is OUT.)
+constexpr int TOPK_MAX = 128;                                 // DIF_TOPK_MAX
+constexpr size_t TOPK_MIN_MAX = WITHIN_CENSUS_MAX / 2;        // tile words (floats) per launch: the census' cap in bytes
+constexpr unsigned long long TOPK_NONE = ~0ull;               // an empty slot of the list: above every candidate
+
+// order-preserving integer image of a float that is not NaN (-inf lowest), and back
+__device__ __forceinline__ unsigned ord_f32(float x) {
+  const unsigned u = __builtin_bit_cast(unsigned, x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float unord_f32(unsigned o) {
+  return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+template <class T>
+__global__ __launch_bounds__(T::NT, 2) void topk_tilemin_kernel(const float* __restrict__ gallery, int64_t G,
+                                                              const float* __restrict__ probes, int B, int D,
+                                                              const float* __restrict__ aux, int metric,
+                                                              float* __restrict__ words, int nparts) {
+  constexpr int WM = T::WM, WN = T::WN;
+  static_assert(T::BM == WITHIN_BM, "one word per 128 gallery rows");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  // block -> (gallery part, probe block) as within_census_kernel
+  const int cblocks = (B + T::BN - 1) / T::BN;
+  const int grp = (int)blockIdx.x / (8 * cblocks), rem = (int)blockIdx.x % (8 * cblocks);
+  const int part = grp * 8 + (rem & 7), cblk = rem >> 3;
+  if (part >= nparts) return;
+  float* s_min = smem + T::LDS_FLOATS;                         // [WGM][BN]: the minimum per wave row
+  const int tid = threadIdx.x;
+  const int wc = T::wave_col();
+  const int p0 = cblk * T::BN;
+  const int ksteps = D / BK;
+  const int64_t gtiles = (G + T::BM - 1) / T::BM;
+  const float inf = __builtin_inff();
+
+  int col[WN];
+#pragma unroll
+  for (int n = 0; n < WN; ++n) col[n] = (wc * WN + n) * 32 + (tid & 31);
+
+  for (int64_t gt = part; gt < gtiles; gt += nparts) {
+    const int64_t g0 = gt * T::BM;
+    f32x16 acc[WM][WN];
+    zero_acc<T>(acc);
+    RowLoader<T::NA, T::RP> al(gallery + g0 * D, G - g0, D);
+    RowLoader<T::NB, T::RP> bl(probes + (int64_t)p0 * D, (int64_t)B - p0, D);
+    gemm_mainloop<T>(al, bl, 0, ksteps, smem, acc);
+
+    // dots -> keys -> one minimum per probe column.  aux[g] = -1/|g| (metric 1) or |g|^2 (metric 0), NaN for the rows kept
+    // out of the filter: fminf drops a NaN, so a NaN key is tested for and makes the minimum -inf.
+    int lane = tid & 63;
+    asm volatile("" : "+v"(lane));                           // opaque per tile, as in within_census_kernel
+    const int wr = T::wave_row();
+    const int64_t rows_left = G - g0;
+    const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(aux + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 4));
+    float mn[WN];
+#pragma unroll
+    for (int n = 0; n < WN; ++n) mn[n] = inf;
+#pragma unroll
+    for (int m = 0; m < WM; ++m) {
+      const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {                          // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
+        const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool ok = rbase + 8 * q + j < rows_left;
+#pragma unroll
+          for (int n = 0; n < WN; ++n) {
+            const float dot = acc[m][n][4 * q + j];
+            float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
+            key = ok ? key : inf;                             // a row past G
+            mn[n] = (key != key) ? -inf : fminf(mn[n], key);  // (once -inf it stays -inf)
+          }
+        }
+      }
+    }
+    // lanes l and l + 32 hold different rows of the same probe column; the WGM waves stacked on M meet in LDS
+#pragma unroll
+    for (int n = 0; n < WN; ++n) {
+      const float v = fminf(mn[n], __shfl_xor(mn[n], 32));
+      if (lane < 32) s_min[wr * T::BN + col[n]] = v;
+    }
+    lds_barrier();
+    for (int c = tid; c < T::BN; c += T::NT) {
+      float v = s_min[c];
+#pragma unroll
+      for (int w = 1; w < T::WGM; ++w) v = fminf(v, s_min[w * T::BN + c]);
+      if (p0 + c < B) words[gt * B + p0 + c] = v;
+    }
+    // (s_min is written again only after the next tile's main loop, i.e. behind several barriers)
+  }
+}
+
+// One block per probe; `words` rows are B floats apart.  All control flow is block-uniform: every thread derives kappa, t and
+// thr_out from the same LDS words, and which tiles are evaluated follows from those alone.
+// (four waves per SIMD asked for: two blocks per CU overlap the latency of the row-by-row stage -- DESIGN 4i has the A/B)
+__global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const float* __restrict__ words, int64_t G, int B,
+                                                                   const float* __restrict__ probes,
+                                                                   const float* __restrict__ gallery, int D, int metric,
+                                                                   float cdot, const unsigned* __restrict__ sqmax_bits,
+                                                                   int clamp, const SumPlan plan, int k, int seed,
+                                                                   int64_t index_base, int64_t* __restrict__ idx_out,
+                                                                   float* __restrict__ dist_out) {
+  constexpr int NT = 64 * WITHIN_NW;
+  static_assert(2 * TOPK_MAX <= NT && TOPK_MAX == WITHIN_BM, "the list holds k kept words and one tile's");
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned long long s_list[2 * TOPK_MAX];         // [0, k): kept, ascending; [TOPK_MAX, ..): the tile being merged
+  __shared__ float s_word[NT];
+  __shared__ unsigned s_hist[256];
+  __shared__ unsigned s_sel[2];
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* q = probes + (int64_t)p * D;
+  const int64_t gtiles = (G + WITHIN_BM - 1) / WITHIN_BM;
+  const float inf = __builtin_inff();
+  if (tid < 2 * TOPK_MAX) s_list[tid] = TOPK_NONE;
+  __syncthreads();
+
+  // ---- seed: kappa = the seed-th smallest word, one byte of its integer image per pass (exact counts: deterministic)
+  unsigned kappa = ~0u;                                       // no more than `seed` tiles: all of them
+  if ((int64_t)seed < gtiles) {
+    unsigned prefix = 0, need = (unsigned)seed;               // the need-th smallest among the words that start with prefix
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      if (tid < 256) s_hist[tid] = 0;
+      __syncthreads();
+      for (int64_t t = tid; t < gtiles; t += NT) {
+        const unsigned o = ord_f32(words[t * B + p]);
+        if ((unsigned)((unsigned long long)o >> (shift + 8)) == prefix) atomicAdd(&s_hist[(o >> shift) & 255u], 1u);
+      }
+      __syncthreads();
+      if (wave == 0) {                                        // four bins per lane, a scan over the lanes
+        unsigned c[4], sum = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          c[i] = s_hist[4 * lane + i];
+          sum += c[i];
+        }
+        unsigned incl = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned v = __shfl_up(incl, o);
+          if (lane >= o) incl += v;
+        }
+        const unsigned excl = incl - sum;
+        if (excl < need && need <= incl) {                    // exactly one lane: 1 <= need <= the total
+          unsigned r = need - excl;
+          int d = 0;
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+            if (d == i && r > c[i]) {
+              r -= c[i];
+              d = i + 1;
+            }
+          s_sel[0] = (unsigned)(4 * lane + d);
+          s_sel[1] = r;
+        }
+      }
+      __syncthreads();
+      prefix = (prefix << 8) | s_sel[0];
+      need = s_sel[1];
+      // (s_sel is written again only behind the two barriers of the next pass)
+    }
+    kappa = prefix;
+  }
+
+  if (gtiles > 0) {
+    const float s = probe_sq(q, D, lane);                     // the same in every thread
+    bool all = false;
+    float thr_out = 0.f;
+#pragma unroll 1
+    for (int phase = 0; phase < 2; ++phase) {                 // 0: the seed's tiles; 1: the sweep
+      if (phase == 1) {
+        const unsigned long long kth = s_list[k - 1];
+        const float t = kth == TOPK_NONE ? inf : unord_f32((unsigned)(kth >> 32));
+        const Band b = within_band(metric, t, s, D, cdot, sqmax_bits);
+        all = b.odd;
+        thr_out = b.T + b.E;
+      }
+      for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+        const float w = t0 + tid < gtiles ? words[(t0 + tid) * B + p] : inf;
+        s_word[tid] = w;
+        const bool mine = phase == 0 ? ord_f32(w) <= kappa : (ord_f32(w) > kappa && (all || !(w > thr_out)));
+        if (!__syncthreads_or(t0 + tid < gtiles && mine)) continue;   // (also the barrier between two rounds of words)
+        const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
+        for (int j = 0; j < nw; ++j) {
+          const float wj = s_word[j];
+          if (!(phase == 0 ? ord_f32(wj) <= kappa : (ord_f32(wj) > kappa && (all || !(wj > thr_out))))) continue;
+          const int64_t g0 = (t0 + j) * WITHIN_BM;
+          const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
+          const unsigned long long kth = s_list[k - 1];       // a word that is not below it cannot enter the list
+          bool any = false;
+          for (int r = wave; r < rows; r += WITHIN_NW) {
+            float d;
+            (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+            if (d == d) {                                     // a NaN distance is never listed
+              const unsigned long long cand = ((unsigned long long)ord_f32(d) << 32) | (unsigned)(g0 + r);
+              if (cand < kth) {
+                if (lane == 0) s_list[TOPK_MAX + r] = cand;
+                any = true;
+              }
+            }
+          }
+          if (!__syncthreads_or(any)) continue;
+          // bitonic sort of the 2 * TOPK_MAX words, ascending; empty slots are above every candidate
+          for (int k2 = 2; k2 <= 2 * TOPK_MAX; k2 <<= 1) {
+            for (int h = k2 >> 1; h > 0; h >>= 1) {
+              if (tid < TOPK_MAX) {
+                const int i = ((tid & ~(h - 1)) << 1) | (tid & (h - 1)), l = i | h;
+                const unsigned long long a = s_list[i], b = s_list[l];
+                if ((a > b) == ((i & k2) == 0)) {
+                  s_list[i] = b;
+                  s_list[l] = a;
+                }
+              }
+              __syncthreads();
+            }
+          }
+          if (tid >= k && tid < 2 * TOPK_MAX) s_list[tid] = TOPK_NONE;   // keep the smallest k
+          __syncthreads();
+        }
+        __syncthreads();                                      // s_word is rewritten by the next round
+      }
+    }
+  }
+
+  if (tid < k) {
+    const unsigned long long w = s_list[tid];
+    idx_out[(int64_t)p * k + tid] = w == TOPK_NONE ? -1 : (int64_t)(unsigned)w + index_base;
+    dist_out[(int64_t)p * k + tid] = w == TOPK_NONE ? __builtin_nanf("") : unord_f32((unsigned)(w >> 32));
+  }
+}
+
+template <class T>
+static int launch_tilemin(const Gallery* g, const float* probes, int B, int metric, hipStream_t st) {
+  auto kern = topk_tilemin_kernel<T>;
+  constexpr int lds = T::LDS_BYTES + T::WGM * T::BN * 4;
+  static bool done[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!done[dev]) {
+    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    done[dev] = true;
+  }
+  const int nparts = match_plan_parts(g, B, false);
+  const int cblocks = (B + T::BN - 1) / T::BN;
+  dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
+  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, g->n, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
+                     g->topk_min, nparts);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st) {
+  if (B <= 0) return 0;
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  const int clamp = g->clamp_nan ? 1 : 0;
+  const int seed = g->topk_seed > 0 ? g->topk_seed : k;
+  const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
+  // probes per round: whole 128-probe blocks whose tile words stay below TOPK_MIN_MAX (an empty gallery has none: one round)
+  int64_t per = gtiles > 0 ? (int64_t)(TOPK_MIN_MAX / (size_t)gtiles) / 128 * 128 : B;
+  if (per < 128) per = 128;
+  if (per > B) per = B;
+  const size_t need = (size_t)gtiles * (size_t)per;
+  if (need > g->topk_min_cap) {
+    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read it
+    if (grow(&g->topk_min, &g->topk_min_cap, need, sizeof(float))) return -1;
+  }
+  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int nb = (int)(B - b0 < per ? B - b0 : per);
+    const float* pr = probes + b0 * g->d;
+    if (gtiles > 0) {
+      const int kind = match_tile_kind(nb);
+      int rc;
+      if (kind == 4 && nb <= 32) rc = launch_tilemin<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st);
+      else if (kind == 1 || nb <= 64) rc = launch_tilemin<Tile<2, 1>>(g, pr, nb, metric, st);
+      else rc = launch_tilemin<Tile<2, 2>>(g, pr, nb, metric, st);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(topk_select_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows, g->d,
+                       metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k, dist_out + b0 * k);
     DIF_HIP(hipGetLastError());
   }
   return 0;

@@ -16,6 +16,7 @@ from . import _native as N
 
 
 MAX_HITS = 8192   # DIF_WITHIN_MAX_HITS (include/dif.h): the longest list `within` returns per probe
+TOPK_MAX = 128    # DIF_TOPK_MAX: the longest list `topk` returns per probe
 
 
 class Gallery:
@@ -124,7 +125,9 @@ class Gallery:
         'frag': layout of the one-term filter's copy -- 1 (default) MFMA-fragment order from 2^18 rows up (embedding sizes that
         are multiples of 128 up to 512), 2 always, 0 row-major; same results (include/dif.h).
         'clamp_nan': 1 reports distance 0 / 1 where the reference's distance is NaN (a similarity rounded
-        beyond +-1); the default 0 reports NaN like the reference.  The arg-min is unaffected."""
+        beyond +-1); the default 0 reports NaN like the reference.  The arg-min is unaffected.
+        'topk_seed': tiles of 128 rows the seed stage of `topk` evaluates per probe -- 0 (default): k of them; same results
+        for every value (include/dif.h)."""
         N.check(N.lib.dif_gallery_set_option(self._h, key.encode(), int(value)), ValueError)
 
     def stat(self, key):
@@ -303,6 +306,55 @@ class Gallery:
             rank, mate_dist = rank.cpu().numpy(), mate_dist.cpu().numpy()
         return rank, mate_dist
 
+    def topk_into(self, probes, k, distance_metric, idx, dist):
+        """Allocation-free form of `topk`: `probes` [B, d] float32 CUDA, results written into the caller's CUDA tensors
+        idx [B, k] int64 and dist [B, k] float32."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        k = int(k)
+        if k < 1 or k > TOPK_MAX:
+            raise ValueError('k %d outside [1, %d]' % (k, TOPK_MAX))
+        if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
+            raise ValueError('probes must be a [B, %d] tensor, got %s' % (
+                self.emd_size, tuple(probes.shape) if hasattr(probes, 'shape') else type(probes).__name__))
+        B = probes.shape[0]
+        for name, t, dt in (('probes', probes, torch.float32), ('idx', idx, torch.int64), ('dist', dist, torch.float32)):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('topk_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
+            if name != 'probes' and tuple(t.shape) != (B, k):
+                raise ValueError('topk_into: %s must have shape [%d, %d], got %s' % (name, B, k, tuple(t.shape)))
+        if B:
+            N.check(N.lib.dif_match_topk(self._h, N.ptr(probes), B, distance_metric, k, N.ptr(idx), N.ptr(dist),
+                                         N.stream_ptr()))
+
+    def topk(self, probes, k, distance_metric=1):
+        """The k nearest enrolled rows of each probe, in order, exact.  -> (idx[B, k] int64, dist[B, k] float32); NumPy in ->
+        NumPy out.  1 <= k <= 128.
+
+        Per probe q: ``d = evaluation.utility.distance(q[None, :], gallery, metric)``, ``order = np.argsort(d, kind='stable')``
+        (ascending distance, exact ties to the lower row), ``keep = order[~np.isnan(d[order])][:k]``; idx = keep + index_base,
+        dist = d[keep].  A NaN distance is never listed (set_option('clamp_nan', 1) orders and reports the clamped 0 / 1
+        instead); k above len(self), or fewer than k rows with a distance that is not NaN, pads with idx -1 and dist NaN, and
+        an empty gallery gives all padding.  `rank(q, idx[:, j])` returns `(j, dist[:, j])`; where no distance is NaN idx[:, 0]
+        is `match`'s row."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        k = int(k)
+        if k < 1 or k > TOPK_MAX:
+            raise ValueError('k %d outside [1, %d]' % (k, TOPK_MAX))
+        p, was_np = N.to_device_f32(probes, self._dev)
+        if p.dim() == 1:
+            p = p[None, :]
+        if p.dim() != 2 or p.shape[1] != self.emd_size:
+            raise ValueError('probes must be [B, %d], got %s' % (self.emd_size, tuple(p.shape)))
+        B = p.shape[0]
+        idx = torch.empty((B, k), dtype=torch.int64, device=self._dev)
+        dist = torch.empty((B, k), dtype=torch.float32, device=self._dev)
+        self.topk_into(p, k, distance_metric, idx, dist)
+        if was_np:
+            idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
+        return idx, dist
+
     def close(self):
         if self._h:
             N.lib.dif_gallery_destroy(self._h)
@@ -342,6 +394,16 @@ def rank(probes, gallery, mates, distance_metric=1):
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
         return g.rank(probes, mates, distance_metric)
+    finally:
+        if g is not gallery:
+            g.close()
+
+
+def topk(probes, gallery, k, distance_metric=1):
+    """One-call form of Gallery.topk: per probe, the k nearest gallery rows in order -> (idx[B, k], dist[B, k])."""
+    g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
+    try:
+        return g.topk(probes, k, distance_metric)
     finally:
         if g is not gallery:
             g.close()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed" (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -269,6 +269,9 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * "bd": 1 (default) the two-term filter ("filter" = 1) runs on match_bd_kernel from 65 probes up; 0 keeps it on
  * match_tile_kernel for every batch (tests, A/B).  Same answers.
  * "bd_fill": 1 (default) .. 16: blocks of match_bd_kernel per resident slot (development; no effect measured).
+ * "topk_seed": 0 (default) the seed stage of dif_match_topk evaluates the k gallery tiles with the smallest search keys
+ * per probe; n > 0 makes it n tiles (1: a loose first tolerance, the sweep stage does the work).  Same answers for every
+ * value (tests, A/B).
  * Every key the library accepts is listed here (dif_gallery_option_name; tests/test_cabi_symbols.py). */
 int dif_gallery_set_option(dif_gallery* g, const char* key, int value);
 /* read-outs (no reference counterpart; for capacity planning and tests).  "split_copy": 1 when the filter's bf16 copy
@@ -337,6 +340,28 @@ int dif_match_within(dif_gallery* g, const float* probes_dev, int n, int metric,
  *   shares dif_match_within's workspace (calls on one stream are ordered) plus 8 bytes per probe. */
 int dif_match_rank(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
                    int64_t* rank_out_dev /* [n] */, float* mate_dist_out_dev /* [n], may be NULL */, void* stream);
+/* top-k search of n probes [n][d]: the k nearest enrolled rows of each probe, in order, exact.  Per probe q
+ *     d     = utility.distance(q[None, :], gallery, metric)        the reference's float32 values
+ *     order = np.argsort(d, kind='stable')                         ascending distance; exact ties go to the lower row
+ *     keep  = order[~np.isnan(d[order])][:k]                       a NaN distance is never listed
+ *     idx_out_dev[p][0 .. len(keep))  = keep + index_base          (dif_gallery_set's index_base: global indices)
+ *     dist_out_dev[p][0 .. len(keep)) = d[keep]
+ *   unused slots -- k above the row count, or fewer than k rows with a distance that is not NaN -- hold idx -1 and dist NaN;
+ *   an empty gallery gives all padding (not an error).  k in [1, DIF_TOPK_MAX]; n = 0 is a no-op; a k outside the range, a
+ *   metric other than 0 / 1 or a NULL handle, probes or output fails.
+ * Units and arithmetic: as dif_match_within / dif_match_rank -- the distances ordered and reported are exactly the ones those
+ *   (and dif_match, dif_pairwise) report for the pair under the handle's "clamp_nan": metric 0 bit-identical to the reference;
+ *   metric 1 up to the arccos (evaluated in double and rounded once; NumPy's float32 arccos is within 2 ulp), so against NumPy
+ *   two rows whose distances lie within ~2e-6 of each other may swap.  On the library's own distances the list is exact on
+ *   both metrics: dif_match_rank of idx_out[p][j] returns (j, dist_out[p][j]).
+ * NaN rule: a row whose distance is NaN is never listed (with "clamp_nan" 1 the clamped 0 / 1 is ordered and reported
+ *   instead).  Where no distance of the probe is NaN, idx_out[p][0] is dif_match's row; they differ where there are NaNs.
+ * Costs one pass of the f32 MFMA over the gallery (dif_match_within's, keeping one minimum key per 128-row tile and probe)
+ *   plus the reference arithmetic on the tiles that can hold one of the k rows -- about k tiles per probe (option
+ *   "topk_seed"); no host synchronisation in steady state; its workspace (4 bytes per probe and 128 rows) is its own. */
+#define DIF_TOPK_MAX 128
+int dif_match_topk(dif_gallery* g, const float* probes_dev, int n, int metric, int k, int64_t* idx_out_dev /* [n][k] */,
+                   float* dist_out_dev /* [n][k] */, void* stream);
 /* merge R per-shard results laid out [R][n] (after an all-gather): lowest key, then
  * lowest global index -- equals np.argmin over the concatenated gallery */
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,
