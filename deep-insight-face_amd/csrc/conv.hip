@@ -2451,7 +2451,9 @@ int conv_run(const ConvArgs& a, hipStream_t st) {
       return set_error("conv: a 256-pixel tile spans more than 2 GiB of input (%dx%dx%d)", a.H, a.W, a.Cin);
   }
   // Winograd F(2x2,3x3) first: its decision reads the shape, the batch and the weights' presence only (conv_winograd.hpp)
-  if (const int wk = wino_applies(a)) return wk == 2 ? launch_conv_winow(a, st) : launch_conv_wino(a, st);
+  // [dbg bit 33554432: the odd maps and the sub-sampled outputs (class 3) stay on the direct kernels, A/B]
+  if (const int wk = wino_applies(a); wk && !(wk == 3 && (a.dbg & 33554432)))
+    return wk == 3 ? launch_conv_winox(a, st) : wk == 2 ? launch_conv_winow(a, st) : launch_conv_wino(a, st);
   // (four waves of 128 x 32 with a six-set B ring, and eight waves on a 256 x 128 tile -- Tile<4, 1, 1, 4>, Tile<2, 2, 4, 2>: the
   // mainloop takes either -- measured the same as this one within 2 %)
   // (three or two bf16 terms per operand: ConvArgs::bf_terms, picked inside the kernel)

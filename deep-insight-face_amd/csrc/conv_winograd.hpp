@@ -1,5 +1,5 @@
-// conv_wino_kernel: Winograd F(2x2, 3x3) for the large-batch 3x3 / stride 1 / pad 1 layers on even maps -- one kernel
-// template in three block shapes (WinoW, below).  Included by conv.hip (inside namespace dif, after the helpers it uses).
+// conv_wino_kernel: Winograd F(2x2, 3x3) for the large-batch 3x3 / stride 1 / pad 1 layers -- one kernel template in three block
+// shapes (WinoW, below) on even maps, and the half block in two more forms (WinoX) on odd maps and sub-sampled outputs.  Included by conv.hip (inside namespace dif, after the helpers it uses).
 //
 // A 3x3 convolution of a 4x4 input tile d is Y = A^T [ (G g G^T) .* (B^T d B) ] A: 2x2 outputs from 16 element-wise
 // products, i.e. 16 GEMMs M_c[tile][co] = sum_ci V_c[tile][ci] U_c[ci][co] with K = Cin instead of one with K = 9 Cin --
@@ -25,6 +25,12 @@ constexpr int64_t MIN_TILES = 64 * 49;
 // the wide maps (level 2): map sides up to 112, and at least 128 images per launch
 constexpr int WIDE_MAX_HW = 112;
 constexpr int64_t WIDE_MIN_IMAGES = 128;
+// the rest (level 2, class 3 of wino_applies): odd maps from 3 x 3 to 16 x 16 (a side of 1 or 2 is half padding: no fewer
+// multiply-adds than direct, and more blocks than the 64-pixel tiles the trace buffer is sized by) with at least the tiles of
+// 128 images of 7 x 7,
+// and even maps whose first output is sub-sampled (ConvArgs::y_sub); both from WIDE_MIN_IMAGES images per launch up
+constexpr int ODD_MAX_HW = 16;
+constexpr int64_t ODD_MIN_TILES = 128 * 16;
 }  // namespace wino
 
 // The block shapes.
@@ -49,11 +55,26 @@ struct WinoW {
   static constexpr int CPW = CPW_;                           // components per wave
   static constexpr int MIN_BLOCKS = MIN_BLOCKS_;             // blocks per CU the launch bound asks for
   static constexpr bool EARLY_REQ = EARLY_REQ_;
+  static constexpr bool ODD = false;                         // (WinoX, below)
+  static constexpr bool YSUB = false;
   static constexpr int MF = TT / 32;                         // 32-tile row fragments per component
   static constexpr int NT = 16 / CPW * 64;                   // threads per block (NT / 8 == TT: one tile x two channels each)
   static constexpr int STAGE = 16 * TT * wino::KC;           // floats per V stage
   static constexpr int LDS_BYTES = 2 * STAGE * 4;            // the epilogue's M half (16 x TT x 32 floats) fits the same
   static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
+};
+
+// The half block on the layers the even-map rule leaves out (wino_applies: 3), one form each:
+// ODD: a map with an odd side.  The tile grid is (H + 1) / 2 x (W + 1) / 2, i.e. the map zero-padded to even sides: vmask
+//   zeroes the input points beyond it as it does the halo, and the epilogue masks the output pixels of the row / column
+//   beyond it (shortcut load and both stores).  IResNet's 7 x 7 stage: 16 tiles per image for 49 pixels, 49 / 64 of 2.25x.
+// YSUB: an even map whose first output keeps the even pixels only (ConvArgs::y_sub): that pixel is output (0, 0) of its
+//   tile and its dense index is the tile's, g.  The second output and the shortcut are whole.
+template <bool ODD_, bool YSUB_>
+struct WinoX : WinoW<32, 4, 2, true> {
+  static constexpr bool ODD = ODD_;
+  static constexpr bool YSUB = YSUB_;
+  static_assert(!(ODD_ && YSUB_), "y_sub is admitted on even maps only");
 };
 
 // B^T x for one 4-vector: (x0 - x2, x1 + x2, x2 - x1, x1 - x3)
@@ -101,8 +122,11 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
   extern __shared__ __attribute__((aligned(16))) float wino_smem[];
   const int b = xcd_remap((int)blockIdx.x, nblocks);
   const int nt = b / blocks_m, mt = b - nt * blocks_m;   // column-slice-major: an XCD's blocks share one slice of U in its L2
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tw = a.W >> 1, tpi = (a.H >> 1) * tw, ntiles = a.N * tpi;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // (WinoX: the wave's number in a scalar register.  With it in a vector register the y_sub form, which carries one more
+  // value across the K loop, spilled the wave's LDS base to scratch; in the WinoW shapes it stays where it always was)
+  const int wave = (S::ODD || S::YSUB) ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+  const int tw = S::ODD ? (a.W + 1) >> 1 : a.W >> 1, tpi = (S::ODD ? (a.H + 1) >> 1 : a.H >> 1) * tw, ntiles = a.N * tpi;
   const int KS = a.Cin / KC;
   unsigned long long ts[5];
   ts[0] = wino_stamp<TRACE>();
@@ -230,7 +254,8 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
   // ---- epilogue: per 32-channel half, M through LDS, Y = A^T M A, BN / activation / shortcut / second output
   const int c4 = cp * 4;
   const uint32_t bytes = (uint32_t)a.M * (uint32_t)a.Cout * 4u;
-  const __amdgpu_buffer_rsrc_t y_rsrc = make_rsrc(a.y, a.y ? bytes : 0u);
+  // (YSUB: the first output is the dense [tile][Cout] tensor of the tiles' (0, 0) pixels)
+  const __amdgpu_buffer_rsrc_t y_rsrc = make_rsrc(a.y, a.y ? (S::YSUB ? (uint32_t)ntiles * (uint32_t)a.Cout * 4u : bytes) : 0u);
   const __amdgpu_buffer_rsrc_t y2_rsrc = make_rsrc(a.y2, a.y2 ? bytes : 0u);
   const __amdgpu_buffer_rsrc_t res_rsrc = make_rsrc(a.res, a.res ? bytes : 0u);
   const bool has_res = a.res != nullptr;
@@ -250,7 +275,10 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-        voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+        if constexpr (S::ODD)                        // output p is input point (1 + p / 2, 1 + p % 2) of the tile: on the map or not
+          voff[p] = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+        else
+          voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
         rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
       __builtin_amdgcn_sched_barrier(0);           // (the requests stay above the LDS traffic)
@@ -285,7 +313,10 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-        voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+        if constexpr (S::ODD)                        // output p is input point (1 + p / 2, 1 + p % 2) of the tile: on the map or not
+          voff[p] = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+        else
+          voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
         rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
@@ -293,7 +324,11 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
     for (int p = 0; p < 4; ++p) {
       f32x4 v, v2;
       epilogue4(yv[p], sc, sh, al, act, has_res, rv[p], sc2, sh2, al2, act2, v, v2);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
+      if constexpr (S::YSUB) {
+        if (p == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, tile_ok ? ((uint32_t)g * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB, 0, 0);
+      } else {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
+      }
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
     }
     lds_barrier();
@@ -303,24 +338,29 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
     if (tid == 0) wino_trace_write(a, tr_c0, ts);
 }
 
-// The layers the Winograd kernels take: 3x3 / stride 1 / pad 1 on an even map (no output shrink), whole 32-channel input
-// slices, whole 64-channel column blocks, no pre-activation, the lean epilogue's plain geometry and unit-stride shortcut,
-// 31-bit byte offsets.  Returns 1 for the narrow maps: at most 16 x 16 with at least wino::MIN_TILES Winograd tiles (level 1
+// The layers the Winograd kernels take: 3x3 / stride 1 / pad 1 (no output shrink), whole 32-channel input slices, whole
+// 64-channel column blocks, no pre-activation, the lean epilogue's plain geometry and unit-stride shortcut, 31-bit byte
+// offsets.  On an even map with a whole first output it returns 1 for the narrow maps: at most 16 x 16 with at least wino::MIN_TILES Winograd tiles (level 1
 // and up; launch_conv_wino runs them in 64-tile blocks at level 1 and in 32-tile blocks at level 2, the same bits); 2 for
 // the wide maps (launch_conv_winow): up to 112 x 112 with the tiles of at least wino::WIDE_MIN_IMAGES images (level 2);
-// 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether the net carries the transformed
+// 3 for the rest (launch_conv_winox; level 2, at least wino::WIDE_MIN_IMAGES images): a map from 3 x 3 to 16 x 16 with an odd
+// side and at least wino::ODD_MIN_TILES tiles of the padded grid, or an even map up to 112 x 112 whose first output is
+// sub-sampled (y_sub); 0 otherwise.  Depends on the shape, the batch of the launch, the level and whether the net carries the transformed
 // weights (Net option "wino") -- on nothing else.
 static int wino_applies(const ConvArgs& a) {
   if (!a.w_wino || a.wino_level < 1 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1) return 0;
-  if (a.Ho != a.H || a.Wo != a.W || (a.H & 1) || (a.W & 1)) return 0;
+  if (a.Ho != a.H || a.Wo != a.W) return 0;
+  const bool odd = (a.H & 1) || (a.W & 1), rest = odd || a.y_sub;
   const bool wide = a.H > 16 || a.W > 16;
+  if (rest && (a.wino_level < 2 || (odd && (a.y_sub || a.H > wino::ODD_MAX_HW || a.W > wino::ODD_MAX_HW || a.H < 3 || a.W < 3)))) return 0;
   if (wide && (a.wino_level < 2 || a.H > wino::WIDE_MAX_HW || a.W > wino::WIDE_MAX_HW)) return 0;
-  if (a.Cin % 32 != 0 || a.Cout % wino::BN != 0 || a.pre_scale || a.y_sub) return 0;
+  if (a.Cin % 32 != 0 || a.Cout % wino::BN != 0 || a.pre_scale) return 0;
   if (!(a.y_H == a.Ho && a.y_W == a.Wo && a.y_oy == 0 && a.y_ox == 0 && a.y_ld == a.Cout && a.y_coff == 0)) return 0;
   if (a.res && (a.res_stride != 1 || a.res_H != a.Ho || a.res_W != a.Wo)) return 0;
   if ((int64_t)a.M * a.Cout * 4 >= 0x7fffffffLL || (int64_t)a.M * a.Cin * 4 >= 0x7fffffffLL) return 0;
   if ((int64_t)16 * a.Cin * a.Cout * 4 > (int64_t)a.w_wino_bytes) return 0;
-  const int64_t tpi = (int64_t)(a.H / 2) * (a.W / 2);
+  const int64_t tpi = (int64_t)((a.H + 1) / 2) * ((a.W + 1) / 2);
+  if (rest) return a.N >= wino::WIDE_MIN_IMAGES && (!odd || a.N * tpi >= wino::ODD_MIN_TILES) ? 3 : 0;
   if (wide) return a.N * tpi >= wino::WIDE_MIN_IMAGES * tpi ? 2 : 0;
   return a.N * tpi >= wino::MIN_TILES ? 1 : 0;
 }
@@ -329,7 +369,7 @@ template <class S>
 static int launch_wino(const ConvArgs& a, hipStream_t st, const char* name) {
   const auto kern = a.trace ? conv_wino_kernel<S, true> : conv_wino_kernel<S, false>;
   if (allow_dynamic_lds(reinterpret_cast<const void*>(kern), S::LDS_BYTES)) return -1;
-  const int64_t ntiles = (int64_t)a.N * (a.H / 2) * (a.W / 2);
+  const int64_t ntiles = S::ODD ? (int64_t)a.N * ((a.H + 1) / 2) * ((a.W + 1) / 2) : (int64_t)a.N * (a.H / 2) * (a.W / 2);
   const int blocks_m = (int)((ntiles + S::TT - 1) / S::TT), tiles_n = a.Cout / wino::BN;
   const int64_t nblocks = (int64_t)blocks_m * tiles_n;
   if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
@@ -349,4 +389,10 @@ static int launch_conv_wino(const ConvArgs& a, hipStream_t st) {             // 
 static int launch_conv_winow(const ConvArgs& a, hipStream_t st) {            // wide maps (wino_applies: 2)
   if (a.dbg & 65536) return launch_wino<WinoW<64, 2, 2, true>>(a, st, "conv_winow_kernel<F(2x2,3x3),64 tiles x 64>");
   return launch_wino<WinoW<32, 4, 2, true>>(a, st, "conv_winow_kernel<F(2x2,3x3),32 tiles x 64>");
+}
+
+// the rest (wino_applies: 3): names of their own, so that the readers of the two lists above see neither class grow
+static int launch_conv_winox(const ConvArgs& a, hipStream_t st) {
+  if (a.y_sub) return launch_wino<WinoX<false, true>>(a, st, "conv_winox_kernel<F(2x2,3x3),32 tiles x 64,ysub>");
+  return launch_wino<WinoX<true, false>>(a, st, "conv_winox_kernel<F(2x2,3x3),32 tiles x 64,odd>");
 }

@@ -1112,16 +1112,19 @@ int Net::finalize(int mb) {
       // Winograd F(2x2,3x3) weights for conv_wino_kernel (conv_winograd.hpp): U_c[ci][co] = (G g G^T)[i][j], c = 4 i + j,
       // formed in double and rounded once, in the kernel's fragment order (1 KB per wave instruction).  Only for the layers
       // its shape rule can admit (wino_applies; the batch threshold is decided per launch) and only with option "wino" on:
-      // maps of at most 16 x 16 at level 1, the wide maps up to 112 x 112 (same kernel, same U layout) at level 2.
+      // maps of at most 16 x 16 at level 1, the wide maps up to 112 x 112 (same kernel, same U layout) at level 2; at level 2
+      // also the maps of at most 16 x 16 with an odd side and the layers whose first output is sub-sampled (y_sub: y is the
+      // small tensor there, the map is y2's).
       op.d_w_wino = nullptr;
       op.w_wino_bytes = 0;
       {
         const TensorDesc& xd = tensors[op.x];
-        const TensorDesc& yd = tensors[op.y >= 0 ? op.y : op.y2];
+        const TensorDesc& yd = tensors[op.y >= 0 && !op.y_sub ? op.y : op.y2];
+        const bool odd = xd.H % 2 != 0 || xd.W % 2 != 0, rest = odd || op.y_sub;
         if (use_wino && !compute_bf16x3 && op.KH == 3 && op.KW == 3 && op.stride == 1 && op.pad_t == 1 && op.pad_l == 1 &&
-            !op.pre_bn.valid() && !op.chw_flatten && !op.y_sub && op.Cin_true == op.Cin && op.Cin % BK == 0 &&
-            op.Cout % 64 == 0 && xd.H % 2 == 0 && xd.W % 2 == 0 && yd.H == xd.H && yd.W == xd.W &&
-            ((xd.H <= 16 && xd.W <= 16) || (use_wino >= 2 && xd.H <= 112 && xd.W <= 112)) &&
+            !op.pre_bn.valid() && !op.chw_flatten && !(rest && use_wino < 2) && !(odd && op.y_sub) && op.Cin_true == op.Cin && op.Cin % BK == 0 &&
+            op.Cout % 64 == 0 && yd.H == xd.H && yd.W == xd.W &&
+            ((xd.H <= 16 && xd.W <= 16) || (use_wino >= 2 && !odd && xd.H <= 112 && xd.W <= 112)) &&
             (uint64_t)16 * op.Cin * op.Cout * 4 < 0xFFFFFFF0ull) {
           static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
           const int KS16 = op.Cin / 16, NTn = op.Cout / 64;

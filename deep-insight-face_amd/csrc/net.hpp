@@ -150,7 +150,8 @@ struct Net {
   int compute_bf16x3 = 0;           // option "bf16x3" (set before finalize): convolutions on the split-bf16 MFMA path
   int use_pipe = 1;                 // option "pipe": 0 keeps every convolution on conv_igemm_kernel
   int use_wino = 2;                 // option "wino", a level: 1 the 14 x 14-class 3x3 layers of large batches on conv_wino_kernel,
-                                    // 2 also the wide maps (28 x 28 .. 112 x 112) of 128 images and up, all in half-size blocks, 0 neither
+                                    // 2 also the wide maps (28 x 28 .. 112 x 112), the odd maps (7 x 7) and the y_sub layers of 128 images
+                                    // and up, all in half-size blocks, 0 neither
   int use_bdp = 1;                  // option "bdp": 0 never conv_bdp_kernel, 1 where it pays, 2 wherever it can run
   int use_stem = 1;                 // option "stem": 0 runs 3-channel first layers on conv_igemm_kernel too
   int use_ysub = 1;                 // option "ysub" (before finalize): 0 keeps outputs read only at stride 2 dense

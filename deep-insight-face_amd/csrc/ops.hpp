@@ -53,7 +53,7 @@ struct ConvArgs {
   uint32_t w3f_bytes;   // gemm_mainloop_patch_bf3), [ceil(Cout/32)][Kpad/32][s 2][plane 3][lane 64][8]
   const float* w_wino;  // Winograd F(2x2,3x3) weights U = G g G^T (conv_winograd.hpp), or null: [16 component][Cout/64][Cin/16]
   uint32_t w_wino_bytes;  // [column half 2][k quad 2][lane 64][t 4] <- U[c][ci = 16 ks + 8 (lane >> 5) + 4 q + t][co = 64 nt + 32 nf + lane % 32]
-  int wino_level;       // Net option "wino": 0 direct everywhere, 1 conv_wino_kernel on maps up to 16 x 16, 2 also on the wide maps
+  int wino_level;       // Net option "wino": 0 direct everywhere, 1 conv_wino_kernel on maps up to 16 x 16, 2 also on the wide maps, odd maps and y_sub
   int bf_terms;         // 3 (or 0): all three planes, six products; 2: the hi and mid planes only, three products ("bf16x2")
   int k_order;          // 0: k = (kh*KW + kw)*Cin + ci (tap-major)
                         // 1: k = ((ci/32)*KH*KW + kh*KW + kw)*32 + ci%32 (channel-block-major, Cin % 32 == 0):

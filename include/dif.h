@@ -430,7 +430,11 @@ int dif_net_finalize(dif_net* net, int max_batch);
  *                operands, transforms and accumulation, different products -- about twice the direct path's rounding
  *                error per layer; 2 (default): level 1 plus the same layers on the wider even maps up to 112 x 112
  *                (IResNet's 28 x 28, 56 x 56 and 112 x 112 stages) from 128 images per launch up, all of them by the same
- *                kernel in half-size blocks, two per CU (the same bits); 0: the direct f32 fma chain everywhere.  Any time;
+ *                kernel in half-size blocks, two per CU (the same bits), and, also from 128 images per launch up, the layers
+ *                the even-map rule leaves out (reported as conv_winox_kernel): maps of at most 16 x 16 with an odd side and
+ *                at least 2048 Winograd tiles per launch (IResNet's 7 x 7 stage: tiled as the map zero-padded to even
+ *                sides) and even maps whose first output is written at even pixels only ("ysub"); 0: the direct f32 fma
+ *                chain everywhere.  Any time;
  *                raised after a dif_net_finalize that ran below it, the new level takes effect at the next
  *                dif_net_finalize, which builds the transformed weights; lowered and raised back, at the next forward
  *   "bf16x3"     0 (default): float32 MFMA -- with "wino" = 0 a bit-exact f32 fma chain, the reference's arithmetic;
@@ -444,7 +448,9 @@ int dif_net_finalize(dif_net* net, int max_batch);
  *   "lane_prio"  0 (default; before dif_net_finalize): all lanes of a multi-lane forward run on least-priority streams
  *                (own hardware queues, whatever else the process created); 1: lane 0 on the caller's stream
  *   "dbg"        0 (default): development aid, bit mask (256: block traces from dif_net_embed_clock; 1024: every layer on
- *                the general epilogue; other bits: ablations of the kernel under work)
+ *                the general epilogue; 33554432: at "wino" = 2 the odd maps and the sub-sampled outputs -- the
+ *                conv_winox_kernel layers -- stay on the direct kernels, the A/B switch of that class; other bits: ablations
+ *                of the kernel under work)
  * env DIF_OPTIONS="key=value,..." applies keys to every net of the process at dif_net_finalize (A/B runs of the tools). */
 int dif_net_set_option(dif_net* net, const char* key, int value);
 /* the i-th key dif_net_set_option / dif_gallery_set_option accepts, NULL past the last one (so that the list above can be
