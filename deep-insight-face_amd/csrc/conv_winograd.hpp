@@ -14,7 +14,11 @@
 // writes them to LDS ([component][tile][16 ch], 16-byte chunks XOR-swizzled by tile); two such stages alternate, one
 // barrier per K-step.  A operands come from LDS, B operands (U in fragment order: 1 KB per wave instruction) straight
 // from L2; both sit in two register sets, component j in set j & 1, fetched two components ahead (B across the K-step
-// boundary).  The epilogue stages M in LDS one 32-channel half at a time, applies A^T M A and epilogue4 (conv.hip).
+// boundary).  The K loop runs every step but the last with all its loads unconditional and the last step peeled; the
+// next step's tile loads are issued half a step in, behind the B loads of the second half, and first waited on by the
+// transform at the end of the step (vmcnt retires in order: what is issued behind them would wait for them).  The
+// compiled order of issue, waits and registers of every instantiation: profiles/r11_wino_kloop_isa.txt, DESIGN 4b.
+// The epilogue stages M in LDS one 32-channel half at a time, applies A^T M A and epilogue4 (conv.hip).
 // Every accumulator sums the same products in the same order in every shape: the block shape changes no bit.
 namespace wino {
 constexpr int BN = 64;                         // output channels per block
@@ -228,26 +232,35 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
     vstore(wino_smem, d);
     lds_barrier();
     ts[1] = wino_stamp<TRACE>();
-    for (int ks = 0; ks < KS; ++ks) {
+    // One K-step; `last` is a compile-time flag (the final step fetches nothing for a next one).  Every step but the last runs
+    // in the loop with all its loads unconditional, the last one is peeled: with the loads under a run-time `more` the
+    // two paths met at one label and the waits in front of the first MFMAs were those of the path WITHOUT the tile loads
+    // (vmcnt retires in order: a wait counted for the B loads alone drained the tile loads issued just before).
+    // Order of issue: the tile loads of step ks + 1 go out after the B loads of this step's second half, so every B wait
+    // in front of the second half's MFMAs counts loads issued before them, and they have that half's MFMAs as cover.
+    auto step = [&](int ks, auto last) {
       const float* cur = wino_smem + (ks & 1) * S::STAGE;
       float* nxt = wino_smem + ((ks + 1) & 1) * S::STAGE;
-      const bool more = ks + 1 < KS;
-      if (more) dload(ks + 1, d);
       aread(cur, 0);
       aread(cur, 1);
 #pragma unroll
       for (int j = 0; j < CPW; ++j) {
         mfma(j);
+        __builtin_amdgcn_sched_barrier(0);
         if (j + 2 < CPW) {
           aread(cur, j + 2);
           bload(j + 2, ks);
-        } else if (more) {
+        } else if (!last.value) {
           bload(j + 2 - CPW, ks + 1);
         }
+        if (!last.value && j == CPW / 2 - 1) dload(ks + 1, d);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      if (more) vstore(nxt, d);
+      if (!last.value) vstore(nxt, d);
       lds_barrier();
-    }
+    };
+    for (int ks = 0; ks + 1 < KS; ++ks) step(ks, std::false_type{});
+    step(KS - 1, std::true_type{});
   }
   ts[2] = wino_stamp<TRACE>();
 
