@@ -8,7 +8,8 @@
 // chain: the per-layer error is about twice the direct path's (tools/winograd_error.py, profiles/r06_winograd_error.txt).
 //
 // Block: TT Winograd tiles (numbered linearly over image x tile grid, so a block may span images) x 64 output channels
-// x all 16 components on 16 / CPW waves; wave w owns components CPW w .. CPW w + CPW - 1 (TT / 32 row fragments x two
+// x all 16 components on 16 / CPW waves; wave w owns components CPW w .. CPW w + CPW - 1 in the eight-wave shapes and
+// w, 4 + w, 8 + w, 12 + w -- a column of the 4 x 4 grid -- in the four-wave ones (TT / 32 row fragments x two
 // 32-channel column fragments each: 128 accumulators per lane in every shape).  Per K-step of 16 input channels every
 // thread fetches one 4x4 input tile of two channels (zero halo from out-of-range buffer loads), forms its 16 V values and
 // writes them to LDS ([component][tile][16 ch], 16-byte chunks XOR-swizzled by tile); two such stages alternate, one
@@ -18,8 +19,13 @@
 // next step's tile loads are issued half a step in, behind the B loads of the second half, and first waited on by the
 // transform at the end of the step (vmcnt retires in order: what is issued behind them would wait for them).  The
 // compiled order of issue, waits and registers of every instantiation: profiles/r11_wino_kloop_isa.txt, DESIGN 4b.
-// The epilogue stages M in LDS one 32-channel half at a time, applies A^T M A and epilogue4 (conv.hip).
-// Every accumulator sums the same products in the same order in every shape: the block shape changes no bit.
+// The epilogue of the eight-wave shapes stages M in LDS one 32-channel half at a time, applies A^T M A and epilogue4
+// (conv.hip).  In the four-wave shapes (WinoW::ONE_PASS) every wave first sums its grid column on its own accumulators
+// -- s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3, the first stage of A^T M A in the order the two-pass form uses -- so eight
+// planes instead of sixteen go through LDS, both halves in one pass with one barrier, and the shortcut tiles of both
+// halves are requested inside the peeled last K-step, into the tile loader's registers.
+// Every accumulator sums the same products in the same order in every shape, and every output the same terms in the same
+// order in both epilogues: the block shape changes no bit.
 namespace wino {
 constexpr int BN = 64;                         // output channels per block
 constexpr int KC = 16;                         // input channels per K-step
@@ -37,6 +43,10 @@ constexpr int ODD_MAX_HW = 16;
 constexpr int64_t ODD_MIN_TILES = 128 * 16;
 }  // namespace wino
 
+#ifndef DIF_WINO_RES_UNDER_K
+#define DIF_WINO_RES_UNDER_K 1                 // (WinoW::RES_UNDER_K)
+#endif
+
 // The block shapes.
 // <64, 2, 1, false>: 64 tiles on eight waves, 128 KiB of LDS, one block per CU -- the narrow maps (at most 16 x 16: IResNet's
 //   14 x 14 stage) at option "wino" = 1 [and at level 2 under dbg bit 16777216, A/B].  K = 256 .. 512 is 16 .. 32 K-steps,
@@ -52,7 +62,9 @@ constexpr int64_t ODD_MIN_TILES = 128 * 16;
 // <64, 2, 2, true>: the full-size block on the wide maps, kept for A/B runs [dbg bit 65536].
 // EARLY_REQ: the epilogue requests each half's shortcut tile and BN / PReLU vectors before M goes to LDS (the operand
 // registers of the K loop are dead by then), so their latency is not paid after the staging barrier; the level 1 shape
-// requests them after the output transform, as it always has.
+// requests them after the output transform, as it always has.  (Read by the two-pass epilogue only, i.e. by <64, 2, 2, true>
+// and <64, 2, 1, false>: the four-wave shapes' one-pass epilogue requests the vectors behind the K loop and the shortcut
+// tiles inside its last step: ONE_PASS, RES_UNDER_K.)
 template <int TT_, int CPW_, int MIN_BLOCKS_, bool EARLY_REQ_>
 struct WinoW {
   static constexpr int TT = TT_;                             // Winograd tiles per block
@@ -65,7 +77,17 @@ struct WinoW {
   static constexpr int NT = 16 / CPW * 64;                   // threads per block (NT / 8 == TT: one tile x two channels each)
   static constexpr int STAGE = 16 * TT * wino::KC;           // floats per V stage
   static constexpr int LDS_BYTES = 2 * STAGE * 4;            // the epilogue's M half (16 x TT x 32 floats) fits the same
+  // The four-wave shapes: wave w owns the COLUMN w, 4 + w, 8 + w, 12 + w of the 4 x 4 component grid, so the first stage
+  // of A^T M A (over the grid's rows) is the wave's own and eight planes, not sixteen, go through LDS: all 64 channels
+  // in one pass (8 x 32 tiles x 64 channels = LDS_BYTES).  The eight-wave shapes own rows, CPW w .. CPW w + CPW - 1.
+  static constexpr bool ONE_PASS = CPW_ == 4;
+  static constexpr int COMP_W = ONE_PASS ? 1 : CPW_;          // component j of wave w is COMP_W w + COMP_J j
+  static constexpr int COMP_J = ONE_PASS ? 4 : 1;
+  // ONE_PASS: the shortcut tiles of both column fragments are requested inside the peeled last K-step, into the registers
+  // the tile loader has left (-DDIF_WINO_RES_UNDER_K=0 requests them behind the K loop instead: the A/B build of round 12)
+  static constexpr bool RES_UNDER_K = ONE_PASS && DIF_WINO_RES_UNDER_K;
   static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
+  static_assert(!ONE_PASS || (TT == 32 && 8 * TT * wino::BN * 4 <= LDS_BYTES), "one pass: eight planes of 32 tiles x 64 channels");
 };
 
 // The half block on the layers the even-map rule leaves out (wino_applies: 3), one form each:
@@ -101,7 +123,8 @@ __device__ __forceinline__ void wino_input_transform(const float (&d)[16], float
 // Block trace (ConvArgs::trace, net.hip: option dbg = 256): the TRACE instantiations stamp the block's start, the first
 // barrier, the end of the K loop and the end of each epilogue half in 100 MHz ticks; thread 0 writes the eight-word record
 // of the direct kernels with low byte 3: [K loop, set-up, epilogue half 0, epilogue half 1, HW_ID | XCC_ID << 32, start,
-// end, 3 | cycles << 8].  The launcher picks TRACE = false whenever trace is null: that code holds no stamp and no branch
+// end, 3 | cycles << 8].  The one-pass shapes put "stage" (K-loop end to the staging barrier: requests, first stage, LDS
+// writes) and "finish" (LDS reads, second stage, epilogue4, stores) in the two epilogue words.  The launcher picks TRACE = false whenever trace is null: that code holds no stamp and no branch
 // on trace (a branch alone moved the register allocation of these kernels, which sit at the 256-VGPR limit).
 template <bool TRACE>
 __device__ __forceinline__ unsigned long long wino_stamp() {
@@ -180,8 +203,8 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
   const int h = lane >> 5, r32 = lane & 31, sw = (r32 >> 2) & 3;
   const int tiles_n = a.Cout / wino::BN;
   const __amdgpu_buffer_rsrc_t wrs = make_rsrc(a.w_wino, a.w_wino_bytes);
-  const uint32_t boff0 = (uint32_t)((CPW * wave * tiles_n + nt) * KS) * 4096u + (uint32_t)lane * 16u;
-  const uint32_t bstep = (uint32_t)(tiles_n * KS) * 4096u;     // one component on
+  const uint32_t boff0 = (uint32_t)((S::COMP_W * wave * tiles_n + nt) * KS) * 4096u + (uint32_t)lane * 16u;
+  const uint32_t bstep = (uint32_t)(S::COMP_J * tiles_n * KS) * 4096u;     // the wave's next component
   f32x4 bw[2][2][2];                             // [set][column fragment][k quad]
   auto bload = [&](int j, int ks) {
 #pragma unroll
@@ -200,7 +223,7 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
     for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
       for (int q = 0; q < 2; ++q)
-        av[j & 1][mf][q] = *reinterpret_cast<const f32x4*>(buf + (CPW * wave + j) * (TT * KC) + mf * 32 * KC + aoff[q]);
+        av[j & 1][mf][q] = *reinterpret_cast<const f32x4*>(buf + (S::COMP_W * wave + S::COMP_J * j) * (TT * KC) + mf * 32 * KC + aoff[q]);
   };
   f32x16 acc[CPW][MF][2];                        // [component][row fragment][column fragment]
 #pragma unroll
@@ -221,6 +244,29 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
 #pragma unroll
           for (int nf = 0; nf < 2; ++nf)
             acc[j][mf][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j & 1][mf][q][t], bw[j & 1][nf][q][t], acc[j][mf][nf], 0, 0, 0);
+  };
+
+  // ---- (ONE_PASS) the byte offsets of the tile's four outputs in both column fragments, for the shortcut loads and the stores
+  // alike, and the request of the shortcut tiles.  The request is unconditional: without a shortcut the descriptor has size
+  // zero and the loads return 0 without touching memory (a run-time branch inside the peeled K-step would bring two paths
+  // to one label and with them the wait counts of the path without the loads).
+  uint32_t voff8[2][4];
+  f32x4 rv8[2][4];
+  auto res_request = [&]() {
+    const __amdgpu_buffer_rsrc_t res_rsrc = make_rsrc(a.res, a.res ? (uint32_t)a.M * (uint32_t)a.Cout * 4u : 0u);
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int pix = pix0 + (p >> 1) * a.W + (p & 1), c = nt * wino::BN + nf * 32 + cp * 4;
+        // Output p is input point (1 + p / 2, 1 + p % 2) of the tile: its vmask bit says whether it is on the map (ODD) and,
+        // on an even map, whether the tile exists at all.  Off the map the offset becomes OOB by arithmetic (the offsets
+        // are multiples of 16): written as a select, the compiler made divergent branches of it inside the K-step, a
+        // load in each arm, and counted the waits of the MFMAs behind them for the shorter path.
+        const uint32_t off_map = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) - 1u;          // 0 on the map, ~0 off it
+        voff8[nf][p] = (((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u) | (off_map & OOB);
+        rv8[nf][p] = buf_load4(res_rsrc, voff8[nf][p]);
+      }
   };
 
   // ---- main loop
@@ -254,6 +300,9 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
           bload(j + 2 - CPW, ks + 1);
         }
         if (!last.value && j == CPW / 2 - 1) dload(ks + 1, d);
+        // (the peeled step has no tile to fetch: d's registers take the shortcut tiles, whose latency then runs under
+        // the second half's MFMAs and the epilogue's first stage)
+        if (last.value && S::RES_UNDER_K && j == CPW / 2 - 1) res_request();
         __builtin_amdgcn_sched_barrier(0);
       }
       if (!last.value) vstore(nxt, d);
@@ -273,79 +322,140 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
   const __amdgpu_buffer_rsrc_t res_rsrc = make_rsrc(a.res, a.res ? bytes : 0u);
   const bool has_res = a.res != nullptr;
   const int act = a.act, act2 = a.act2;
+  if constexpr (S::ONE_PASS) {
+    // ---- one pass.  Y = A^T M A sums the component grid's rows first: s0[w] = m[w] + m[4 + w] + m[8 + w] and
+    // s1[w] = m[4 + w] - m[8 + w] - m[12 + w] have all their operands in wave w's accumulators, element for element.
+    // The same adds in the same order as the two-pass form below, so the same bits.
+    static_assert(MF == 1 && CPW == 4, "one row fragment, one grid column per wave");
+    if constexpr (!S::RES_UNDER_K) res_request();
+    // the per-channel vectors of both fragments, into the registers the K loop's operands have left (L2 hits)
+    f32x4 sc[2], sh[2], al[2], sc2[2], sh2[2], al2[2];
 #pragma unroll
-  for (int nf = 0; nf < 2; ++nf) {
-    const int c = nt * wino::BN + nf * 32 + c4;
-    // The half's per-channel vectors and shortcut tile are requested in one of two places (S::EARLY_REQ).  The requests are
-    // written out at both: behind a lambda, a member or a free function the 32-tile shape spilled to scratch and the traced
-    // 64-tile kernels went from 254 to 256 VGPRs (profiles/r09_wino_unified_isa.txt).
-    f32x4 sc, sh, al, sc2, sh2, al2, rv[4];
-    uint32_t voff[4];
-    if constexpr (S::EARLY_REQ) {
-      // into the registers the K loop's operands have left: the latency runs under the LDS round trip of M, not after it
-      sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
-      sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-        if constexpr (S::ODD)                        // output p is input point (1 + p / 2, 1 + p % 2) of the tile: on the map or not
-          voff[p] = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-        else
-          voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-        rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      __builtin_amdgcn_sched_barrier(0);           // (the requests stay above the LDS traffic)
+    for (int nf = 0; nf < 2; ++nf) {
+      const int c = nt * wino::BN + nf * 32 + c4;
+      sc[nf] = load4_or(a.scale, c, 1.f), sh[nf] = load4_or(a.shift, c, 0.f), al[nf] = load4_or(a.alpha, c, 0.f);
+      sc2[nf] = load4_or(a.scale2, c, 1.f), sh2[nf] = load4_or(a.shift2, c, 0.f), al2[nf] = load4_or(a.alpha2, c, 0.f);
     }
+    __builtin_amdgcn_sched_barrier(0);             // (the requests stay above the LDS traffic)
 #pragma unroll
-    for (int j = 0; j < CPW; ++j)
+    for (int nf = 0; nf < 2; ++nf) {
+      acc[3][0][nf] = (acc[1][0][nf] - acc[2][0][nf]) - acc[3][0][nf];       // s1[w]
+      acc[0][0][nf] = (acc[0][0][nf] + acc[1][0][nf]) + acc[2][0][nf];       // s0[w]
+    }
+    // plane (s, w) of fragment nf at [(4 s + w) * 2 + nf][tile][32 ch]: the rows of the two-pass layout, so the same
+    // conflict-free ds_write_b32 / ds_read_b128 patterns
 #pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
+    for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          wino_smem[(CPW * wave + j) * (TT * 32) + (mf * 32 + frag_row(lane, r)) * 32 + r32] = acc[j][mf][nf][r];
+      for (int r = 0; r < 16; ++r) {
+        wino_smem[(wave * 2 + nf) * (TT * 32) + frag_row(lane, r) * 32 + r32] = acc[0][0][nf][r];
+        wino_smem[((4 + wave) * 2 + nf) * (TT * 32) + frag_row(lane, r) * 32 + r32] = acc[3][0][nf][r];
+      }
     lds_barrier();
-    f32x4 m[16];
+    ts[3] = wino_stamp<TRACE>();
 #pragma unroll
-    for (int k = 0; k < 16; ++k) m[k] = *reinterpret_cast<const f32x4*>(wino_smem + k * (TT * 32) + ltile * 32 + c4);
-    f32x4 yv[4];                                  // outputs (0,0), (0,1), (1,0), (1,1) of the tile
-    {
+    for (int nf = 0; nf < 2; ++nf) {
       f32x4 s0[4], s1[4];
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
-        s0[jj] = m[jj] + m[4 + jj] + m[8 + jj];
-        s1[jj] = m[4 + jj] - m[8 + jj] - m[12 + jj];
+        s0[jj] = *reinterpret_cast<const f32x4*>(wino_smem + (jj * 2 + nf) * (TT * 32) + ltile * 32 + c4);
+        s1[jj] = *reinterpret_cast<const f32x4*>(wino_smem + ((4 + jj) * 2 + nf) * (TT * 32) + ltile * 32 + c4);
       }
+      f32x4 yv[4];                                  // outputs (0,0), (0,1), (1,0), (1,1) of the tile
       yv[0] = s0[0] + s0[1] + s0[2];
       yv[1] = s0[1] - s0[2] - s0[3];
       yv[2] = s1[0] + s1[1] + s1[2];
       yv[3] = s1[1] - s1[2] - s1[3];
-    }
-    if constexpr (!S::EARLY_REQ) {
-      sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
-      sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        const int pix = pix0 + (p >> 1) * a.W + (p & 1);
-        if constexpr (S::ODD)                        // output p is input point (1 + p / 2, 1 + p % 2) of the tile: on the map or not
-          voff[p] = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-        else
-          voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
-        rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 v, v2;
+        epilogue4(yv[p], sc[nf], sh[nf], al[nf], act, has_res, rv8[nf][p], sc2[nf], sh2[nf], al2[nf], act2, v, v2);
+        if constexpr (S::YSUB) {
+          if (p == 0)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc,
+                                                   tile_ok ? ((uint32_t)g * (uint32_t)a.Cout + (uint32_t)(nt * wino::BN + nf * 32 + c4)) * 4u : OOB, 0, 0);
+        } else {
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff8[nf][p], 0, 0);
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff8[nf][p], 0, 0);
       }
     }
+    ts[4] = wino_stamp<TRACE>();                   // (no barrier: nothing writes LDS after the last read of a block)
+  } else {
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      f32x4 v, v2;
-      epilogue4(yv[p], sc, sh, al, act, has_res, rv[p], sc2, sh2, al2, act2, v, v2);
-      if constexpr (S::YSUB) {
-        if (p == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, tile_ok ? ((uint32_t)g * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB, 0, 0);
-      } else {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
+    for (int nf = 0; nf < 2; ++nf) {
+      const int c = nt * wino::BN + nf * 32 + c4;
+      // The half's per-channel vectors and shortcut tile are requested in one of two places (S::EARLY_REQ).  The requests are
+      // written out at both: behind a lambda, a member or a free function the 32-tile shape spilled to scratch and the traced
+      // 64-tile kernels went from 254 to 256 VGPRs (profiles/r09_wino_unified_isa.txt).
+      f32x4 sc, sh, al, sc2, sh2, al2, rv[4];
+      uint32_t voff[4];
+      if constexpr (S::EARLY_REQ) {
+        // into the registers the K loop's operands have left: the latency runs under the LDS round trip of M, not after it
+        sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
+        sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int pix = pix0 + (p >> 1) * a.W + (p & 1);
+          if constexpr (S::ODD)                        // output p is input point (1 + p / 2, 1 + p % 2) of the tile: on the map or not
+            voff[p] = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+          else
+            voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+          rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        __builtin_amdgcn_sched_barrier(0);           // (the requests stay above the LDS traffic)
       }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
+#pragma unroll
+      for (int j = 0; j < CPW; ++j)
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            wino_smem[(CPW * wave + j) * (TT * 32) + (mf * 32 + frag_row(lane, r)) * 32 + r32] = acc[j][mf][nf][r];
+      lds_barrier();
+      f32x4 m[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) m[k] = *reinterpret_cast<const f32x4*>(wino_smem + k * (TT * 32) + ltile * 32 + c4);
+      f32x4 yv[4];                                  // outputs (0,0), (0,1), (1,0), (1,1) of the tile
+      {
+        f32x4 s0[4], s1[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          s0[jj] = m[jj] + m[4 + jj] + m[8 + jj];
+          s1[jj] = m[4 + jj] - m[8 + jj] - m[12 + jj];
+        }
+        yv[0] = s0[0] + s0[1] + s0[2];
+        yv[1] = s0[1] - s0[2] - s0[3];
+        yv[2] = s1[0] + s1[1] + s1[2];
+        yv[3] = s1[1] - s1[2] - s1[3];
+      }
+      if constexpr (!S::EARLY_REQ) {
+        sc = load4_or(a.scale, c, 1.f), sh = load4_or(a.shift, c, 0.f), al = load4_or(a.alpha, c, 0.f);
+        sc2 = load4_or(a.scale2, c, 1.f), sh2 = load4_or(a.shift2, c, 0.f), al2 = load4_or(a.alpha2, c, 0.f);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int pix = pix0 + (p >> 1) * a.W + (p & 1);
+          if constexpr (S::ODD)                        // output p is input point (1 + p / 2, 1 + p % 2) of the tile: on the map or not
+            voff[p] = ((vmask >> (5 + 4 * (p >> 1) + (p & 1))) & 1u) ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+          else
+            voff[p] = tile_ok ? ((uint32_t)pix * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB;
+          rv[p] = has_res ? buf_load4(res_rsrc, voff[p]) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        f32x4 v, v2;
+        epilogue4(yv[p], sc, sh, al, act, has_res, rv[p], sc2, sh2, al2, act2, v, v2);
+        if constexpr (S::YSUB) {
+          if (p == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, tile_ok ? ((uint32_t)g * (uint32_t)a.Cout + (uint32_t)c) * 4u : OOB, 0, 0);
+        } else {
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, voff[p], 0, 0);
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v2), y2_rsrc, voff[p], 0, 0);
+      }
+      lds_barrier();
+      ts[3 + nf] = wino_stamp<TRACE>();
     }
-    lds_barrier();
-    ts[3 + nf] = wino_stamp<TRACE>();
   }
   if constexpr (TRACE)
     if (tid == 0) wino_trace_write(a, tr_c0, ts);

@@ -1749,7 +1749,8 @@ int Net::embed_clock(const void* xin, int n, int layout, int dtype, float* out, 
                 lag += (double)(u[5] - v[5]);
                 ++pairs;
               }
-        fprintf(stderr, "      winograd: epilogue halves %.1f + %.1f us/block | %zu CUs, %.2f blocks/CU | blocks starting beside a resident one: %d, "
+        // (the two epilogue words: halves 0 and 1 in the 64-tile shapes, stage + finish in the one-pass 32-tile shapes)
+        fprintf(stderr, "      winograd: epilogue halves | stage + finish %.1f + %.1f us/block | %zu CUs, %.2f blocks/CU | blocks starting beside a resident one: %d, "
                         "%.1f us = %.2f of its life after it\n", w_e0 / nb / 100.0, w_e1 / nb / 100.0, w_cu.size(), (double)nb / w_cu.size(), pairs,
                 pairs ? lag / pairs / 100.0 : 0.0, pairs ? ph / pairs : 0.0);
       }

@@ -2,6 +2,7 @@
 """SHA-256 digests of whole-net outputs (raw float32 bytes) on the cases that reach every conv_wino_kernel instantiation.
 
     python tools/winograd_bits.py --commit $(git rev-parse HEAD) [--lib libdif_parent.so] [--out tests/golden/winograd_bits.json]
+    python tools/winograd_bits.py --cases epilogue --commit ...     (EPILOGUE_CASES -> tests/golden/winograd_epilogue_bits.json)
 
 A change that only re-schedules the Winograd K loop must leave every bit of the outputs where it was.  The suite holds the
 kernels to the oracle and to each other, but nothing in it holds one commit to the one before: this file does.  The golden
@@ -46,6 +47,34 @@ CASES = {
 K2_LAYER = ('yolov3_129', 'conv_3', 9 * 32 * 64 * 16 * 32)      # (case, layer, its multiply-adds per image: op_table())
 DEFAULTS = {'wino': 2, 'dbg': 0}
 
+# A second list, for a change to the half block's epilogue (round 12: one pass through LDS for both column fragments, the
+# shortcut tiles requested under the last K-step); tests/test_winograd_epilogue_gpu.py.  Here the last field names the
+# layers the case is there for: {layer: (kernel, multiply-adds per image)}, checked against op_table().
+ODD, YSUB = 'conv_winox_kernel<F(2x2,3x3),%s,odd>' % HALF, 'conv_winox_kernel<F(2x2,3x3),%s,ysub>' % HALF
+EPILOGUE_CASES = {
+    # ResNet-50V2 maps out ('v3') at 128 images, the fewest the odd-map rule admits: conv4 on 7 x 9 (4 x 5 tiles: the last tile
+    # row and column half off the map) and on 8 x 7 -- masked output pixels in both column fragments of one pass
+    'resnet50v2_128_7x9': ('resnet', 'v3', 512, (112, 144), 128, {'wino': 2},
+                           {'conv4_block%d_2_conv' % b: (ODD, 9 * 256 * 256 * 7 * 9) for b in range(1, 6)}),
+    'resnet50v2_128_8x7': ('resnet', 'v3', 512, (128, 112), 128, {'wino': 2},
+                           {'conv4_block%d_2_conv' % b: (ODD, 9 * 256 * 256 * 8 * 7) for b in range(1, 6)}),
+    # the y_sub layer with Cout = 64 (one column block): IResNet-50's layer1_2_conv2 on 56 x 56; 129 images are 3 160 whole
+    # blocks and a half-filled one, whose dense first store comes from the one-pass layout
+    'iresnet50_129_ysub64': ('iresnet50', 'v2', 512, (112, 112), 129, {'wino': 2},
+                             {'layer1_2_conv2': (YSUB, 9 * 64 * 64 * 56 * 56)}),
+    # K of 2 steps with a shortcut (Darknet-53's conv_3 adds its block's input after the leaky ReLU): the shortcut requests
+    # go out one loop pass after the prologue
+    'yolov3_129_k2_shortcut': ('yolov3', 'v3', 1, (32, 64), 129, {'wino': 2},
+                               {'conv_3': ('conv_winow_kernel<F(2x2,3x3),%s>' % HALF, K2_LAYER[2])}),
+}
+
+
+def check_layers(model, kern, want):
+    """The layers an EPILOGUE_CASES entry names ran the kernel it names, on the shape it names."""
+    macs = {nm: mac for nm, _, mac in model.op_table()}
+    for layer, (kernel, mac) in want.items():
+        assert kern.get(layer) == kernel and macs[layer] == mac, (layer, kern.get(layer), macs.get(layer))
+
 
 def digest(out):
     """SHA-256 over the raw bytes of the output tensor (of every output in order, for a net with several)."""
@@ -78,8 +107,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lib', help='library file name under deep-insight-face_amd/lib (DIF_LIB)')
     ap.add_argument('--commit', required=True, help='the commit the library was built from')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'tests', 'golden', 'winograd_bits.json'))
+    ap.add_argument('--cases', choices=['kloop', 'epilogue'], default='kloop', help='CASES or EPILOGUE_CASES')
+    ap.add_argument('--out', help='default: tests/golden/winograd_bits.json, or winograd_epilogue_bits.json for --cases epilogue')
     args = ap.parse_args()
+    epi = args.cases == 'epilogue'
+    out = args.out or os.path.join(ROOT, 'tests', 'golden', 'winograd_epilogue_bits.json' if epi else 'winograd_bits.json')
     if args.lib:
         os.environ['DIF_LIB'] = args.lib
     os.environ['DIF_STREAMS'] = '1'
@@ -87,7 +119,7 @@ def main():
     import torch
     from deep_insight_face.networks.triplet import DifEmbedder
     nets, res = {}, {'commit': args.commit, 'cases': {}}
-    for name, (arch, head, emd, hw, n, opts, want) in CASES.items():
+    for name, (arch, head, emd, hw, n, opts, want) in (EPILOGUE_CASES if epi else CASES).items():
         key = (arch, head, emd, hw, n)
         if key not in nets:
             m = DifEmbedder(arch, head, emd, hw + (3,), max_batch=n).init_synthetic(2024)
@@ -96,7 +128,10 @@ def main():
             nets[key] = m
         dig, kern = run_case(nets[key], torch.from_numpy(pool(hw, n)).cuda(), opts)
         ran = sorted(set(kern.values()))
-        assert ran == sorted(want), (name, ran)
+        if epi:
+            check_layers(nets[key], kern, want)
+        else:
+            assert ran == sorted(want), (name, ran)
         res['cases'][name] = dig
         print('%-22s %s  %d Winograd layers: %s' % (name, dig[:16], len(kern), ', '.join(ran)), flush=True)
         if name == K2_LAYER[0]:
@@ -104,7 +139,7 @@ def main():
             assert K2_LAYER[1] in kern and macs[K2_LAYER[1]] == K2_LAYER[2], (kern, macs.get(K2_LAYER[1]))
     for m in nets.values():
         m.close()
-    with open(args.out, 'w') as fh:
+    with open(out, 'w') as fh:
         json.dump(res, fh, indent=1, sort_keys=True)
         fh.write('\n')
 
