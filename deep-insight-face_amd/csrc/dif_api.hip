@@ -99,7 +99,8 @@ int dif_gallery_destroy(dif_gallery* h) {
   for (void* p : {(void*)g.part_key, (void*)g.part_cnt, (void*)g.part_idx, (void*)g.eps, (void*)g.eps32, (void*)g.best,
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
-                  (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min})
+                  (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min, (void*)g.cluster_parent,
+                  (void*)g.cluster_bad})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -219,7 +220,7 @@ int dif_gallery_remove(dif_gallery* h, const int64_t* rows_dev, int64_t k, int64
 int64_t dif_gallery_size(const dif_gallery* h) { return h ? h->g.n : 0; }
 int64_t dif_gallery_capacity(const dif_gallery* h) { return h ? h->g.cap : 0; }
 
-static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", nullptr};
+static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", "cluster_round", nullptr};
 
 const char* dif_gallery_option_name(int i) {
   int n = 0;
@@ -242,6 +243,12 @@ int dif_gallery_set_option(dif_gallery* h, const char* key, int value) {
     // tiles the seed stage of dif_match_topk evaluates per probe (0: k of them).  Same answers: the sweep completes the list
     if (value < 0) return set_error("dif_gallery_set_option: 'topk_seed' takes 0 or a positive tile count");
     h->g.topk_seed = value;
+    return 0;
+  }
+  if (std::string(key) == "cluster_round") {
+    // probes per round of dif_gallery_cluster (0: a sixteenth of the rows, at least 2048).  Same answers: tests force several rounds
+    if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'cluster_round' takes 0 or a multiple of 128");
+    h->g.cluster_round = value;
     return 0;
   }
   if (std::string(key) == "bd_fill") {
@@ -362,6 +369,21 @@ int dif_match_topk(dif_gallery* h, const float* probes_dev, int n, int metric, i
   if (n == 0) return 0;
   if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match_topk: null pointer");
   return topk_run(&h->g, probes_dev, n, metric, k, idx_out_dev, dist_out_dev, (hipStream_t)stream);
+}
+
+int dif_gallery_cluster(dif_gallery* h, int metric, float tolerance, int64_t first_row, const int64_t* labels_in_dev,
+                        int64_t* labels_out_dev, int64_t* n_clusters_dev, void* stream) {
+  if (!h) return set_error("dif_gallery_cluster: null handle");
+  if (check_metric(metric)) return -1;
+  if (tolerance != tolerance) return set_error("dif_gallery_cluster: the tolerance is NaN");
+  const Gallery& g = h->g;
+  if (g.d % 32 != 0) return set_error("dif_gallery_cluster: embedding size must be a multiple of 32 (got %d)", g.d);
+  if (first_row < 0 || first_row > g.n)
+    return set_error("dif_gallery_cluster: first_row %lld outside [0, %lld]", (long long)first_row, (long long)g.n);
+  if (first_row > 0 && !labels_in_dev) return set_error("dif_gallery_cluster: first_row > 0 needs the earlier labels");
+  if (!n_clusters_dev || (g.n > 0 && !labels_out_dev)) return set_error("dif_gallery_cluster: null pointer");
+  if (g.n >= 0x7fffffffLL) return set_error("dif_gallery_cluster: at most 2^31-1 rows");
+  return cluster_run(&h->g, metric, tolerance, first_row, labels_in_dev, labels_out_dev, n_clusters_dev, (hipStream_t)stream);
 }
 
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,

@@ -71,6 +71,12 @@ struct Gallery {
   float* topk_min = nullptr;
   size_t topk_min_cap = 0;                   // ... in floats
   int topk_seed = 0;                         // "topk_seed": tiles the seed of dif_match_topk evaluates per probe (0: k of them)
+  // dif_gallery_cluster (csrc/match_within.hip) shares the census and its thresholds (stream-ordered calls) and adds the
+  // union-find's parent array, one int per row, and one int that tells cluster_flatten_kernel of a bad labels_in entry
+  int* cluster_parent = nullptr;
+  size_t cluster_parent_cap = 0;             // ... in rows
+  int* cluster_bad = nullptr;
+  int cluster_round = 0;                     // "cluster_round": probes per round of dif_gallery_cluster (0: a sixteenth of the rows, at least 2048)
   // dif_gallery_remove's plan (csrc/match.hip): the record the host reads, then one destination per tail slot
   int64_t* remove_ws = nullptr;
   size_t remove_ws_cap = 0;                  // ... in 8-byte words
@@ -88,6 +94,8 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
 int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
              float* mate_dist_out, hipStream_t st);
 int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
+int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
+                int64_t* n_clusters, hipStream_t st);
 int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D, int metric, float* out,
                  hipStream_t st);
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,

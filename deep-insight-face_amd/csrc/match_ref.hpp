@@ -222,6 +222,7 @@ static int grow(P** p, size_t* cap, size_t need, size_t elem) {
 }
 
 int match_tile_kind(int B);                                  // match.hip: the f32 tile shape for B probes
-int match_plan_parts(const Gallery* g, int B, bool bd);      // match.hip: gallery parts (blocks along the rows) of a tile launch
+// match.hip: gallery parts (blocks along the rows) of a tile launch over the first `rows` rows (-1: all of them)
+int match_plan_parts(const Gallery* g, int B, bool bd, int64_t rows = -1);
 
 }  // namespace dif

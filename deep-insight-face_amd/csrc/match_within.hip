@@ -1,6 +1,7 @@
 // Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), the rank of
 // one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel), and the k nearest rows in order
-// (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel).
+// (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), and the connected components
+// of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find).
 // hipcc-flags: -ffp-contract=off
 // (the resolve stage restates the reference's float32 operations one by one, as match.hip's re-rank does)
 //
@@ -373,8 +374,9 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
   }
 }
 
+// `rows`: the census covers gallery rows [0, rows) only (-1: all of them); its words are laid out as for a gallery of `rows` rows
 template <class T>
-static int launch_census(const Gallery* g, const float* probes, int B, int metric, hipStream_t st) {
+static int launch_census(const Gallery* g, const float* probes, int B, int metric, hipStream_t st, int64_t rows = -1) {
   auto kern = within_census_kernel<T>;
   constexpr int lds = T::LDS_BYTES + T::WGM * T::BN * 4;
   static bool done[64];
@@ -384,10 +386,11 @@ static int launch_census(const Gallery* g, const float* probes, int B, int metri
     DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     done[dev] = true;
   }
-  const int nparts = match_plan_parts(g, B, false);
+  if (rows < 0) rows = g->n;
+  const int nparts = match_plan_parts(g, B, false, rows);
   const int cblocks = (B + T::BN - 1) / T::BN;
   dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
-  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, g->n, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
+  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, rows, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
                      reinterpret_cast<const f32x4*>(g->within_thr), g->within_census, nparts);
   DIF_HIP(hipGetLastError());
   return 0;
@@ -791,6 +794,201 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
                        metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k, dist_out + b0 * k);
     DIF_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Which enrolled rows are the same person (dif_gallery_cluster): the connected components of the graph on the gallery's rows
+// whose edges are the pairs within the tolerance -- exact single-linkage clustering.  With the rows themselves as probes:
+//   for i in range(G):  d = distance(rows[i][None, :], rows[:i + 1], metric);  for j in np.flatnonzero(d <= t): unite(i, j)
+//   label[i] = index_base + min(rows of i's component);  n_clusters = number of components
+// The range search with a self-join driver and a resolve stage that unites instead of listing; nothing of size G x G is kept:
+//   cluster_init_kernel     parent[i] = i, or the earlier label of the incremental form (checked: it is an index into parent)
+//   per round of probes [p0, p1), whole 128-probe blocks:
+//     within_prep_kernel    unchanged, on the gallery's own rows
+//     within_census_kernel  unchanged, over gallery rows [0, p1) only: probe i needs rows j <= i -- the lower triangle, half
+//                           the MFMA work of running every row as a probe of dif_match_within
+//     cluster_resolve_kernel  one block per probe i walks its words in ascending tile order up to i's own tile.  A census
+//                           word holds counts, not row numbers, so every tile with a sure OR a borderline row is evaluated
+//                           row by row with ref_distance, a wave per row j < i (the self hit changes nothing), and on
+//                           dist <= t lane 0 calls cl_unite(i, j).  A probe outside the bound's validity resolves every tile.
+//   cluster_flatten_kernel  label[i] = index_base + cl_find(i), read-only; n_clusters = number of i with cl_find(i) == i, one
+//                           integer atomicAdd per block.
+// The union-find.  parent[x] <= x always; x is a root iff parent[x] == x.  cl_unite(i, j) finds both roots and hooks the
+// LARGER under the smaller by atomicCAS(&parent[hi], hi, lo), retrying from the finds when the CAS fails (hi was hooked by
+// someone else meanwhile).  Facts, each by induction over the successful writes:
+//   (a) no cycles: every write to parent[x] stores a value below x -- the CAS stores lo < hi; path halving stores the parent of
+//       x's parent, which is below x because x was seen not to be a root -- so a walk along parent strictly descends and ends.
+//   (b) a row that has stopped being a root never becomes one again: only the CAS writes to a root, it expects parent[hi] == hi,
+//       and by (a) no later write restores that.  So a path-halving store can never undo a hook, and it only ever stores an
+//       ancestor of x, i.e. a row of x's own component.
+//   (c) the root of a component is its smallest row: true for singletons; a hook puts a root hi, the minimum of its tree, under
+//       lo < hi, whose tree's root is (still, or by now) an even smaller row.
+// Every edge found is united, trees only merge, and when the last round has ended two rows share a root iff a chain of edges
+// joins them.  By (c) that root is the component's minimum, whatever the order the edges arrived in, whichever thread won
+// which CAS: the labels are a function of the edge SET, and the edge set is decided by ref_distance alone.  Hence two calls,
+// or a different round size, give identical arrays.  (The incremental form starts from the labels of rows [0, r): those trees
+// have the components of the earlier call and the same roots, and probes >= r add exactly the edges the full call adds after
+// its probe r - 1.)
+// Memory.  The eight XCDs do not share an L2, so a plain cached load of parent may stay stale for a whole kernel.  A stale
+// value is a former parent, still an ancestor by (b): correctness does not need fresh loads.  Termination of the retry loop
+// does: a CAS fails because parent[hi] changed, and the next cl_find must see that change to make progress.  So cl_find reads
+// through agent-scope atomic loads, the halving store is an agent-scope atomic store, and the CAS is HIP's atomicCAS: plain
+// HIP C++, vector global atomics.  Kernel boundaries order the rounds.
+__device__ __forceinline__ int cl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+template <bool HALVE>
+__device__ __forceinline__ int cl_find(int* __restrict__ parent, int x) {
+  for (;;) {
+    const int p = cl_load(parent + x);
+    if (p == x) return x;
+    const int gp = cl_load(parent + p);
+    if (gp == p) return p;
+    if (HALVE) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = gp;
+  }
+}
+
+__device__ __forceinline__ void cl_unite(int* __restrict__ parent, int a, int b) {
+  for (;;) {
+    a = cl_find<true>(parent, a);
+    b = cl_find<true>(parent, b);
+    if (a == b) return;
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    if (atomicCAS(parent + hi, hi, lo) == hi) return;
+  }
+}
+
+__global__ __launch_bounds__(256) void cluster_init_kernel(int* __restrict__ parent, int64_t G, int64_t first_row,
+                                                           const int64_t* __restrict__ labels_in, int64_t index_base,
+                                                           int* __restrict__ bad, int64_t* __restrict__ n_clusters) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) *n_clusters = 0;
+  if (i >= G) return;
+  int64_t v = i;
+  if (i < first_row) {
+    // (unsigned: one comparison covers both sides and cannot overflow, as in rank_prep_kernel)
+    const uint64_t l = (uint64_t)labels_in[i] - (uint64_t)index_base;
+    if (l <= (uint64_t)i) {
+      v = (int64_t)l;
+    } else {
+      *bad = 1;                                               // (identical stores; the row stays a singleton: parent stays in bounds)
+    }
+  }
+  parent[i] = (int)v;
+}
+
+// One block per probe i = p0 + blockIdx.x; `census` rows are B words apart and cover tiles 0 .. (p0 + B - 1) / 128.  Which
+// tiles are evaluated is block-uniform (the same LDS words); a wave owns the rows it evaluates.
+__global__ __launch_bounds__(64 * WITHIN_NW) void cluster_resolve_kernel(const unsigned short* __restrict__ census, int B,
+                                                                       const f32x4* __restrict__ thr,
+                                                                       const float* __restrict__ gallery, int64_t p0,
+                                                                       int64_t first_row, int D, int metric, float t,
+                                                                       int clamp, const SumPlan plan,
+                                                                       int* __restrict__ parent) {
+  constexpr int NT = 64 * WITHIN_NW;
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned short s_word[NT];
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t i = p0 + p;
+  if (i < first_row) return;                                  // (block-uniform) a row the earlier labels already cover
+  const float* q = gallery + i * D;
+  const int64_t gtiles = i / WITHIN_BM + 1;                   // up to the probe's own tile
+  const bool all = thr[p][3] != 0.f;
+  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
+    s_word[tid] = w;
+    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
+    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
+    for (int j = 0; j < nw; ++j) {
+      if (!(all || s_word[j] != 0)) continue;
+      const int64_t g0 = (t0 + j) * WITHIN_BM;
+      const int rows = i - g0 < WITHIN_BM ? (int)(i - g0) : WITHIN_BM;   // rows j < i only
+      for (int r = wave; r < rows; r += WITHIN_NW) {
+        float d;
+        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+        if (lane == 0 && d <= t) cl_unite(parent, (int)i, (int)(g0 + r));   // NaN: not an edge
+      }
+    }
+    __syncthreads();                                          // s_word is rewritten by the next round
+  }
+}
+
+__global__ __launch_bounds__(256) void cluster_flatten_kernel(int* __restrict__ parent, int64_t G, int64_t index_base,
+                                                              const int* __restrict__ bad, int64_t* __restrict__ labels_out,
+                                                              int64_t* __restrict__ n_clusters) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int root = -1;
+  if (i < G) {
+    root = cl_find<false>(parent, (int)i);
+    labels_out[i] = index_base + root;
+  }
+  const int roots = __syncthreads_count(i < G && root == (int)i);
+  if (threadIdx.x != 0) return;
+  if (*bad) {                                                 // a labels_in entry that no earlier call can have produced
+    if (blockIdx.x == 0) *n_clusters = -1;
+  } else if (roots) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(n_clusters), (unsigned long long)roots);   // integer: order-free
+  }
+}
+
+int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
+                int64_t* n_clusters, hipStream_t st) {
+  const int64_t n = g->n;
+  if (n <= 0) {
+    DIF_HIP(hipMemsetAsync(n_clusters, 0, sizeof(int64_t), st));
+    return 0;
+  }
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  const int clamp = g->clamp_nan ? 1 : 0;
+  const int64_t gtiles = (n + WITHIN_BM - 1) / WITHIN_BM;
+  // probes per round: at most what the census cap allows, as in within_run.  A round's census covers rows [0, its last probe],
+  // so R equal rounds do (R + 1) / 2R of the square's MFMA work: one round would do all of it.  The default is a sixteenth of
+  // the rows (17 / 32 of the square), never below 2048 probes (a launch that fills the chip), or the "cluster_round" option
+  int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
+  if (per < 128) per = 128;
+  int64_t want = g->cluster_round;
+  if (want <= 0) {
+    want = ((n + 15) / 16 + 127) / 128 * 128;
+    if (want < 2048) want = 2048;
+  }
+  if (want < per) per = want;
+  const size_t need_t = (size_t)(per < n ? per : n), need_c = (size_t)gtiles * need_t;
+  if (need_c > g->within_census_cap || need_t > g->within_thr_cap || (size_t)n > g->cluster_parent_cap || !g->cluster_bad) {
+    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
+    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
+    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
+    if (grow(&g->cluster_parent, &g->cluster_parent_cap, (size_t)n, sizeof(int))) return -1;
+    if (!g->cluster_bad) DIF_HIP(hipMalloc(&g->cluster_bad, sizeof(int)));
+  }
+  DIF_HIP(hipMemsetAsync(g->cluster_bad, 0, sizeof(int), st));
+  const unsigned nblk = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(cluster_init_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, n, first_row, labels_in,
+                     g->index_base, g->cluster_bad, n_clusters);
+  DIF_HIP(hipGetLastError());
+  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
+  for (int64_t b0 = first_row / 128 * 128; b0 < n && first_row < n; b0 += per) {
+    const int nb = (int)(n - b0 < per ? n - b0 : per);
+    const float* pr = g->rows + b0 * g->d;
+    hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
+                       g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
+    DIF_HIP(hipGetLastError());
+    const int kind = match_tile_kind(nb);
+    const int64_t limit = b0 + nb;                            // the triangle: no probe of this round looks past its last row
+    int rc;
+    if (kind == 4 && nb <= 32) rc = launch_census<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st, limit);
+    else if (kind == 1 || nb <= 64) rc = launch_census<Tile<2, 1>>(g, pr, nb, metric, st, limit);
+    else rc = launch_census<Tile<2, 2>>(g, pr, nb, metric, st, limit);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cluster_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, nb,
+                       reinterpret_cast<const f32x4*>(g->within_thr), g->rows, b0, first_row, g->d, metric, tolerance, clamp,
+                       plan, g->cluster_parent);
+    DIF_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(cluster_flatten_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, n, g->index_base, g->cluster_bad,
+                     labels_out, n_clusters);
+  DIF_HIP(hipGetLastError());
   return 0;
 }
 

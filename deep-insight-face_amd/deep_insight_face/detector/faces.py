@@ -28,6 +28,17 @@ class FrameFaces(typing.NamedTuple):
     idx: typing.Optional[torch.Tensor] = None    # [M] gallery row, or None without a gallery
     dist: typing.Optional[torch.Tensor] = None   # [M]
 
+    def cluster(self, tolerance, distance_metric: int = 1) -> torch.Tensor:
+        """The distinct people of the batch, without a gallery: labels [M] int64 on the device, ``labels[i]`` = the smallest
+        row of this FrameFaces that a chain of pairs within ``tolerance`` joins to row i (``oneshot.Gallery.cluster`` on the M
+        embeddings; exact single linkage, units of ``evaluation.utility.distance``).  ``M == 0`` gives an empty tensor."""
+        if self.emb is None:
+            raise ValueError('FrameFaces.cluster needs the embeddings (embed_and_match, or a pipeline\'s faces())')
+        if self.emb.shape[0] == 0:
+            return torch.empty((0,), dtype=torch.int64, device=self.emb.device)
+        from .. import oneshot
+        return oneshot.cluster(self.emb, tolerance, distance_metric)[0]
+
 
 def _tensor(x):
     return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))

@@ -127,7 +127,9 @@ class Gallery:
         'clamp_nan': 1 reports distance 0 / 1 where the reference's distance is NaN (a similarity rounded
         beyond +-1); the default 0 reports NaN like the reference.  The arg-min is unaffected.
         'topk_seed': tiles of 128 rows the seed stage of `topk` evaluates per probe -- 0 (default): k of them; same results
-        for every value (include/dif.h)."""
+        for every value (include/dif.h).
+        'cluster_round': probes per round of `cluster`, a multiple of 128 -- 0 (default): a sixteenth of the rows, at least 2048; same
+        results for every value (include/dif.h)."""
         N.check(N.lib.dif_gallery_set_option(self._h, key.encode(), int(value)), ValueError)
 
     def stat(self, key):
@@ -355,6 +357,68 @@ class Gallery:
             idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
         return idx, dist
 
+    def cluster_into(self, tolerance, distance_metric, labels, n_clusters, first_row=0, prev=None):
+        """Allocation-free form of `cluster`: results written into the caller's CUDA tensors labels [G] int64 and n_clusters
+        (one int64 element, 0-d or [1]); `prev` [first_row] int64 CUDA holds the earlier labels when first_row > 0 (it may
+        be `labels` itself or a slice of it)."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        tolerance = float(tolerance)
+        if tolerance != tolerance:
+            raise ValueError('cluster: the tolerance is NaN')
+        G, first_row = len(self), int(first_row)
+        if first_row < 0 or first_row > G:
+            raise ValueError('first_row %d outside [0, %d]' % (first_row, G))
+        if first_row > 0 and prev is None:
+            raise ValueError('cluster: first_row > 0 needs the labels of the earlier call')
+        for name, t in (('labels', labels), ('n_clusters', n_clusters), ('prev', prev)):
+            if t is None and name == 'prev':
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('cluster_into: %s must be a contiguous %s tensor on %s' % (name, torch.int64, self._dev))
+        if tuple(labels.shape) != (G,):
+            raise ValueError('cluster_into: labels must have shape [%d], got %s' % (G, tuple(labels.shape)))
+        if n_clusters.numel() != 1:
+            raise ValueError('cluster_into: n_clusters must hold one element, got %s' % (tuple(n_clusters.shape),))
+        if first_row > 0 and (prev.dim() != 1 or prev.shape[0] < first_row):
+            raise ValueError('cluster_into: prev must hold the labels of rows [0, %d), got %s' % (first_row, tuple(prev.shape)))
+        N.check(N.lib.dif_gallery_cluster(self._h, distance_metric, tolerance, first_row,
+                                          N.ptr(prev) if first_row > 0 else None, N.ptr(labels) if G else None,
+                                          N.ptr(n_clusters), N.stream_ptr()), ValueError)
+
+    def cluster(self, tolerance, distance_metric=1, first_row=0, labels=None):
+        """Which enrolled rows are the same person: exact single-linkage clustering at `tolerance`, i.e. the connected
+        components of the graph whose edges are the pairs of rows within it.  -> (labels [G] int64, n_clusters 0-d int64),
+        both on the device; nothing of size G x G is kept and nothing is read back.
+
+        Every row i is a probe against rows[:i + 1]: ``d = evaluation.utility.distance(rows[i][None, :], rows[:i + 1], metric)``
+        and every ``j`` with ``d[j] <= tolerance`` (inclusive; NaN is no edge) joins i's component.  labels[i] = index_base +
+        the smallest row number of i's component -- canonical: two calls give identical tensors -- and n_clusters the number
+        of components.  A row whose distances are all NaN or above the tolerance is a component of its own.  The tolerance
+        has `within`'s units and edge cases: metric 0 is the SQUARED L2 distance; tolerance < 0 gives G singletons; under metric
+        1 a tolerance >= 1 joins every pair whose distance is not NaN.  'clamp_nan' is honoured as `within` honours it: with the
+        default 0 two identical rows whose similarity rounds above 1 have a NaN distance under metric 1 and are NOT joined, so
+        de-duplicating exact copies under metric 1 wants set_option('clamp_nan', 1).
+
+        Incremental form (enrolment): ``cluster(t, metric, first_row=r, labels=prev)`` with ``prev`` the labels of a call over
+        rows [0, r) with the same tolerance and metric (a tensor or an array of at least r entries) probes rows [r, G) only and
+        returns what the full call returns, at O((G - r) * G) cost.  A `prev` entry that no such call can have produced (outside
+        [index_base, index_base + its own row]) gives n_clusters == -1.  After `remove` row numbers have moved and earlier
+        labels are void: run the full call."""
+        G, first_row = len(self), int(first_row)
+        if first_row < 0 or first_row > G:
+            raise ValueError('first_row %d outside [0, %d]' % (first_row, G))
+        prev = None
+        if first_row > 0:
+            if labels is None:
+                raise ValueError('cluster: first_row > 0 needs the labels of the earlier call')
+            prev = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels, dtype=np.int64)))
+            prev = prev.to(device=self._dev, dtype=torch.int64).contiguous()
+        out = torch.empty((G,), dtype=torch.int64, device=self._dev)
+        n = torch.empty((), dtype=torch.int64, device=self._dev)
+        self.cluster_into(tolerance, distance_metric, out, n, first_row, prev)
+        return out, n
+
     def close(self):
         if self._h:
             N.lib.dif_gallery_destroy(self._h)
@@ -406,6 +470,19 @@ def topk(probes, gallery, k, distance_metric=1):
         return g.topk(probes, k, distance_metric)
     finally:
         if g is not gallery:
+            g.close()
+
+
+def cluster(embeddings, tolerance, distance_metric=1):
+    """One-call form of Gallery.cluster on a temporary gallery of `embeddings` [M, d]: which rows are the same person
+    -> (labels[M] int64, n_clusters 0-d int64), on the device."""
+    g = embeddings if isinstance(embeddings, Gallery) else Gallery(embeddings)
+    try:
+        labels, n = g.cluster(tolerance, distance_metric)
+        torch.cuda.current_stream().synchronize()   # the temporary gallery is freed below: the work must have ended
+        return labels, n
+    finally:
+        if g is not embeddings:
             g.close()
 
 

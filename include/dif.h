@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed" (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round" (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -272,6 +272,10 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * "topk_seed": 0 (default) the seed stage of dif_match_topk evaluates the k gallery tiles with the smallest search keys
  * per probe; n > 0 makes it n tiles (1: a loose first tolerance, the sweep stage does the work).  Same answers for every
  * value (tests, A/B).
+ * "cluster_round": 0 (default) dif_gallery_cluster takes a sixteenth of the rows as the probes of one round, in whole blocks
+ * of 128 and at least 2048 (a round's MFMA pass stops at its last probe's row: sixteen rounds do 17 / 32 of the square, one
+ * round all of it); n > 0, a multiple of 128, makes it n probes.  Either way at most what the census workspace allows (2^27
+ * words / the number of 128-row tiles).  Same answers for every value (tests: several rounds on a small gallery).
  * Every key the library accepts is listed here (dif_gallery_option_name; tests/test_cabi_symbols.py). */
 int dif_gallery_set_option(dif_gallery* g, const char* key, int value);
 /* read-outs (no reference counterpart; for capacity planning and tests).  "split_copy": 1 when the filter's bf16 copy
@@ -362,6 +366,36 @@ int dif_match_rank(dif_gallery* g, const float* probes_dev, int n, int metric, c
 #define DIF_TOPK_MAX 128
 int dif_match_topk(dif_gallery* g, const float* probes_dev, int n, int metric, int k, int64_t* idx_out_dev /* [n][k] */,
                    float* dist_out_dev /* [n][k] */, void* stream);
+/* which enrolled rows are the same person: exact single-linkage clustering of the gallery's own rows at a tolerance, i.e. the
+ * connected components of the graph whose edges are the pairs of rows within `tolerance`.  With n = dif_gallery_size:
+ *     for i in range(n):                                            every enrolled row is a probe
+ *         d = utility.distance(rows[i][None, :], rows[:i + 1], metric)      the reference's float32 values, rows 0..i only
+ *         for j in np.flatnonzero(d <= tolerance): unite(i, j)      inclusive; NaN <= t is False
+ *     labels_out_dev[i] = index_base + the smallest row number of i's component;  n_clusters_dev[0] = number of components
+ *   Only the lower triangle is evaluated (row i as the probe, row j <= i as the enrolled row): the reference's arithmetic is
+ *   symmetric in its two arguments, and stated this way the result does not depend on it.  A label is the smallest row of its
+ *   component, so the result is canonical: it depends neither on thread order nor on the order in which edges are found, and
+ *   two calls give identical arrays.  A row whose distance to every other row is NaN or above the tolerance is a component of
+ *   its own (label = its own row): a zero-norm or non-finite row under metric 1, for instance.
+ * Units, arithmetic and NaN rule: dif_match_within's, under the handle's "clamp_nan".  tolerance < 0 gives n singletons; under
+ *   metric 1 a tolerance >= 1 joins every pair whose distance is not NaN.  With "clamp_nan" 0 two IDENTICAL rows whose
+ *   similarity rounds above 1 are NOT joined under metric 1 (their distance is NaN): de-duplicating exact copies under
+ *   metric 1 wants "clamp_nan" 1.  Metric 1 pairs within ~2e-6 of the tolerance may differ from NumPy's (the arccos).
+ * Incremental form (enrolment): first_row = r > 0 and labels_in_dev = the labels_out of a call over rows [0, r) with the same
+ *   tolerance, metric and index_base.  The union-find starts from those labels, only rows [r, n) are probes (each against
+ *   rows[:i + 1]) and the result equals the full call's at O((n - r) n) cost.  first_row = n copies the labels.  After
+ *   dif_gallery_remove row numbers have moved and earlier labels are void: run the full call.  labels_in_dev may alias
+ *   labels_out_dev.  A labels_in entry outside [index_base, index_base + its own row] cannot come from such a call; it is
+ *   detected on the device, without a host read: n_clusters_dev[0] = -1 then, and labels_out holds no meaning.
+ * An empty gallery writes n_clusters = 0.  A metric other than 0 / 1, a NaN tolerance, an embedding size that is not a
+ *   multiple of 32, first_row outside [0, n], labels_in_dev NULL with first_row > 0, or a NULL handle or output fails.
+ * Costs the lower triangle of dif_match_within's f32 MFMA pass (half the work of running every row as its probe) plus the
+ *   reference arithmetic on the 128-row tiles that hold a row within, or too close to, the tolerance; nothing of size n x n
+ *   is kept; no host synchronisation in steady state.  Workspace: dif_match_within's (shared; calls on one stream are
+ *   ordered) plus 4 bytes per row.  Probes go in rounds (gallery option "cluster_round"). */
+int dif_gallery_cluster(dif_gallery* g, int metric, float tolerance, int64_t first_row,
+                        const int64_t* labels_in_dev /* [first_row], or NULL when first_row == 0 */,
+                        int64_t* labels_out_dev /* [n] */, int64_t* n_clusters_dev /* [1] */, void* stream);
 /* merge R per-shard results laid out [R][n] (after an all-gather): lowest key, then
  * lowest global index -- equals np.argmin over the concatenated gallery */
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,
