@@ -100,7 +100,7 @@ int dif_gallery_destroy(dif_gallery* h) {
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
                   (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min, (void*)g.cluster_parent,
-                  (void*)g.cluster_bad})
+                  (void*)g.cluster_bad, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -220,7 +220,7 @@ int dif_gallery_remove(dif_gallery* h, const int64_t* rows_dev, int64_t k, int64
 int64_t dif_gallery_size(const dif_gallery* h) { return h ? h->g.n : 0; }
 int64_t dif_gallery_capacity(const dif_gallery* h) { return h ? h->g.cap : 0; }
 
-static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", "cluster_round", nullptr};
+static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", "cluster_round", "roc_round", "roc_blocks", nullptr};
 
 const char* dif_gallery_option_name(int i) {
   int n = 0;
@@ -249,6 +249,18 @@ int dif_gallery_set_option(dif_gallery* h, const char* key, int value) {
     // probes per round of dif_gallery_cluster (0: a sixteenth of the rows, at least 2048).  Same answers: tests force several rounds
     if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'cluster_round' takes 0 or a multiple of 128");
     h->g.cluster_round = value;
+    return 0;
+  }
+  if (std::string(key) == "roc_round") {
+    // probes per round of dif_match_roc (0: what the mask workspace's cap allows).  Same answers: tests force several rounds
+    if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'roc_round' takes 0 or a multiple of 128");
+    h->g.roc_round = value;
+    return 0;
+  }
+  if (std::string(key) == "roc_blocks") {
+    // most blocks the resolve stage of dif_match_roc launches (0: 2048).  Same answers: tests make a block take several trips
+    if (value < 0 || value > 65536) return set_error("dif_gallery_set_option: 'roc_blocks' takes 0 .. 65536");
+    h->g.roc_blocks = value;
     return 0;
   }
   if (std::string(key) == "bd_fill") {
@@ -322,6 +334,15 @@ int dif_gallery_get_stat(dif_gallery* h, const char* key, int64_t* out, void* st
     *out = v;
     return 0;
   }
+  if (k == "roc_resolved") {                   // pairs the last dif_match_roc evaluated one by one (too close to a threshold to call)
+    unsigned long long v = 0;
+    if (g.roc_bins) {
+      DIF_HIP(hipMemcpyAsync(&v, g.roc_bins + 2 * (DIF_ROC_MAX_THRESHOLDS + 2), sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      DIF_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
+    *out = (int64_t)v;
+    return 0;
+  }
   return set_error("dif_gallery_get_stat: unknown key '%s'", key);
 }
 
@@ -384,6 +405,32 @@ int dif_gallery_cluster(dif_gallery* h, int metric, float tolerance, int64_t fir
   if (!n_clusters_dev || (g.n > 0 && !labels_out_dev)) return set_error("dif_gallery_cluster: null pointer");
   if (g.n >= 0x7fffffffLL) return set_error("dif_gallery_cluster: at most 2^31-1 rows");
   return cluster_run(&h->g, metric, tolerance, first_row, labels_in_dev, labels_out_dev, n_clusters_dev, (hipStream_t)stream);
+}
+
+int dif_match_roc(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* probe_labels_dev,
+                  const int64_t* row_labels_dev, const int64_t* first_row_dev, const float* thresholds_dev, int n_thresholds,
+                  int64_t* accept_out_dev, int64_t* totals_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_roc: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_roc: negative probe count");
+  if (n_thresholds < 1 || n_thresholds > DIF_ROC_MAX_THRESHOLDS)
+    return set_error("dif_match_roc: n_thresholds %d outside [1, %d]", n_thresholds, DIF_ROC_MAX_THRESHOLDS);
+  if (!thresholds_dev || !accept_out_dev || !totals_out_dev) return set_error("dif_match_roc: null pointer");
+  const Gallery& g = h->g;
+  if (n > 0 && (!probes_dev || !probe_labels_dev)) return set_error("dif_match_roc: null probes or probe labels");
+  if (n > 0 && g.n > 0 && !row_labels_dev) return set_error("dif_match_roc: null row labels");
+  // the one host read of the call, of an INPUT: the thresholds (at most 4 KB) are checked before anything is launched
+  float thr[DIF_ROC_MAX_THRESHOLDS];
+  hipStream_t st = (hipStream_t)stream;
+  DIF_HIP(hipMemcpyAsync(thr, thresholds_dev, (size_t)n_thresholds * sizeof(float), hipMemcpyDeviceToHost, st));
+  DIF_HIP(hipStreamSynchronize(st));
+  for (int j = 0; j < n_thresholds; ++j) {
+    if (thr[j] != thr[j]) return set_error("dif_match_roc: threshold %d is NaN", j);
+    if (j > 0 && thr[j] < thr[j - 1])
+      return set_error("dif_match_roc: the thresholds must be non-decreasing (%d: %g after %g)", j, (double)thr[j], (double)thr[j - 1]);
+  }
+  return roc_run(&h->g, probes_dev, n, metric, probe_labels_dev, row_labels_dev, first_row_dev, thresholds_dev, n_thresholds,
+                 accept_out_dev, totals_out_dev, st);
 }
 
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,

@@ -77,6 +77,15 @@ struct Gallery {
   size_t cluster_parent_cap = 0;             // ... in rows
   int* cluster_bad = nullptr;
   int cluster_round = 0;                     // "cluster_round": probes per round of dif_gallery_cluster (0: a sixteenth of the rows, at least 2048)
+  // dif_match_roc's workspace (csrc/match_roc.hip), its own; every buffer grows against a capacity of its own
+  unsigned* roc_mask = nullptr;              // [gallery tile][probe][4]: the 128-bit mask of the borderline rows
+  size_t roc_mask_cap = 0;                   // ... in masks of 16 bytes
+  float* roc_thr = nullptr;                  // per probe: {scale of the key, half width of the band, |key| >= [2]: borderline, -}
+  size_t roc_thr_cap = 0;                    // ... in probes
+  float* roc_tab = nullptr;                  // the call's two search tables, 2048 floats each (allocated once)
+  unsigned long long* roc_bins = nullptr;    // the call's bins, [DIF_ROC_MAX_THRESHOLDS + 2][2] (allocated once)
+  int roc_blocks = 0;                        // "roc_blocks": most blocks of roc_resolve_kernel (0: 2048)
+  int roc_round = 0;                         // "roc_round": probes per round of dif_match_roc (0: what the mask workspace's cap allows)
   // dif_gallery_remove's plan (csrc/match.hip): the record the host reads, then one destination per tail slot
   int64_t* remove_ws = nullptr;
   size_t remove_ws_cap = 0;                  // ... in 8-byte words
@@ -96,6 +105,8 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
 int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
 int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
                 int64_t* n_clusters, hipStream_t st);
+int roc_run(Gallery* g, const float* probes, int B, int metric, const int64_t* probe_labels, const int64_t* row_labels,
+            const int64_t* first_row, const float* thresholds, int nT, int64_t* accept_out, int64_t* totals_out, hipStream_t st);
 int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D, int metric, float* out,
                  hipStream_t st);
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,

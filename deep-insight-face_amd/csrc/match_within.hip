@@ -50,49 +50,11 @@
 #include "gemm_core.hpp"
 #include "dif_internal.hpp"
 #include "match_ref.hpp"
+#include "match_band.hpp"
 
 namespace dif {
 
-constexpr int WITHIN_BM = 128;          // gallery rows per census word: every f32 tile shape of the match has 128-row tiles
-constexpr int WITHIN_NW = 8;            // waves of a resolve block
 constexpr size_t WITHIN_CENSUS_MAX = (size_t)128 << 20;   // census words per launch (256 MB); more probes go in several rounds
-
-// The band of one probe at tolerance t (the formulas of the header comment); s = |q|^2 summed as an fma chain over 64 lanes.
-struct Band {
-  float T, E, H;
-  bool odd;                                                   // outside the bound's validity: every tile is resolved
-};
-__device__ __forceinline__ Band within_band(int metric, float t, float s, int D, float cdot,
-                                            const unsigned* __restrict__ sqmax_bits) {
-  const float u = U24, qn = sqrtf(s) * 1.0001f, inf = __builtin_inff();
-  Band b;
-  if (metric == 1) {
-    b.odd = !(s >= NORM_LO && s <= NORM_HI);
-    b.E = key_err1_rel(cdot) * qn + (96.f + (float)(D / 64)) * u * qn;
-    b.T = t >= 1.f ? inf : (t < 0.f ? -inf : (float)(-sqrt((double)s) * cos(3.14159265358979323846 * (double)t)));
-    b.H = sqrtf(s) * (1.f - (2e-4f + 1.01f * (cdot + 136.f * u)));
-  } else {
-    b.odd = !(s <= NORM_HI);
-    const float gmax = sqrtf(__builtin_bit_cast(float, *sqmax_bits)) * 1.0001f;
-    b.E = key_err0(cdot, qn, gmax) + 32.f * u * (qn + gmax) * (qn + gmax) +
-          ((float)(D / 64) + 8.f) * u * (qn * qn + gmax * gmax) + u * (fabsf(t) + qn * qn);
-    b.T = t - s;
-    b.H = inf;
-  }
-  return b;
-}
-
-// |q|^2 of one probe row by one wave: an fma chain per lane, then the butterfly (every lane returns the sum)
-__device__ __forceinline__ float probe_sq(const float* __restrict__ q, int D, int lane) {
-  float s = 0.f;
-  for (int k = lane; k < D; k += 64) {
-    const float x = q[k];
-    s = fmaf(x, x, s);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  return s;
-}
 
 __global__ __launch_bounds__(256) void within_prep_kernel(const float* __restrict__ probes, int B, int D, int metric, float t,
                                                           float cdot, const unsigned* __restrict__ sqmax_bits,
@@ -426,11 +388,7 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
     hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
                        g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
     DIF_HIP(hipGetLastError());
-    const int kind = match_tile_kind(nb);
-    int rc;
-    if (kind == 4 && nb <= 32) rc = launch_census<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st);
-    else if (kind == 1 || nb <= 64) rc = launch_census<Tile<2, 1>>(g, pr, nb, metric, st);
-    else rc = launch_census<Tile<2, 2>>(g, pr, nb, metric, st);
+    const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st); });
     if (rc) return rc;
     hipLaunchKernelGGL(within_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
                        reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
@@ -468,11 +426,7 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
                        g->rank_mate, mate_dist_out ? mate_dist_out + b0 : nullptr);
     DIF_HIP(hipGetLastError());
     if (gtiles > 0) {
-      const int kind = match_tile_kind(nb);
-      int rc;
-      if (kind == 4 && nb <= 32) rc = launch_census<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st);
-      else if (kind == 1 || nb <= 64) rc = launch_census<Tile<2, 1>>(g, pr, nb, metric, st);
-      else rc = launch_census<Tile<2, 2>>(g, pr, nb, metric, st);
+      const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st); });
       if (rc) return rc;
     }
     hipLaunchKernelGGL(rank_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
@@ -783,11 +737,7 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
     const int nb = (int)(B - b0 < per ? B - b0 : per);
     const float* pr = probes + b0 * g->d;
     if (gtiles > 0) {
-      const int kind = match_tile_kind(nb);
-      int rc;
-      if (kind == 4 && nb <= 32) rc = launch_tilemin<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st);
-      else if (kind == 1 || nb <= 64) rc = launch_tilemin<Tile<2, 1>>(g, pr, nb, metric, st);
-      else rc = launch_tilemin<Tile<2, 2>>(g, pr, nb, metric, st);
+      const int rc = with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
       if (rc) return rc;
     }
     hipLaunchKernelGGL(topk_select_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows, g->d,
@@ -974,12 +924,8 @@ int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, cons
     hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
                        g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
     DIF_HIP(hipGetLastError());
-    const int kind = match_tile_kind(nb);
     const int64_t limit = b0 + nb;                            // the triangle: no probe of this round looks past its last row
-    int rc;
-    if (kind == 4 && nb <= 32) rc = launch_census<Tile<1, 1, 4, 1>>(g, pr, nb, metric, st, limit);
-    else if (kind == 1 || nb <= 64) rc = launch_census<Tile<2, 1>>(g, pr, nb, metric, st, limit);
-    else rc = launch_census<Tile<2, 2>>(g, pr, nb, metric, st, limit);
+    const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st, limit); });
     if (rc) return rc;
     hipLaunchKernelGGL(cluster_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, nb,
                        reinterpret_cast<const f32x4*>(g->within_thr), g->rows, b0, first_row, g->d, metric, tolerance, clamp,

@@ -17,6 +17,18 @@ from . import _native as N
 
 MAX_HITS = 8192   # DIF_WITHIN_MAX_HITS (include/dif.h): the longest list `within` returns per probe
 TOPK_MAX = 128    # DIF_TOPK_MAX: the longest list `topk` returns per probe
+ROC_MAX_THRESHOLDS = 1024   # DIF_ROC_MAX_THRESHOLDS: the most thresholds one `roc` call takes
+
+
+def up32(thresholds):
+    """float64 thresholds -> the float32 thresholds that compare the same way with a float32 distance: for a float32 d,
+    ``d < t64`` (NumPy compares in double) holds exactly when ``d < up32(t64)``, the smallest float32 >= t64.  Rounding to
+    nearest would move a threshold below a distance that equals the rounded value.  NaN stays NaN."""
+    t64 = np.asarray(thresholds, dtype=np.float64)
+    with np.errstate(over='ignore'):
+        t32 = t64.astype(np.float32)
+    low = t32.astype(np.float64) < t64
+    return np.where(low, np.nextafter(t32, np.float32(np.inf)), t32).astype(np.float32)
 
 
 class Gallery:
@@ -129,7 +141,10 @@ class Gallery:
         'topk_seed': tiles of 128 rows the seed stage of `topk` evaluates per probe -- 0 (default): k of them; same results
         for every value (include/dif.h).
         'cluster_round': probes per round of `cluster`, a multiple of 128 -- 0 (default): a sixteenth of the rows, at least 2048; same
-        results for every value (include/dif.h)."""
+        results for every value (include/dif.h).
+        'roc_round': probes per round of `roc`, a multiple of 128 -- 0 (default): what its workspace allows; same results for
+        every value (include/dif.h).
+        'roc_blocks': most blocks of `roc`'s resolve stage -- 0 (default): 2048; same results for every value (include/dif.h)."""
         N.check(N.lib.dif_gallery_set_option(self._h, key.encode(), int(value)), ValueError)
 
     def stat(self, key):
@@ -138,7 +153,8 @@ class Gallery:
         'filter_terms': bf16 terms per operand the next match's filter runs on (0: float32 rows);
         'frag_copy': 1 when the one-term copy is held in MFMA-fragment order (option 'frag': match_g1_kernel serves);
         'row_bytes': device bytes per row;
-        'exact_probes': probes the last match sent to the exact whole-gallery search (synchronises)."""
+        'exact_probes': probes the last match sent to the exact whole-gallery search (synchronises);
+        'roc_resolved': pairs the last `roc` evaluated one by one, too close to a threshold to call (synchronises)."""
         v = ctypes.c_int64(0)
         N.check(N.lib.dif_gallery_get_stat(self._h, key.encode(), ctypes.byref(v), N.stream_ptr()), ValueError)
         return int(v.value)
@@ -418,6 +434,88 @@ class Gallery:
         n = torch.empty((), dtype=torch.int64, device=self._dev)
         self.cluster_into(tolerance, distance_metric, out, n, first_row, prev)
         return out, n
+
+    def roc_into(self, probes, probe_labels, row_labels, first_row, thresholds, distance_metric, accept, totals):
+        """Allocation-free form of `roc`, the library's own terms: `probes` [B, d] float32, `probe_labels` [B] int64,
+        `row_labels` [len(self)] int64, `first_row` [B] int64 or None, `thresholds` [T] float32 NON-DECREASING -- all CUDA;
+        results written into the caller's CUDA tensors accept [T, 2] int64 and totals [4] int64.  The thresholds are checked
+        by the library (one 4 KB read; ValueError with its message); the counts are not read back."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
+            raise ValueError('probes must be a [B, %d] tensor, got %s' % (
+                self.emd_size, tuple(probes.shape) if hasattr(probes, 'shape') else type(probes).__name__))
+        B, G = probes.shape[0], len(self)
+        for name, t, dt, shape in (('probes', probes, torch.float32, None), ('probe_labels', probe_labels, torch.int64, (B,)),
+                                   ('row_labels', row_labels, torch.int64, (G,)), ('first_row', first_row, torch.int64, (B,)),
+                                   ('thresholds', thresholds, torch.float32, None), ('accept', accept, torch.int64, None),
+                                   ('totals', totals, torch.int64, (4,))):
+            if t is None and name == 'first_row':
+                continue
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('roc_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError('roc_into: %s must have shape %s, got %s' % (name, list(shape), tuple(t.shape)))
+        if thresholds.dim() != 1:
+            raise ValueError('roc_into: thresholds must have shape [T], got %s' % (tuple(thresholds.shape),))
+        T = thresholds.shape[0]
+        if tuple(accept.shape) != (T, 2):
+            raise ValueError('roc_into: accept must have shape [%d, 2], got %s' % (T, tuple(accept.shape)))
+        N.check(N.lib.dif_match_roc(self._h, N.ptr(probes) if B else None, B, distance_metric,
+                                    N.ptr(probe_labels) if B else None, N.ptr(row_labels) if G else None,
+                                    N.ptr(first_row) if first_row is not None and B else None,
+                                    N.ptr(thresholds) if T else None, T, N.ptr(accept) if T else None, N.ptr(totals),
+                                    N.stream_ptr()), ValueError)
+
+    def roc(self, probes, probe_labels, row_labels, thresholds, distance_metric=1, first_row=None):
+        """All-pairs verification counts: how many genuine and impostor (probe, enrolled row) pairs lie below each threshold,
+        exact, in one pass over the gallery whatever the number of thresholds.
+        -> (accept [T, 2] int64, totals [4] int64), both on the device and in the caller's threshold order.
+
+        With ``dist = evaluation.utility.distance(q[:, None], gallery[None, :], metric)`` (never materialised),
+        ``use = (probe_labels[:, None] >= 0) & (row_labels[None, :] >= 0) & (index_base + arange(G)[None, :] >= first_row[:, None])``
+        and ``same = probe_labels[:, None] == row_labels[None, :]``:
+        accept[j] = [sum(use & same & (dist < thresholds[j])), sum(use & ~same & (dist < thresholds[j]))] -- strict, as
+        calculate_val_far's np.less; NaN < t is False -- and totals = [sum(use & same), sum(use & ~same), and of each the pairs
+        whose dist is NaN].  Labels are integers (any integer dtype; a negative one takes the probe or row out of every pair),
+        `row_labels` in the gallery's row order; the gallery stores none.  `first_row` [B] (default: zeros) is a global row
+        index: a labelled set against itself passes its own row + 1 and gets every unordered pair once
+        (evaluation.verification.all_pairs_counts).  `thresholds`: up to 1024 numbers in any order, float64 welcome -- they are
+        converted with `up32`, the rule under which a float32 distance compares with them as NumPy compares it in double, and
+        sorted for the library; duplicates, values <= 0 or > 1 and +-inf are fine, a NaN raises ValueError.  Distances, units
+        and the NaN rule ('clamp_nan') are `within`'s; an empty gallery gives zeros."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        p, _ = N.to_device_f32(probes, self._dev)
+        if p.dim() == 1:
+            p = p[None, :]
+        if p.dim() != 2 or p.shape[1] != self.emd_size:
+            raise ValueError('probes must be [B, %d], got %s' % (self.emd_size, tuple(p.shape)))
+        B, G = p.shape[0], len(self)
+
+        def ints(x, name, n):
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+            if t.numel() == 0:
+                t = t.to(torch.int64)
+            if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+                raise ValueError('%s must be integers, got %s' % (name, t.dtype))
+            if tuple(t.shape) != (n,):
+                raise ValueError('%s must have shape [%d], got %s' % (name, n, tuple(t.shape)))
+            return t.to(device=self._dev, dtype=torch.int64).contiguous()
+
+        pl, rl = ints(probe_labels, 'probe_labels', B), ints(row_labels, 'row_labels', G)
+        fr = None if first_row is None else ints(first_row, 'first_row', B)
+        th = thresholds.detach().cpu().numpy() if torch.is_tensor(thresholds) else np.asarray(thresholds)
+        t32 = up32(th.astype(np.float64).reshape(-1))
+        order = np.argsort(t32, kind='stable')                  # (a NaN sorts last and the library names it)
+        ts = torch.from_numpy(np.ascontiguousarray(t32[order])).to(self._dev)
+        T = ts.shape[0]
+        acc = torch.empty((T, 2), dtype=torch.int64, device=self._dev)
+        totals = torch.empty((4,), dtype=torch.int64, device=self._dev)
+        self.roc_into(p, pl, rl, fr, ts, distance_metric, acc, totals)
+        accept = torch.empty_like(acc)
+        accept[torch.from_numpy(order).to(self._dev)] = acc     # back to the caller's order, on the device
+        return accept, totals
 
     def close(self):
         if self._h:

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round" (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round"; + dif_match_roc, gallery option "roc_round" (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -276,13 +276,19 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * of 128 and at least 2048 (a round's MFMA pass stops at its last probe's row: sixteen rounds do 17 / 32 of the square, one
  * round all of it); n > 0, a multiple of 128, makes it n probes.  Either way at most what the census workspace allows (2^27
  * words / the number of 128-row tiles).  Same answers for every value (tests: several rounds on a small gallery).
+ * "roc_round": 0 (default) dif_match_roc takes as many probes per round as its mask workspace allows (2^24 masks of 16 bytes /
+ * the number of 128-row tiles, in whole blocks of 128, at least 128); n > 0, a multiple of 128, makes it n probes when that is
+ * fewer.  Same answers for every value (tests: several rounds at a small shape).
+ * "roc_blocks": 0 (default) the resolve stage of dif_match_roc launches at most 2048 blocks, each taking 512 masks per trip;
+ * n in 1 .. 65536 makes it at most n.  Same answers for every value (tests: one block that takes many trips at a small shape).
  * Every key the library accepts is listed here (dif_gallery_option_name; tests/test_cabi_symbols.py). */
 int dif_gallery_set_option(dif_gallery* g, const char* key, int value);
 /* read-outs (no reference counterpart; for capacity planning and tests).  "split_copy": 1 when the filter's bf16 copy
  * of the current rows exists; "filter_terms": bf16 terms per operand the next dif_match's filter runs on (1 or 2; 0 = the f32 rows);
  * "frag_copy": 1 when that copy is held in MFMA-fragment order (gallery option "frag");
  * "row_bytes": device bytes held per gallery row; "exact_probes": how many probes the
- * last dif_match on `stream` sent to the exact whole-gallery search (synchronises the stream). */
+ * last dif_match on `stream` sent to the exact whole-gallery search (synchronises the stream); "roc_resolved": how many pairs the
+ * last dif_match_roc on `stream` evaluated one by one, being too close to a threshold to call (synchronises the stream). */
 int dif_gallery_get_stat(dif_gallery* g, const char* key, int64_t* out, void* stream);
 /* top-1 search of n probes [n][d]: idx_out_dev[n] = np.argmin over the reference's float32 distances
  * (int64 global index; first minimum; a row whose reference distance is NaN ranks first, as in
@@ -396,6 +402,43 @@ int dif_match_topk(dif_gallery* g, const float* probes_dev, int n, int metric, i
 int dif_gallery_cluster(dif_gallery* g, int metric, float tolerance, int64_t first_row,
                         const int64_t* labels_in_dev /* [first_row], or NULL when first_row == 0 */,
                         int64_t* labels_out_dev /* [n] */, int64_t* n_clusters_dev /* [1] */, void* stream);
+/* all-pairs verification counts at every threshold, exact: how many genuine (equal labels) and impostor (different labels) pairs
+ * of (probe, enrolled row) have a distance below each of T thresholds -- the numerators and denominators of TAR / VAL and FAR
+ * over EVERY pair (deep_insight_face/evaluation/verification.py), where utility.calculate_val_far sees a list of pairs.
+ * Per call, with B = n probes and G = dif_gallery_size rows:
+ *     dist  = utility.distance(q[:, None], gallery[None, :], metric)    the reference's float32 values, B x G, never materialised
+ *     use   = (probe_labels[:, None] >= 0) & (row_labels[None, :] >= 0) & (arange(G)[None, :] + index_base >= first_row[:, None])
+ *     same  = probe_labels[:, None] == row_labels[None, :]
+ *     accept_out_dev[j][0] = sum(use &  same & (dist < thresholds[j]))  np.less, as calculate_val_far: STRICT; NaN < t is False
+ *     accept_out_dev[j][1] = sum(use & ~same & (dist < thresholds[j]))
+ *     totals_out_dev = [sum(use & same), sum(use & ~same), sum(use & same & isnan(dist)), sum(use & ~same & isnan(dist))]
+ * Inputs: probe_labels_dev int64 [n]; row_labels_dev int64 [G] in LOCAL row order -- the caller owns the labels as it owns the
+ *   name table dif_gallery_remove reports moves for; the handle stores none.  A negative label takes that probe or row out of
+ *   every pair.  first_row_dev int64 [n], or NULL for all zeros, is compared with the GLOBAL row index (index_base included): a
+ *   labelled set evaluated against itself passes own row + 1 and gets every unordered pair once and no row with itself.
+ * Outputs are int64, on the device, and are not read back by the call: accept [n_thresholds][2], totals [4].
+ * Thresholds: float32 [n_thresholds] on the device, NON-DECREASING, 1 <= n_thresholds <= DIF_ROC_MAX_THRESHOLDS.  Duplicates,
+ *   values <= 0 (accept nothing; so does -inf), values > 1 and +inf (accepts every distance that is neither NaN nor +inf itself) are allowed.  A NaN
+ *   threshold, a decreasing pair or an n_thresholds outside the range fails with an error string: the thresholds are the one
+ *   thing the call copies to the host (at most 4 KB), so it synchronises the stream once, before anything is
+ *   launched.  For that reason the call CANNOT be recorded under stream capture (hipGraph, torch.cuda.graph), unlike the other
+ *   searches of the gallery.
+ *   A float64 threshold t of the reference (np.arange) compares with a float32 distance as the smallest float32 >= t does:
+ *   convert with that rule, not by rounding to nearest (oneshot.Gallery.roc does).
+ * Strictness: dist < t is dist <= nextafterf(t, -inf), the device dif_match_rank uses.
+ * Units, arithmetic and NaN rule: dif_match_within's, under the handle's "clamp_nan" -- metric 0 bit-identical to the
+ *   reference; metric 1 up to the arccos (evaluated in double and rounded once), so against NumPy a pair within ~2e-6 of a
+ *   threshold may fall on its other side.  The counts are exact on the distances dif_pairwise / dif_match_within report.
+ * An empty gallery gives zeros; n = 0 launches no search and still zeroes the outputs.
+ * Costs ONE pass of the f32 MFMA over the gallery per round of probes whatever n_thresholds is (dif_match_within's main loop,
+ *   tiles and key; each key is binned by a binary search of an LDS table) plus the reference arithmetic on exactly the pairs
+ *   too close to a threshold to call, one by one.  Counts are integers throughout: two calls give identical arrays.  Workspace,
+ *   its own: 16 bytes per probe and 128 rows (gallery option "roc_round").  The counts of row shards add. */
+#define DIF_ROC_MAX_THRESHOLDS 1024
+int dif_match_roc(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* probe_labels_dev /* [n] */,
+                  const int64_t* row_labels_dev /* [size] */, const int64_t* first_row_dev /* [n], or NULL */,
+                  const float* thresholds_dev /* [n_thresholds] */, int n_thresholds,
+                  int64_t* accept_out_dev /* [n_thresholds][2] */, int64_t* totals_out_dev /* [4] */, void* stream);
 /* merge R per-shard results laid out [R][n] (after an all-gather): lowest key, then
  * lowest global index -- equals np.argmin over the concatenated gallery */
 int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n,
