@@ -15,7 +15,9 @@
 // writes them to LDS ([component][tile][16 ch], 16-byte chunks XOR-swizzled by tile); two such stages alternate, one
 // barrier per K-step.  A operands come from LDS, B operands (U in fragment order: 1 KB per wave instruction) straight
 // from L2; both sit in two register sets, component j in set j & 1, fetched two components ahead (B across the K-step
-// boundary).  The K loop runs every step but the last with all its loads unconditional and the last step peeled; the
+// boundary; in the four-wave shapes B comes in half sets, each re-filled behind the eight MFMAs that read it, 24 MFMAs
+// ahead of its next use: WinoW::B_HALVES).  The K loop runs every step but the last with all its
+// loads unconditional and the last step peeled; the
 // next step's tile loads are issued half a step in, behind the B loads of the second half, and first waited on by the
 // transform at the end of the step (vmcnt retires in order: what is issued behind them would wait for them).  The
 // compiled order of issue, waits and registers of every instantiation: profiles/r11_wino_kloop_isa.txt, DESIGN 4b.
@@ -45,6 +47,9 @@ constexpr int64_t ODD_MIN_TILES = 128 * 16;
 
 #ifndef DIF_WINO_RES_UNDER_K
 #define DIF_WINO_RES_UNDER_K 1                 // (WinoW::RES_UNDER_K)
+#endif
+#ifndef DIF_WINO_B_HALVES
+#define DIF_WINO_B_HALVES 1                    // (WinoW::B_HALVES)
 #endif
 
 // The block shapes.
@@ -86,6 +91,12 @@ struct WinoW {
   // ONE_PASS: the shortcut tiles of both column fragments are requested inside the peeled last K-step, into the registers
   // the tile loader has left (-DDIF_WINO_RES_UNDER_K=0 requests them behind the K loop instead: the A/B build of round 12)
   static constexpr bool RES_UNDER_K = ONE_PASS && DIF_WINO_RES_UNDER_K;
+  // The four-wave shapes: a component's B operands are fetched as two halves (k quads 0 and 1: the operands of its first
+  // and of its last eight MFMAs), each right behind the eight MFMAs that read the registers it overwrites -- 24 MFMAs
+  // (1 536 cycles) ahead of its first use, where a whole set behind the component's last MFMA is 16 ahead.  A wave alone
+  // on its SIMD waited on B in front of every component (profiles/r13_wino_block_trace.txt).
+  // -DDIF_WINO_B_HALVES=0 builds whole sets, the loop the eight-wave shapes keep: the A/B build of round 13
+  static constexpr bool B_HALVES = CPW_ == 4 && DIF_WINO_B_HALVES;
   static_assert(NT / 8 == TT && CPW % 2 == 0, "one loader thread per (tile, channel pair)");
   static_assert(!ONE_PASS || (TT == 32 && 8 * TT * wino::BN * 4 <= LDS_BYTES), "one pass: eight planes of 32 tiles x 64 channels");
 };
@@ -246,6 +257,23 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
             acc[j][mf][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j & 1][mf][q][t], bw[j & 1][nf][q][t], acc[j][mf][nf], 0, 0, 0);
   };
 
+  // (B_HALVES) k quad q of component j alone: the B loads of its two column fragments, and the eight MFMAs that read them
+  // (mfma(j) is mfma_half(j, 0) then mfma_half(j, 1): the same MFMAs in the same order)
+  auto bload_half = [&](int j, int ks, int q) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+      bw[j & 1][nf][q] = buf_load4(wrs, boff0 + (uint32_t)j * bstep + (uint32_t)ks * 4096u + (uint32_t)(nf * 2 + q) * 1024u);
+  };
+  auto mfma_half = [&](int j, int q) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+        for (int nf = 0; nf < 2; ++nf)
+          acc[j][mf][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j & 1][mf][q][t], bw[j & 1][nf][q][t], acc[j][mf][nf], 0, 0, 0);
+  };
+
   // ---- (ONE_PASS) the byte offsets of the tile's four outputs in both column fragments, for the shortcut loads and the stores
   // alike, and the request of the shortcut tiles.  The request is unconditional: without a shortcut the descriptor has size
   // zero and the loads return 0 without touching memory (a run-time branch inside the peeled K-step would bring two paths
@@ -284,6 +312,9 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
     // (vmcnt retires in order: a wait counted for the B loads alone drained the tile loads issued just before).
     // Order of issue: the tile loads of step ks + 1 go out after the B loads of this step's second half, so every B wait
     // in front of the second half's MFMAs counts loads issued before them, and they have that half's MFMAs as cover.
+    // B_HALVES: the same step with every B set re-filled in two halves, the first in the middle of the component that
+    // reads the set, the second where the whole set went; the tile loads keep their place behind the last B load of the
+    // first half of the step, and every B wait in front of the second half still counts loads issued before them.
     auto step = [&](int ks, auto last) {
       const float* cur = wino_smem + (ks & 1) * S::STAGE;
       float* nxt = wino_smem + ((ks + 1) & 1) * S::STAGE;
@@ -291,13 +322,29 @@ __global__ __launch_bounds__(S::NT, S::MIN_BLOCKS) void conv_wino_kernel(const C
       aread(cur, 1);
 #pragma unroll
       for (int j = 0; j < CPW; ++j) {
-        mfma(j);
-        __builtin_amdgcn_sched_barrier(0);
-        if (j + 2 < CPW) {
-          aread(cur, j + 2);
-          bload(j + 2, ks);
-        } else if (!last.value) {
-          bload(j + 2 - CPW, ks + 1);
+        if constexpr (S::B_HALVES) {
+          mfma_half(j, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (j + 2 < CPW) bload_half(j + 2, ks, 0);
+          else if (!last.value) bload_half(j + 2 - CPW, ks + 1, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          mfma_half(j, 1);
+          __builtin_amdgcn_sched_barrier(0);
+          if (j + 2 < CPW) {
+            aread(cur, j + 2);
+            bload_half(j + 2, ks, 1);
+          } else if (!last.value) {
+            bload_half(j + 2 - CPW, ks + 1, 1);
+          }
+        } else {
+          mfma(j);
+          __builtin_amdgcn_sched_barrier(0);
+          if (j + 2 < CPW) {
+            aread(cur, j + 2);
+            bload(j + 2, ks);
+          } else if (!last.value) {
+            bload(j + 2 - CPW, ks + 1);
+          }
         }
         if (!last.value && j == CPW / 2 - 1) dload(ks + 1, d);
         // (the peeled step has no tile to fetch: d's registers take the shortcut tiles, whose latency then runs under
@@ -492,11 +539,19 @@ template <class S>
 static int launch_wino(const ConvArgs& a, hipStream_t st, const char* name) {
   const auto kern = a.trace ? conv_wino_kernel<S, true> : conv_wino_kernel<S, false>;
   if (allow_dynamic_lds(reinterpret_cast<const void*>(kern), S::LDS_BYTES)) return -1;
+  // [dbg bit 67108864: the half-block shapes ask for 24 KiB of dynamic LDS they do not use, 88 KiB in all, so that one block
+  // is resident per CU and every wave is alone on its SIMD -- with dbg 256 the stamps of a lone wave's K loop.  The limit
+  // is raised per launch: allow_dynamic_lds remembers a kernel, not a size]
+  int lds = S::LDS_BYTES;
+  if (S::TT == 32 && (a.dbg & 67108864)) {
+    lds += 24 * 1024;
+    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  }
   const int64_t ntiles = S::ODD ? (int64_t)a.N * ((a.H + 1) / 2) * ((a.W + 1) / 2) : (int64_t)a.N * (a.H / 2) * (a.W / 2);
   const int blocks_m = (int)((ntiles + S::TT - 1) / S::TT), tiles_n = a.Cout / wino::BN;
   const int64_t nblocks = (int64_t)blocks_m * tiles_n;
   if (nblocks >= 0x7fffffffLL) return set_error("conv: too many tiles");
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(S::NT), S::LDS_BYTES, st, a, blocks_m, (int)nblocks);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(S::NT), lds, st, a, blocks_m, (int)nblocks);
   DIF_HIP(hipGetLastError());
   g_last_kernel = name;
   return 0;
