@@ -113,6 +113,7 @@ int Net::pool(const std::string& name, int x, int k, int stride, int pad, int mo
   p.pad_t = p.pad_l = pad;
   p.zero_pad = zero_pad;
   p.pool_mode = mode;
+  p.ceil_mode = ceil_mode;
   p.Cin = p.Cout = td.C;
   // ceil_mode (Caffe's pooling, MTCNN): the last window may hang over the bottom / right edge; the kernel skips taps outside
   const int rnd = ceil_mode ? stride - 1 : 0;
@@ -1365,14 +1366,16 @@ const char* Net::kernel_name(const Op& op, int n) const {
   return "?";
 }
 
+float* Net::root_ptr(int t, const Lane& L, float* out) const {
+  if (t < 0) return nullptr;
+  // outputs are laid out one after another, each for the WHOLE batch: a lane writes its images' part of each
+  if (is_output(t)) return out + (int64_t)L.out_n * output_offset(t) + (int64_t)L.out_start * tensors[t].elems();
+  return L.bufs[tensors[root_of(t)].buf];
+}
+
 // One layer op of one lane (a lane = its own activation buffers + stream-K workspace).
 int Net::run_op(const Op& op, Lane& L, const void* xin, int n, int layout, int dtype, float* out, hipStream_t st) {
-  auto ptr = [&](int t) -> float* {
-    if (t < 0) return nullptr;
-    // outputs are laid out one after another, each for the WHOLE batch: a lane writes its images' part of each
-    if (is_output(t)) return out + (int64_t)L.out_n * output_offset(t) + (int64_t)L.out_start * tensors[t].elems();
-    return L.bufs[tensors[root_of(t)].buf];
-  };
+  auto ptr = [&](int t) -> float* { return root_ptr(t, L, out); };
   switch (op.kind) {
     case OP_INPUT: {
       InputArgs a;
@@ -1646,6 +1649,93 @@ int Net::embed(const void* xin, int n, int layout, int dtype, float* out, hipStr
   for (int l = l_first; l < nl; ++l) {
     DIF_HIP(hipEventRecord(lanes[l].done, lanes[l].stream));
     DIF_HIP(hipStreamWaitEvent(st, lanes[l].done, 0));
+  }
+  return 0;
+}
+
+// What run_op hands op i's kernel, as text (include/dif.h: dif_net_op_describe).  Names, not folded values: a reader
+// folds the batch normalisations itself from the parameters.  Valid before finalize (finalize may then still turn a
+// first output into its even pixels, y_sub, and its reader's stride into 1: the line says what holds when it is asked).
+const char* Net::describe(int i) {
+  static const char* const kinds[] = {"input", "conv", "maxpool", "dwfull", "l2norm", "lrn", "zero", "upsample", "copy",
+                                      "dwconv", "gdctail"};
+  static const char* const acts[] = {"none", "relu", "prelu", "relu6"};
+  static const char* const pools[] = {"max", "l2", "avg"};
+  const Op& op = ops[i];
+  char b[256];
+  std::string s = std::string("kind=") + kinds[op.kind] + " name=" + op.name;
+  auto tensor = [&](const char* key, int t) {
+    if (t < 0) {
+      s += std::string(" ") + key + "=-";
+      return;
+    }
+    const TensorDesc& v = tensors[t];
+    const TensorDesc& r = tensors[root_of(t)];
+    // root H,W,C, then the view window: channel offset, row / column offset, and the view's H,W,C
+    snprintf(b, sizeof(b), " %s=%d,%d,%d,%d,%d,%d,%d,%d,%d", key, r.H, r.W, r.C, v.parent >= 0 ? v.coff : 0,
+             v.parent >= 0 ? v.oy : 0, v.parent >= 0 ? v.ox : 0, v.H, v.W, v.C);
+    s += b;
+  };
+  tensor("x", op.x);
+  tensor("res", op.res);
+  tensor("y", op.y);
+  tensor("y2", op.y2);
+  snprintf(b, sizeof(b), " k=%d,%d stride=%d pad=%d,%d cin=%d cin_true=%d cout=%d", op.KH, op.KW, op.stride, op.pad_t,
+           op.pad_l, op.Cin, op.Cin_true, op.Cout);
+  s += b;
+  snprintf(b, sizeof(b), " act=%s act2=%s pre_act=%s const_alpha=%.9g res_stride=%d y_sub=%d chw_flatten=%d k_order=%d",
+           acts[op.act], acts[op.act2], acts[op.pre_act], (double)op.const_alpha, op.res_stride, (int)op.y_sub,
+           (int)op.chw_flatten, op.k_order);
+  s += b;
+  snprintf(b, sizeof(b), " pool=%s zero_pad=%d ceil=%d", pools[op.pool_mode], op.zero_pad, (int)op.ceil_mode);
+  s += b;
+  auto param = [&](const char* key, int p) { s += std::string(" ") + key + "=" + (p >= 0 ? params[p].name : std::string("-")); };
+  param("w", op.w);
+  param("bias", op.bias);
+  param("alpha", op.alpha);
+  param("alpha2", op.alpha2);
+  auto bnref = [&](const char* key, const BNRef& r) {
+    if (!r.valid()) {
+      s += std::string(" ") + key + "=-";
+      return;
+    }
+    const std::string& g = params[r.gamma].name;     // "<prefix>/gamma"
+    snprintf(b, sizeof(b), ",%.9g", (double)r.eps);
+    s += std::string(" ") + key + "=" + g.substr(0, g.rfind('/')) + b;
+  };
+  bnref("bn", op.bn);
+  bnref("bn2", op.bn2);
+  bnref("pre_bn", op.pre_bn);
+  describe_line = s;
+  return describe_line.c_str();
+}
+
+// One forward on the single-lane path (as the profiled and the clocked forward) that also copies out, right after op i is
+// enqueued, the first n images of the ROOT buffers of that op's x, res, y and y2 (taps[0..3]; null = not wanted): the very
+// memory run_op's ptr() gave the kernel, outputs that live in the caller's buffer included.  Device-to-device copies on
+// the same stream: no sync, no kernel, nothing different in the launches.
+int Net::embed_tap(const void* xin, int n, int layout, int dtype, float* out, hipStream_t st, int i, float* const taps[4]) {
+  if (!finalized) return set_error("dif_net_embed_tap: call dif_net_finalize first");
+  if (i < 0 || i >= (int)ops.size()) return set_error("dif_net_embed_tap: op index %d outside [0, %d)", i, (int)ops.size());
+  if (n < 1 || n > max_batch) return set_error("dif_net_embed_tap: batch %d outside [1, max_batch=%d]", n, max_batch);
+  if (!xin || !out) return set_error("dif_net_embed_tap: null pointer");
+  if (layout != DIF_LAYOUT_NHWC && layout != DIF_LAYOUT_NCHW) return set_error("dif_net_embed_tap: bad layout %d", layout);
+  if (dtype != DIF_DTYPE_F32 && dtype != DIF_DTYPE_U8) return set_error("dif_net_embed_tap: bad dtype %d", dtype);
+  lanes_active = false;
+  lanes[0].out_n = n;
+  lanes[0].out_start = 0;
+  for (int k = 0; k < (int)ops.size(); ++k) {
+    if (run_op(ops[k], lanes[0], xin, n, layout, dtype, out, st)) return -1;
+    if (k != i) continue;
+    const int operands[4] = {ops[k].x, ops[k].res, ops[k].y, ops[k].y2};
+    for (int j = 0; j < 4; ++j) {
+      const int t = operands[j];
+      if (t < 0 || !taps[j]) continue;
+      const int r = root_of(t);
+      if (!is_output(t) && tensors[r].buf < 0) return set_error("dif_net_embed_tap: op %d operand %d has no buffer", i, j);
+      DIF_HIP(hipMemcpyAsync(taps[j], root_ptr(t, lanes[0], out), (size_t)n * tensors[r].elems() * sizeof(float),
+                             hipMemcpyDeviceToDevice, st));
+    }
   }
   return 0;
 }

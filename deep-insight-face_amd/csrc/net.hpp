@@ -52,6 +52,7 @@ struct Op {
   bool y_sub = false;         // output y keeps its even pixels only (finalize: its one reader is a 1x1 / stride 2 convolution)
   int zero_pad = 0;
   int pool_mode = POOL_MAX;
+  bool ceil_mode = false;     // pooling: the last window may hang over the bottom / right edge (Net::pool; dif_net_op_describe reports it)
   float const_alpha = 0.f;    // act == ACT_PRELU with one slope for every channel (LeakyReLU)
   bool chw_flatten = false;
   int k_order = 0;            // see ConvArgs::k_order   // dense after an NCHW-order flatten: permute kernel rows at pack time
@@ -172,6 +173,13 @@ struct Net {
   std::vector<size_t> trace_off;
   int embed_clock(const void* x, int n, int layout, int dtype, float* out, hipStream_t st, double* ghz);
   int run_op(const Op& op, Lane& L, const void* x, int n, int layout, int dtype, float* out, hipStream_t st);
+  // where tensor t's ROOT lives in this forward: the lane's pooled buffer, or the lane's part of the caller's output buffer
+  float* root_ptr(int t, const Lane& L, float* out) const;
+  // diagnostics (dif_net_op_describe / dif_net_embed_tap): what run_op hands op i's kernel, as one line of key=value pairs,
+  // and a single-lane forward that copies the root buffers of op i's operands out right after the op is enqueued
+  std::string describe_line;
+  const char* describe(int i);
+  int embed_tap(const void* x, int n, int layout, int dtype, float* out, hipStream_t st, int i, float* const taps[4]);
   const char* kernel_name(const Op& op, int n) const;
   double flops_per_image() const;
   void release_device();

@@ -147,6 +147,21 @@ int dif_net_op_info(const dif_net* h, int i, const char** name, const char** ker
   return 0;
 }
 
+const char* dif_net_op_describe(const dif_net* h, int i) {
+  if (!h || i < 0 || i >= (int)h->net.ops.size()) {
+    set_error("dif_net_op_describe: index out of range");
+    return nullptr;
+  }
+  return const_cast<dif_net*>(h)->net.describe(i);   // (the line lives in the net until the next call)
+}
+
+int dif_net_embed_tap(dif_net* h, const void* x_dev, int n, int layout, int dtype, float* out_dev, int i, float* x_tap,
+                      float* res_tap, float* y_tap, float* y2_tap, void* stream) {
+  if (!h) return set_error("dif_net_embed_tap: null handle");
+  float* const taps[4] = {x_tap, res_tap, y_tap, y2_tap};
+  return h->net.embed_tap(x_dev, n, layout, dtype, out_dev, (hipStream_t)stream, i, taps);
+}
+
 int dif_net_op_traffic(const dif_net* h, int i, double* act_bytes_per_image, double* param_bytes) {
   if (!h || i < 0 || i >= (int)h->net.ops.size()) return set_error("dif_net_op_traffic: index out of range");
   const Net& net = h->net;

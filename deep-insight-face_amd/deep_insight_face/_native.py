@@ -95,6 +95,9 @@ SIGNATURES = {
     'dif_net_op_info': (c_int, [c_void_p, c_int, P(c_char_p), P(c_char_p), P(c_double)]),
     'dif_net_op_traffic': (c_int, [c_void_p, c_int, P(c_double), P(c_double)]),
     'dif_net_embed_profile': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, P(c_float)]),
+    'dif_net_op_describe': (c_char_p, [c_void_p, c_int]),
+    'dif_net_embed_tap': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     'dif_arcmargin_create': (c_int, [P(c_void_p), c_int, c_int64, c_float, c_float]),
     'dif_arcmargin_destroy': (c_int, [c_void_p]),
     'dif_arcmargin_set_weight': (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -241,6 +241,77 @@ class DifEmbedder:
             rows.append((name.value.decode(), kern.value.decode(), macs.value))
         return rows
 
+    def op_describe(self):
+        """What every launch hands its kernel (include/dif.h: dif_net_op_describe), one dict per launch of ``op_table()``.
+        'x', 'res', 'y', 'y2' are None or dicts {'root': (H, W, C), 'coff', 'oy', 'ox', 'view': (H, W, C)}; 'k' and 'pad' are
+        pairs; 'bn', 'bn2', 'pre_bn' are None or (prefix, eps); 'w', 'bias', 'alpha', 'alpha2' parameter names or None;
+        the other numeric keys are ints ('const_alpha' a float), 'kind', 'name', 'act', 'act2', 'pre_act', 'pool' strings.
+        Needs no device: it reads the launch list, before or after the net is finalized."""
+        rows = []
+        for i in range(N.lib.dif_net_launch_count(self._h)):
+            line = N.lib.dif_net_op_describe(self._h, i)
+            if line is None:
+                raise N.DifError(N.last_error())
+            d = {}
+            for item in line.decode().split(' '):
+                key, val = item.split('=', 1)
+                if key in ('x', 'res', 'y', 'y2'):
+                    if val == '-':
+                        d[key] = None
+                    else:
+                        v = [int(t) for t in val.split(',')]
+                        d[key] = {'root': tuple(v[0:3]), 'coff': v[3], 'oy': v[4], 'ox': v[5], 'view': tuple(v[6:9])}
+                elif key in ('k', 'pad'):
+                    d[key] = tuple(int(t) for t in val.split(','))
+                elif key in ('bn', 'bn2', 'pre_bn'):
+                    d[key] = None if val == '-' else (val.rsplit(',', 1)[0], float(val.rsplit(',', 1)[1]))
+                elif key in ('w', 'bias', 'alpha', 'alpha2'):
+                    d[key] = None if val == '-' else val
+                elif key in ('kind', 'name', 'act', 'act2', 'pre_act', 'pool'):
+                    d[key] = val
+                elif key == 'const_alpha':
+                    d[key] = float(val)
+                else:
+                    d[key] = int(val)
+            rows.append(d)
+        return rows
+
+    def tap(self, x, i):
+        """One single-lane forward of the batch x (at most max_batch images) that also copies out what launch i's kernel was
+        handed (include/dif.h: dif_net_embed_tap): a dict with the ROOT tensors of the launch's 'x', 'res', 'y', 'y2' as
+        float32 CUDA tensors [n, H, W, C] (the operands it has) and 'out', the forward's outputs as ``embed`` returns
+        them.  Afterwards ``op_table()`` names the kernels this forward ran."""
+        dev = N.require_device()
+        self._finalize()
+        t = torch.from_numpy(np.ascontiguousarray(x)) if not torch.is_tensor(x) else x
+        if t.dtype != torch.uint8:
+            t = t.to(torch.float32)
+        t = t.to(dev).contiguous()
+        n = t.shape[0]
+        if t.dim() != 4 or n < 1 or n > self.max_batch:
+            raise ValueError('tap one 4-D batch of 1 .. max_batch = %d images' % self.max_batch)
+        if tuple(t.shape[1:]) == self.input_shape:
+            layout = N.LAYOUT_NHWC
+        elif tuple(t.shape[1:]) == (3,) + self.input_shape[:2]:
+            layout = N.LAYOUT_NCHW
+        else:
+            raise ValueError('input %s matches neither layout of %s' % (tuple(t.shape), self.input_shape))
+        dtype = N.DTYPE_U8 if t.dtype == torch.uint8 else N.DTYPE_F32
+        desc = self.op_describe()[i]
+        sizes = [int(np.prod(s)) for s in self.output_shapes]
+        flat = torch.empty((n * sum(sizes),), dtype=torch.float32, device=dev)
+        taps = {k: torch.empty((n,) + desc[k]['root'], dtype=torch.float32, device=dev)
+                for k in ('x', 'res', 'y', 'y2') if desc[k] is not None}
+        N.check(N.lib.dif_net_embed_tap(self._h, N.ptr(t), n, layout, dtype, N.ptr(flat), int(i),
+                                        *[N.ptr(taps[k]) if k in taps else None for k in ('x', 'res', 'y', 'y2')],
+                                        N.stream_ptr()))
+        outs, off = [], 0
+        for sz, shp in zip(sizes, self.output_shapes):
+            outs.append(flat[off:off + n * sz].view((n,) + shp))
+            off += n * sz
+        taps['out'] = outs if len(outs) > 1 else outs[0].view((n,) + self.output_shape)
+        return taps
+
     def op_traffic(self):
         """Compulsory HBM bytes of every launch: (activation bytes per image, parameter bytes) -- the mixed roofline's
         memory side (include/dif.h: dif_net_op_traffic)."""

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round"; + dif_match_roc, gallery option "roc_round" (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round"; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -562,6 +562,22 @@ int dif_net_op_info(const dif_net* net, int i, const char** name, const char** k
 int dif_net_op_traffic(const dif_net* net, int i, double* act_bytes_per_image, double* param_bytes);
 int dif_net_embed_profile(dif_net* net, const void* x_dev, int n, int layout, int dtype, float* out_dev,
                           void* stream, float* ms_host);
+/* test aids: one layer at a time against a reference of that layer.
+ * dif_net_op_describe: what launch i (the index of dif_net_op_info) hands its kernel, as one line of key=value pairs; the
+ * pointer is valid until the next call on that net; works before dif_net_finalize (which may still turn a first output
+ * into its even pixels -- y_sub -- and its reader's stride into 1: the line says what holds when it is asked).  Keys:
+ *   kind (input conv maxpool dwfull l2norm lrn zero upsample copy dwconv gdctail), name;
+ *   x, res, y, y2: "-" or nine integers -- the ROOT tensor's H,W,C, then the view window coff,oy,ox and the view's H,W,C;
+ *   k=KH,KW stride pad=top,left cin cin_true cout; act act2 pre_act (none relu prelu relu6) const_alpha res_stride y_sub
+ *   chw_flatten k_order; pool (max l2 avg) zero_pad ceil; w bias alpha alpha2: parameter NAMES (dif_net_param_info) or "-";
+ *   bn bn2 pre_bn: "-" or "<prefix>,<eps>" with parameters <prefix>/gamma, /beta, /moving_mean, /moving_variance.
+ * dif_net_embed_tap: one forward of n in [1, max_batch] images on a single lane (as dif_net_embed_profile) which, right after
+ * launch i is enqueued, copies the first n images of the root buffers of that launch's x, res, y and y2 -- the memory the
+ * kernel was handed, [n,H,W,C] of the root -- device to device on `stream` into x_tap .. y2_tap (null, or an operand the
+ * launch does not have: skipped).  No sync, no extra kernel; the launches are those of dif_net_embed on one lane. */
+const char* dif_net_op_describe(const dif_net* net, int i);
+int dif_net_embed_tap(dif_net* net, const void* x_dev, int n, int layout, int dtype, float* out_dev, int i, float* x_tap,
+                      float* res_tap, float* y_tap, float* y2_tap, void* stream);
 
 /* ------------------------------------------------------------------ ArcMargin logits
  * Not in the reference (north_star only; ArcFace, Deng et al. 2019):

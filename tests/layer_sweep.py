@@ -1,0 +1,136 @@
+"""The layer-tap sweep shared by tests/test_layer_taps_gpu.py and tools/layer_taps.py: for EVERY launch of a
+net, one tapped forward, the float64 reference of that launch computed on the device from the very x and res the kernel
+read, and every element of every image of what it stored held to the gates:
+
+  hard, per element      |y - ref| <= B (layer_ref.bound_factor x A~), y2 the same; exact layers bit for bit
+  tight, per layer       max |y - ref| / A~ <= 8 max(max |y32 - ref| / A~, 2 u)   (f32 and Winograd forms; y32: the float32
+                         yardstick on the same input -- the same sum over taps, or the Winograd order of operations)
+  untouched forward      every tapped forward's outputs equal embed's, bit for bit
+
+Failures are collected, not raised: the caller asserts on the list, so one run names every failing layer."""
+import re
+
+import torch
+
+import layer_ref as L
+
+WINO = ('conv_wino_kernel', 'conv_winow_kernel', 'conv_winox_kernel')
+# launches that keep their own head / whole-net tests (the issue's "what stays out"): no per-layer reference here
+STAY_OUT = ('gdctail', 'dwfull', 'l2norm', 'lrn')
+
+
+def kernel_form(kern):
+    if kern.startswith(WINO):
+        return 'wino'
+    if 'split-bf16' in kern:
+        return 'bf16'
+    return 'direct'
+
+
+def family(kern):
+    """The label a record is kept under: the kernel's name with its tile / operand form, as op_table() gives it, without the
+    split-K factor (it moves with the batch and the device's block count)."""
+    return re.sub(r',S=\d+', '', kern)
+
+
+def _outs(t):
+    return list(t) if isinstance(t, (list, tuple)) else [t]
+
+
+def _fmt(name, kern, what, ratio, at, extra=''):
+    return '%s [%s] %s: ratio %.3g at image %d, pixel (%d, %d), channel %d%s' % (name, kern, what, ratio, at[0], at[1], at[2], at[3], extra)
+
+
+def sweep(model, x, label='', record=None, verbose=False, params=None):
+    """x: the input batch on the device (uint8 or float32, NHWC).  Returns (failures, kernel labels seen, launches checked).
+    record: dict kernel label -> {'hard': (ratio, layer), 'tight': (kernel / yardstick ratio, layer)}, worst kept.
+    params: the reference's parameters, the model's own unless a test hands it others on purpose."""
+    params = model.get_weights() if params is None else params
+    descs = model.op_describe()
+    want_out = [t.clone() for t in _outs(model.embed(x))]
+    scale, bias, bgr, hflip = getattr(model, '_transform', (1.0, (0.0, 0.0, 0.0), False, False))
+    bf_terms = {'bf16x3': 3, 'bf16x2': 2}.get(model.compute, 0)
+    fails, seen, checked = [], set(), 0
+
+    def note(kern, key, ratio, layer):
+        if record is not None:
+            r = record.setdefault(family(kern), {})
+            if key not in r or ratio > r[key][0]:
+                r[key] = (ratio, layer)
+
+    for i, d in enumerate(descs):
+        tap = model.tap(x, i)
+        name, kern, _ = model.op_table()[i]
+        seen.add(kern)
+        got_out = _outs(tap['out'])
+        if len(got_out) != len(want_out) or not all(torch.equal(a, b) for a, b in zip(got_out, want_out)):
+            fails.append('%s [%s]: the tapped forward\'s outputs differ from embed\'s' % (name, kern))
+        kind = d['kind']
+        if kind in STAY_OUT:
+            continue
+        checked += 1
+        try:
+            if kind == 'input':
+                ref = L.input_convert(x, False, scale, bias, bgr, hflip)
+                if not torch.equal(tap['y'], ref):
+                    r, at = L.worst(tap['y'], ref, torch.zeros_like(ref, dtype=torch.float64))
+                    fails.append(_fmt(name, kern, 'not bit-exact', r, at))
+            elif kind == 'maxpool':
+                y, y2 = L.pool_layer(d, params, tap['x'])
+                for key, ref in (('y', y), ('y2', y2)):
+                    if ref is None:
+                        continue
+                    got = L.window(d[key], tap[key])
+                    if not torch.equal(got, ref):
+                        r, at = L.worst(got, ref, torch.zeros_like(ref, dtype=torch.float64))
+                        fails.append(_fmt(name, kern, key + ' not bit-exact', r, at))
+            elif kind in ('upsample', 'copy'):
+                L._whole(d['x'], 'x')
+                ref = L.upsample_layer(tap['x']) if kind == 'upsample' else tap['x']
+                got = L.window(d['y'], tap['y'])
+                if not torch.equal(got, ref):
+                    r, at = L.worst(got, ref, torch.zeros_like(ref, dtype=torch.float64))
+                    fails.append(_fmt(name, kern, 'not bit-exact', r, at))
+            elif kind == 'zero':
+                if bool((L.window(d['y'], tap['y']) != 0).any()):
+                    fails.append('%s [%s]: not zero' % (name, kern))
+            elif kind == 'dwconv':
+                ref, A = L.dwconv_layer(d, params, tap['x'])
+                K = d['k'][0] * d['k'][1]
+                r, at = L.worst(L.window(d['y'], tap['y']), ref, (K + 8) * L.U * A)
+                note(kern, 'hard', r, name)
+                if not r <= 1.0:
+                    fails.append(_fmt(name, kern, '|y - ref| / B', r, at))
+            elif kind == 'conv':
+                form = kernel_form(kern)
+                ry, ry2, A, A2 = L.conv_layer(d, params, tap['x'], tap.get('res'), torch.float64, form)
+                f = L.bound_factor(d, form, bf_terms)
+                y32 = y32_2 = None
+                if form != 'bf16':
+                    y32, y32_2, _, _ = L.conv_layer(d, params, tap['x'], tap.get('res'), torch.float32, form)
+                for key, ref, mag, yard in (('y', ry, A, y32), ('y2', ry2, A2, y32_2)):
+                    if ref is None:
+                        continue
+                    got = L.window(d[key], tap[key])
+                    ref, mag = L.stored(d, key, ref), L.stored(d, key, mag)
+                    if got.shape != ref.shape:
+                        raise L.NotUnderstood('%s stored as %s, reference %s' % (key, tuple(got.shape), tuple(ref.shape)))
+                    r, at = L.worst(got, ref, f * mag)
+                    note(kern, 'hard', r, name)
+                    if verbose:
+                        print('%s %s [%s] %s: |y - ref| / B %.4f' % (label, name, kern, key, r))
+                    if not r <= 1.0:
+                        fails.append(_fmt(name, kern, '|%s - ref| / B' % key, r, at, ' (K = %d, form %s)' % (d['k'][0] * d['k'][1] * d['cin_true'], form)))
+                    if yard is not None:
+                        yard = L.stored(d, key, yard)
+                        rel, lim = L.rel_error(got, ref, mag), L.tight_limit(yard, ref, mag)
+                        note(kern, 'tight', rel / (lim / L.TIGHT_FACTOR), name)
+                        if not rel <= lim:
+                            _, at = L.worst(got, ref, mag)
+                            fails.append(_fmt(name, kern, 'tight gate on %s: |y - ref| / A~ = %.3g, limit %.3g; kernel / yardstick' % (key, rel, lim),
+                                              rel / (lim / L.TIGHT_FACTOR), at))
+            else:
+                raise L.NotUnderstood('launch kind %r' % kind)
+        except L.NotUnderstood as e:
+            fails.append('%s [%s]: the reference does not understand this launch: %s' % (name, kern, e))
+    return fails, seen, checked

@@ -1,0 +1,397 @@
+"""tests/layer_ref.py against the NumPy oracle, its bounds against float32 arithmetic and against planted defects, and
+`op_describe()` against the parameter and launch tables of every architecture (no GPU).
+
+1. conv_layer equals oracle.nets.conv2d / batchnorm / prelu / relu composed in float64 on tiny layers of every geometry
+   the describe line can hold.
+2. The float32 NumPy oracle of the same layers, and the Winograd emulation of tools/winograd_error.py, stay WITHIN the
+   a-priori bound (printed: the worst |y32 - ref| / B).
+3. Five planted defects in a float32 layer (2 images, 6 x 10 x 32 -> 64), each of the size a slipped index leaves in ONE
+   place, each rejected by a gate of tests/test_layer_taps_gpu.py.
+4. For every arch the library builds: each describe line parses, every parameter it names exists with the shape the
+   geometry implies, and the launch list is op_table()'s.
+"""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import layer_ref as L
+from oracle import nets
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 1e-3
+
+
+def T(h, w, c, root=None, coff=0, oy=0, ox=0):
+    return {'root': root or (h, w, c), 'coff': coff, 'oy': oy, 'ox': ox, 'view': (h, w, c)}
+
+
+def D(x, y, k, stride=1, pad=(0, 0), **kw):
+    d = {'kind': 'conv', 'name': 'layer', 'x': x, 'res': None, 'y': y, 'y2': None, 'k': k, 'stride': stride, 'pad': pad,
+         'cin': x['root'][2], 'cin_true': x['root'][2], 'cout': (y or kw.get('y2'))['view'][2], 'act': 'none', 'act2': 'none',
+         'pre_act': 'none', 'const_alpha': 0.0, 'res_stride': 1, 'y_sub': 0, 'chw_flatten': 0, 'k_order': 0, 'pool': 'max',
+         'zero_pad': 0, 'ceil': 0, 'w': 'layer/kernel', 'bias': None, 'alpha': None, 'alpha2': None, 'bn': None, 'bn2': None,
+         'pre_bn': None}
+    d.update(kw)
+    return d
+
+
+def bn_params(rng, prefix, c):
+    return {prefix + '/gamma': rng.uniform(0.5, 1.5, c), prefix + '/beta': rng.standard_normal(c) * 0.2,
+            prefix + '/moving_mean': rng.standard_normal(c) * 0.2, prefix + '/moving_variance': rng.uniform(0.5, 1.5, c)}
+
+
+def make_case(name):
+    """-> desc, params (float32 arrays), x, res, and the oracle composition as a function of (x, res, params)."""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    n = 2
+    p, res = {}, None
+
+    def kernel(kh, kw, ci, co):
+        return rng.standard_normal((kh, kw, ci, co)) * np.sqrt(2.0 / (kh * kw * ci))
+
+    if name == '3x3 pad 1':
+        x = rng.standard_normal((n, 5, 7, 8))
+        p.update({'layer/kernel': kernel(3, 3, 8, 12), 'layer/bias': rng.standard_normal(12) * 0.1}, **bn_params(rng, 'bn', 12))
+        desc = D(T(5, 7, 8), T(5, 7, 12), (3, 3), 1, (1, 1), bias='layer/bias', bn=('bn', EPS), act='relu')
+
+        def want(x, res, q):
+            return nets.relu(nets.batchnorm(nets.conv2d(x, q['layer/kernel'], q['layer/bias'], 1, (1, 1, 1, 1)), q, 'bn', EPS)), None
+    elif name == '3x3 stride 2 detector padding':
+        x = rng.standard_normal((n, 6, 9, 8))
+        p.update({'layer/kernel': kernel(3, 3, 8, 12)}, **bn_params(rng, 'bn', 12))
+        desc = D(T(6, 9, 8), T(3, 4, 12), (3, 3), 2, (1, 1), bn=('bn', EPS), act='prelu', const_alpha=0.1)
+
+        def want(x, res, q):
+            return nets.prelu(nets.batchnorm(nets.conv2d(x, q['layer/kernel'], None, 2, (1, 0, 1, 0)), q, 'bn', EPS), 0.1), None
+    elif name == '1x1 stride 2':
+        x = rng.standard_normal((n, 5, 7, 8))
+        p.update({'layer/kernel': kernel(1, 1, 8, 12), 'layer/bias': rng.standard_normal(12) * 0.1})
+        desc = D(T(5, 7, 8), T(3, 4, 12), (1, 1), 2, (0, 0), bias='layer/bias')
+
+        def want(x, res, q):
+            return nets.conv2d(x, q['layer/kernel'], q['layer/bias'], 2), None
+    elif name == 'VALID 2x2':
+        x = rng.standard_normal((n, 5, 7, 8))
+        p.update({'layer/kernel': kernel(2, 2, 8, 12), 'alpha': rng.uniform(0.1, 0.4, 12)})
+        desc = D(T(5, 7, 8), T(4, 6, 12), (2, 2), 1, (0, 0), act='prelu', alpha='alpha')
+
+        def want(x, res, q):
+            return nets.prelu(nets.conv2d(x, q['layer/kernel']), q['alpha']), None
+    elif name == 'dense after a channel-major flatten':
+        x = rng.standard_normal((n, 3, 2, 8))
+        p.update({'layer/kernel': rng.standard_normal((48, 10)) * 0.2, 'layer/bias': rng.standard_normal(10) * 0.1},
+                 **bn_params(rng, 'features', 10))
+        desc = D(T(3, 2, 8), T(1, 1, 10), (3, 2), 1, (0, 0), bias='layer/bias', bn=('features', EPS), chw_flatten=1)
+
+        def want(x, res, q):
+            flat = x.transpose(0, 3, 1, 2).reshape(x.shape[0], -1)
+            return nets.batchnorm((flat @ q['layer/kernel'] + q['layer/bias']).reshape(-1, 1, 1, 10), q, 'features', EPS), None
+    elif name == 'pre-activation BN':
+        x = rng.standard_normal((n, 5, 7, 8))
+        p.update({'layer/kernel': kernel(3, 3, 8, 12)}, **bn_params(rng, 'pre', 8))
+        desc = D(T(5, 7, 8), T(5, 7, 12), (3, 3), 1, (1, 1), pre_bn=('pre', EPS), pre_act='relu')
+
+        def want(x, res, q):
+            return nets.conv2d(nets.relu(nets.batchnorm(x, q, 'pre', EPS)), q['layer/kernel'], None, 1, (1, 1, 1, 1)), None
+    elif name == 'shortcut at res_stride 2':
+        x = rng.standard_normal((n, 3, 4, 8))
+        res = rng.standard_normal((n, 5, 7, 12))
+        p.update({'layer/kernel': kernel(1, 1, 8, 12), 'layer/bias': rng.standard_normal(12) * 0.1})
+        desc = D(T(3, 4, 8), T(3, 4, 12), (1, 1), 1, (0, 0), bias='layer/bias', res=T(5, 7, 12), res_stride=2)
+
+        def want(x, res, q):
+            return nets.conv2d(x, q['layer/kernel'], q['layer/bias']) + res[:, ::2, ::2, :], None
+    elif name == 'second output, first one sub-sampled':
+        x = rng.standard_normal((n, 6, 8, 8))
+        res = rng.standard_normal((n, 6, 8, 12))
+        p.update({'layer/kernel': kernel(3, 3, 8, 12)}, **bn_params(rng, 'bn', 12), **bn_params(rng, 'bn2', 12))
+        desc = D(T(6, 8, 8), T(3, 4, 12), (3, 3), 1, (1, 1), y2=T(6, 8, 12), bn=('bn', EPS), bn2=('bn2', EPS), act2='relu',
+                 res=T(6, 8, 12), y_sub=1)
+
+        def want(x, res, q):
+            y = nets.batchnorm(nets.conv2d(x, q['layer/kernel'], None, 1, (1, 1, 1, 1)), q, 'bn', EPS) + res
+            return y[:, ::2, ::2, :], nets.relu(nets.batchnorm(y, q, 'bn2', EPS))
+    else:
+        raise KeyError(name)
+    p = {k: np.asarray(v, np.float32) for k, v in p.items()}
+    x = x.astype(np.float32)
+    res = None if res is None else res.astype(np.float32)
+    return desc, p, x, res, want
+
+
+CASES = ['3x3 pad 1', '3x3 stride 2 detector padding', '1x1 stride 2', 'VALID 2x2', 'dense after a channel-major flatten',
+         'pre-activation BN', 'shortcut at res_stride 2', 'second output, first one sub-sampled']
+
+
+def run_ref(desc, p, x, res, dtype=torch.float64, form='direct'):
+    y, y2, A, A2 = L.conv_layer(desc, p, torch.from_numpy(x), None if res is None else torch.from_numpy(res), dtype, form)
+    return (None if y is None else L.stored(desc, 'y', y), y2, L.stored(desc, 'y', A), A2)
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_conv_layer_equals_the_oracle_composed_in_float64(name):
+    desc, p, x, res, want = make_case(name)
+    y, y2, A, A2 = run_ref(desc, p, x, res)
+    p64 = nets.cast_params(p, np.float64)
+    wy, wy2 = want(x.astype(np.float64), None if res is None else res.astype(np.float64), p64)
+    for got, w in ((y, wy), (y2, wy2)):
+        if w is None:
+            assert got is None
+            continue
+        assert tuple(got.shape) == w.shape
+        err = np.abs(got.numpy() - w).max()
+        print('%s: max |conv_layer - oracle| = %.2e (max |oracle| %.2f)' % (name, err, np.abs(w).max()))
+        assert err <= 1e-13 * max(np.abs(w).max(), 1.0)
+    assert bool((A >= y.abs() * (1 - 1e-12)).all())             # the magnitude dominates the value it bounds
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_float32_arithmetic_is_within_the_a_priori_bound(name):
+    """The float32 NumPy oracle of the layer, and conv_layer's own float32 run (the GPU test's yardstick), against the float64
+    reference: inside B = (K + 8) u A~ at every element, and far inside (the issue measured 0.001 .. 0.02)."""
+    desc, p, x, res, want = make_case(name)
+    y, y2, A, A2 = run_ref(desc, p, x, res)
+    f = L.bound_factor(desc, 'direct')
+    oy, oy2 = want(x, res, p)
+    ly, ly2, _, _ = run_ref(desc, p, x, res, torch.float32)
+    for label, got, ref, mag in (('oracle f32 y', oy, y, A), ('oracle f32 y2', oy2, y2, A2), ('yardstick y', ly, y, A), ('yardstick y2', ly2, y2, A2)):
+        if got is None:
+            continue
+        got = torch.as_tensor(np.asarray(got, np.float32))
+        r, at = L.worst(got, ref, f * mag)
+        print('%s, %s: worst |y32 - ref| / B = %.4f at %s (K = %d)' % (name, label, r, at, desc['k'][0] * desc['k'][1] * desc['cin_true']))
+        assert r <= 1.0
+
+
+def _winograd_error():
+    spec = importlib.util.spec_from_file_location('winograd_error', os.path.join(ROOT, 'tools', 'winograd_error.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize('hw,cin', [((6, 10), 32), ((8, 8), 96), ((7, 5), 32)])
+def test_winograd_emulation_is_within_the_winograd_bound(hw, cin):
+    """tools/winograd_error.py's NumPy emulation of the kernels' order of operations, and this module's torch port of it (the
+    GPU test's yardstick for the Winograd forms), inside (Cin + 16 + 8) u A~w; the two emulations agree to rounding; A~w is
+    the 2.5 .. 4 fold of the direct A~ the issue measured (3.6)."""
+    we = _winograd_error()
+    rng = np.random.default_rng(hw[0] * 100 + cin)
+    x = np.maximum(rng.standard_normal((2,) + hw + (cin,)), 0).astype(np.float32)
+    p = {'layer/kernel': (rng.standard_normal((3, 3, cin, 64)) * np.sqrt(2 / (9 * cin))).astype(np.float32)}
+    p.update({k: np.asarray(v, np.float32) for k, v in bn_params(rng, 'bn', 64).items()})
+    desc = D(T(*hw, cin), T(*hw, 64), (3, 3), 1, (1, 1), bn=('bn', EPS), act='relu')
+    y, _, Aw, _ = run_ref(desc, p, x, None, torch.float64, 'wino')
+    _, _, A, _ = run_ref(desc, p, x, None)
+    y_direct, _, _, _ = run_ref(desc, p, x, None)
+    assert torch.equal(y, y_direct)                                  # the reference itself is the plain sum, whatever the form
+    xe = np.pad(x, ((0, 0), (0, hw[0] % 2), (0, hw[1] % 2), (0, 0)))
+    emu = we.wino_even(xe, p['layer/kernel'])[:, :hw[0], :hw[1]]
+    emu = nets.relu(nets.batchnorm(emu, p, 'bn', EPS))
+    port, _, _, _ = run_ref(desc, p, x, None, torch.float32, 'wino')
+    f = L.bound_factor(desc, 'wino')
+    for label, got in (('NumPy emulation', torch.from_numpy(emu)), ('torch port', port)):
+        r, at = L.worst(got, y, f * Aw)
+        print('%s Cin %d, %s: worst |y32 - ref| / B = %.4f at %s; A~w / A~ mean %.2f' % (hw, cin, label, r, at, float((Aw / A).mean())))
+        assert r <= 1.0
+    assert float((port - torch.from_numpy(emu)).abs().max()) <= 64 * L.U * float(y.abs().max())
+    assert 1.5 < float((Aw / A).mean()) < 6.0 and bool((Aw >= A * (1 - 1e-12)).all())
+
+
+# ------------------------------------------------------------------------------------------------- the other layers
+def test_depthwise_reference_and_its_bound():
+    """dwconv_layer equals the oracle's depthwise convolution + BN + ReLU6 in float64 (stride 2 with MobileNetV2's (0, 1)
+    padding of an even side); the float32 oracle is inside (9 + 8) u A~."""
+    rng = np.random.default_rng(11)
+    x = np.maximum(rng.standard_normal((2, 6, 9, 8)), 0).astype(np.float32)
+    p = {'dw/depthwise_kernel': rng.standard_normal((3, 3, 8, 1)).astype(np.float32)}
+    p.update({k: np.asarray(v, np.float32) for k, v in bn_params(rng, 'dw_BN', 8).items()})
+    desc = D(T(6, 9, 8), T(3, 5, 8), (3, 3), 2, (0, 1), w='dw/depthwise_kernel', bn=('dw_BN', EPS), act='relu6', kind='dwconv')
+
+    def oracle(x, q):
+        return nets.relu6(nets.batchnorm(nets.depthwise_conv2d(x, q['dw/depthwise_kernel'], 2, (0, 1, 1, 1)), q, 'dw_BN', EPS))
+    y, A = L.dwconv_layer(desc, p, torch.from_numpy(x))
+    want = oracle(x.astype(np.float64), nets.cast_params(p, np.float64))
+    assert np.abs(y.numpy() - want).max() <= 1e-13 * np.abs(want).max()
+    r, at = L.worst(torch.from_numpy(oracle(x, p)), y, 17 * L.U * A)
+    print('depthwise float32 oracle: worst |y32 - ref| / B = %.4f at %s' % (r, at))
+    assert r <= 1.0
+
+
+@pytest.mark.parametrize('zero_pad,ceil', [(1, 0), (0, 0), (0, 1)])
+def test_pool_reference_is_the_oracles_pool(zero_pad, ceil):
+    """pool_layer: 3 / 2 with one padded row and column that count as 0 (ResNet50V2's ZeroPadding2D) or are skipped, and 2 / 2
+    windows hanging over the bottom / right edge (MTCNN's ceil mode); the second output relu(bn2(y)) in float32."""
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal((2, 7, 9, 8)).astype(np.float32)
+    p = {k: np.asarray(v, np.float32) for k, v in bn_params(rng, 'bn2', 8).items()}
+    if ceil:
+        desc = D(T(7, 9, 8), T(4, 5, 8), (2, 2), 2, (0, 0), kind='maxpool', ceil=1)
+        want = nets.maxpool(x, 2, 2, (0, 1, 0, 1), -np.inf)
+    else:
+        desc = D(T(7, 9, 8), T(4, 5, 8), (3, 3), 2, (1, 1), kind='maxpool', zero_pad=zero_pad, y2=T(4, 5, 8), bn2=('bn2', EPS), act2='relu')
+        want = nets.maxpool(x, 3, 2, (1, 1, 1, 1), 0.0 if zero_pad else -np.inf)
+    y, y2 = L.pool_layer(desc, p, torch.from_numpy(x))
+    assert np.array_equal(y.numpy(), want)
+    if not ceil:
+        sc = (p['bn2/gamma'] / np.sqrt(p['bn2/moving_variance'] + np.float32(EPS))).astype(np.float32)
+        sh = (p['bn2/beta'] - p['bn2/moving_mean'] * sc).astype(np.float32)
+        fused = np.maximum((want.astype(np.float64) * sc + sh).astype(np.float32), 0)        # one rounding: the kernel's fmaf
+        assert np.array_equal(y2.numpy(), fused)
+        assert np.abs(y2.numpy() - nets.relu(nets.batchnorm(want, p, 'bn2', EPS))).max() <= 4 * L.U * np.abs(want).max() * 2
+
+
+def test_input_conversion_and_upsampling_references():
+    rng = np.random.default_rng(3)
+    u8 = rng.integers(0, 256, (2, 4, 5, 3), dtype=np.uint8)
+    y = L.input_convert(torch.from_numpy(u8), False, 1 / 255., (0.0, 0.0, 0.0)).numpy()
+    assert y.shape == (2, 4, 5, 4) and np.all(y[..., 3] == 0)
+    assert np.array_equal(y[..., :3], u8.astype(np.float32) * np.float32(1 / 255.))
+    f = rng.standard_normal((2, 3, 4, 5)).astype(np.float32)                                       # NCHW float, BGR + mean, mirrored
+    mean = (103.939, 116.779, 123.68)
+    y = L.input_convert(torch.from_numpy(f), True, 1.0, tuple(-m for m in mean), bgr=True, hflip=True).numpy()
+    want = f.transpose(0, 2, 3, 1)[:, :, ::-1, ::-1] - np.asarray(mean, np.float32)
+    assert np.array_equal(y[..., :3], want)
+    up = L.upsample_layer(torch.from_numpy(f)).numpy()
+    assert up.shape == (2, 6, 8, 5) and all(np.array_equal(up[:, a::2, b::2], f) for a in (0, 1) for b in (0, 1))
+
+
+# ------------------------------------------------------------------------------------------------- planted defects
+def _defect_layer():
+    rng = np.random.default_rng(7)
+    n, H, W, ci, co = 2, 6, 10, 32, 64
+    x = np.maximum(rng.standard_normal((n, H, W, ci)), 0).astype(np.float32)
+    res = rng.standard_normal((n, H, W, co)).astype(np.float32)
+    p = {'layer/kernel': (rng.standard_normal((3, 3, ci, co)) * np.sqrt(2 / (9 * ci))).astype(np.float32)}
+    p.update({k: np.asarray(v, np.float32) for k, v in bn_params(rng, 'bn', co).items()})
+    desc = D(T(H, W, ci), T(H, W, co), (3, 3), 1, (1, 1), bn=('bn', EPS), act='relu', res=T(H, W, co))
+    return desc, p, x, res
+
+
+def _np_layer(p, x, res, defect=None):
+    """The layer in float32 NumPy, tap by tap; `defect` plants one slip."""
+    n, H, W, ci = x.shape
+    k = p['layer/kernel']
+    scale = (p['bn/gamma'] / np.sqrt(p['bn/moving_variance'] + np.float32(EPS))).astype(np.float32)
+    shift = (p['bn/beta'] - p['bn/moving_mean'] * scale).astype(np.float32)
+    xp = np.pad(x, ((0, 0), (1, 1), (1, 1), (0, 0)))
+    if defect == 'border column padded from the wrong side':
+        xp[:, :, W + 1, :] = xp[:, :, 1, :]                      # the right halo column holds the map's FIRST column
+    v = np.zeros((n, H, W, k.shape[3]), np.float32)
+    for kh in range(3):
+        for kw in range(3):
+            v += xp[:, kh:kh + H, kw:kw + W, :] @ k[kh, kw]
+    if defect == 'one tap of one 32-channel block dropped at one pixel':
+        v[1, 3, 4] -= xp[1, 3 + 2, 4 + 0, :32] @ k[2, 0, :32]
+    if defect == 'the shift left out for one channel':
+        shift = shift.copy()
+        shift[17] = 0
+    r = res
+    if defect == 'the shortcut read from the neighbouring pixel':
+        r = res.copy()
+        r[0, 2, 5] = res[0, 2, 6]
+    y = np.maximum(v * scale + shift, 0) + r
+    if defect == "one image's last tile left at its previous contents":
+        y[1, H - 2:, W - 2:] = y[0, H - 2:, W - 2:]               # what the buffer held: another image's values of the same layer
+    return y.astype(np.float32)
+
+
+DEFECTS = ['border column padded from the wrong side', 'one tap of one 32-channel block dropped at one pixel',
+           'the shift left out for one channel', 'the shortcut read from the neighbouring pixel',
+           "one image's last tile left at its previous contents"]
+
+
+def test_clean_layer_passes_both_gates():
+    desc, p, x, res = _defect_layer()
+    ref, _, A, _ = run_ref(desc, p, x, res)
+    y32, _, _, _ = run_ref(desc, p, x, res, torch.float32)
+    got = torch.from_numpy(_np_layer(p, x, res))
+    hard, _ = L.worst(got, ref, L.bound_factor(desc, 'direct') * A)
+    rel, lim = L.rel_error(got, ref, A), L.tight_limit(y32, ref, A)
+    print('clean float32 NumPy layer: worst |y - ref| / B = %.4f; |y - ref| / A~ = %.2e against the tight limit %.2e' % (hard, rel, lim))
+    assert hard <= 1.0 and rel <= lim
+
+
+@pytest.mark.parametrize('defect', DEFECTS)
+def test_planted_defect_breaks_a_gate(defect):
+    desc, p, x, res = _defect_layer()
+    ref, _, A, _ = run_ref(desc, p, x, res)
+    y32, _, _, _ = run_ref(desc, p, x, res, torch.float32)
+    got = torch.from_numpy(_np_layer(p, x, res, defect))
+    B = L.bound_factor(desc, 'direct') * A
+    hard, at = L.worst(got, ref, B)
+    bad = int(((got.double() - ref).abs() > B).sum())
+    rel, lim = L.rel_error(got, ref, A), L.tight_limit(y32, ref, A)
+    print('%s: %d elements past the hard bound, worst |y - ref| / B = %.1f at %s; tight %.2e against %.2e'
+          % (defect, bad, hard, at, rel, lim))
+    assert bad >= 1 and hard > 1.0
+    assert rel > lim
+
+
+# ------------------------------------------------------------------------------------------------- op_describe
+ARCHS = [('resnet', 'v1', 128, (128, 256)), ('resnet', 'v2', 512, (112, 112)), ('resnet', 'v3', 512, (72, 104)),
+         ('resnet', 'sv2', 128, (72, 104)), ('vgg16', 'v3', 512, (48, 80)), ('vgg16', 'sv2', 128, (96, 160)),
+         ('mobilenet', 'v2', 512, (96, 80)), ('mobilenet', 'v3', 512, (75, 41)), ('iresnet50', 'v2', 512, (112, 112)),
+         ('iresnet100', 'v2', 512, (112, 112)), ('nn4', 'v2', 128, (96, 96)), ('yolov3', 'v3', 1, (64, 160)),
+         ('mtcnn_pnet', 'v3', 1, (37, 53)), ('mtcnn_rnet', 'v3', 1, (24, 24)), ('mtcnn_onet', 'v3', 1, (48, 48))]
+KEYS = {'kind', 'name', 'x', 'res', 'y', 'y2', 'k', 'stride', 'pad', 'cin', 'cin_true', 'cout', 'act', 'act2', 'pre_act',
+        'const_alpha', 'res_stride', 'y_sub', 'chw_flatten', 'k_order', 'pool', 'zero_pad', 'ceil', 'w', 'bias', 'alpha', 'alpha2',
+        'bn', 'bn2', 'pre_bn'}
+KERNEL_OF = {'input': 'input_convert_kernel', 'maxpool': 'maxpool_kernel', 'dwfull': 'dwfull_kernel', 'l2norm': 'l2norm_kernel',
+             'lrn': 'lrn_kernel', 'zero': 'memset', 'upsample': 'upsample2_kernel', 'copy': 'copy_to_view_kernel',
+             'dwconv': 'dwconv_kernel', 'gdctail': 'gdc_tail'}
+
+
+@pytest.mark.parametrize('arch,head,emd,hw', ARCHS)
+def test_op_describe_agrees_with_the_parameter_and_launch_tables(arch, head, emd, hw):
+    from deep_insight_face.networks.triplet import DifEmbedder
+    m = DifEmbedder(arch, head, emd, hw + (3,), max_batch=2)
+    try:
+        rows, table, spec = m.op_describe(), m.op_table(), dict(m.param_spec())
+    finally:
+        m.close()
+    assert [r['name'] for r in rows] == [name for name, _, _ in table] and len(rows) > 3
+    used = set()
+    for r, (_, kern, _) in zip(rows, table):
+        assert set(r) == KEYS, (r['name'], set(r) ^ KEYS)
+        assert kern.startswith(KERNEL_OF[r['kind']]) if r['kind'] != 'conv' else kern.startswith(('conv_', 'stem')), (r['name'], kern)
+        assert r['act'] in ('none', 'relu', 'prelu', 'relu6') and r['pool'] in ('max', 'l2', 'avg')
+        for key in ('x', 'res', 'y', 'y2'):
+            t = r[key]
+            if t is None:
+                continue
+            (rh, rw, rc), (vh, vw, vc) = t['root'], t['view']
+            assert 0 <= t['oy'] and t['oy'] + vh <= rh and 0 <= t['ox'] and t['ox'] + vw <= rw and 0 <= t['coff'] and t['coff'] + vc <= rc, (r['name'], key, t)
+        names = [r[k] for k in ('w', 'bias', 'alpha', 'alpha2') if r[k]]
+        for k, c in (('bn', r['cout'] if r['kind'] != 'gdctail' else r['cin']), ('bn2', r['cout']), ('pre_bn', r['cin'])):
+            if r[k]:
+                assert r[k][1] > 0
+                for part in ('gamma', 'beta', 'moving_mean', 'moving_variance'):
+                    assert spec[r[k][0] + '/' + part] == (c,), (r['name'], k, part)
+                    names.append(r[k][0] + '/' + part)
+        for nm in names:
+            assert nm in spec, (r['name'], nm)
+        used.update(names)
+        if r['kind'] == 'conv':
+            KH, KW = r['k']
+            want = (KH, KW, r['cin_true'], r['cout'])
+            shape = spec[r['w']]
+            assert shape == want or (len(shape) == 2 and shape == (KH * KW * r['cin_true'], r['cout'])), (r['name'], shape, want)
+            assert r['x']['view'][2] == r['cin'] and r['cin_true'] in (r['cin'], 3)
+            Ho, Wo = L.geometry(r)
+            H, W = r['x']['view'][:2]
+            for o, i, kk, pd in ((Ho, H, KH, r['pad'][0]), (Wo, W, KW, r['pad'][1])):
+                assert (o - 1) * r['stride'] - pd < i and (o - 1) * r['stride'] + kk - pd <= i + kk - 1, (r['name'], o, i)
+            for key in ('bias', 'alpha', 'alpha2'):
+                if r[key]:
+                    assert int(np.prod(spec[r[key]])) == r['cout'], (r['name'], key)
+            if r['res']:
+                assert r['res']['view'][2] == r['cout']
+        if r['kind'] == 'dwconv':
+            assert spec[r['w']] == (r['k'][0], r['k'][1], r['cin'], 1)
+    unused = sorted(set(spec) - used)
+    # what no describe line names belongs to the fused head tail (its 1x1 and dense kernels): nothing of a convolution
+    assert all(any(r['kind'] == 'gdctail' for r in rows) for _ in unused) and len(unused) <= 2, unused
