@@ -1373,6 +1373,10 @@ float* Net::root_ptr(int t, const Lane& L, float* out) const {
   return L.bufs[tensors[root_of(t)].buf];
 }
 
+// tf.nn.lrn defaults: depth_radius 5, bias 1; alpha / beta from inceptionv3.py:95.  run_op passes them, describe prints them.
+static constexpr int LRN_RADIUS = 5;
+static constexpr float LRN_BIAS = 1.f, LRN_ALPHA = 1e-4f, LRN_BETA = 0.75f;
+
 // One layer op of one lane (a lane = its own activation buffers + stream-K workspace).
 int Net::run_op(const Op& op, Lane& L, const void* xin, int n, int layout, int dtype, float* out, hipStream_t st) {
   auto ptr = [&](int t) -> float* { return root_ptr(t, L, out); };
@@ -1541,7 +1545,10 @@ int Net::run_op(const Op& op, Lane& L, const void* xin, int n, int layout, int d
       if (gdc_tail_run(ptr(op.x), op.d_w, op.d_scale, op.d_shift, op.d_w_pw, op.d_w_dense, ptr(op.y), n, xd.H * xd.W,
                        op.Cout, 1e-12f, L.tail_ws, st))
         return -1;
-      op.ran_kernel = n <= 2 && op.Cout % 32 == 0 ? "gdc_tail_a_kernel+gdc_tail_b_kernel" : "gdc_tail_kernel";
+      // the form gdc_tail_run dispatched (its three conditions, elementwise.hip)
+      op.ran_kernel = n <= 2 && L.tail_ws && op.Cout % 32 == 0 ? "gdc_tail_a_kernel+gdc_tail_b_kernel"
+                      : n <= 2                                 ? "gdc_tail_kernel<KSPLIT=8>"
+                                                               : "gdc_tail_kernel<KSPLIT=2>";
       break;
     }
     case OP_DWFULL: {
@@ -1559,8 +1566,7 @@ int Net::run_op(const Op& op, Lane& L, const void* xin, int n, int layout, int d
     }
     case OP_LRN: {
       const TensorDesc& xd = tensors[op.x];
-      // tf.nn.lrn defaults: depth_radius 5, bias 1; alpha / beta from inceptionv3.py:95
-      if (lrn_run(ptr(op.x), ptr(op.y), (int64_t)n * xd.H * xd.W, xd.C, 5, 1.f, 1e-4f, 0.75f, st)) return -1;
+      if (lrn_run(ptr(op.x), ptr(op.y), (int64_t)n * xd.H * xd.W, xd.C, LRN_RADIUS, LRN_BIAS, LRN_ALPHA, LRN_BETA, st)) return -1;
       break;
     }
     case OP_UPSAMPLE: {
@@ -1706,6 +1712,14 @@ const char* Net::describe(int i) {
   bnref("bn", op.bn);
   bnref("bn2", op.bn2);
   bnref("pre_bn", op.pre_bn);
+  param("w_pw", op.kind == OP_GDCTAIL ? op.w_pw : -1);
+  param("w_dense", op.kind == OP_GDCTAIL ? op.w_dense : -1);
+  if (op.kind == OP_LRN) {
+    snprintf(b, sizeof(b), " lrn=%d,%.9g,%.9g,%.9g", LRN_RADIUS, (double)LRN_BIAS, (double)LRN_ALPHA, (double)LRN_BETA);
+    s += b;
+  } else {
+    s += " lrn=-";
+  }
   describe_line = s;
   return describe_line.c_str();
 }

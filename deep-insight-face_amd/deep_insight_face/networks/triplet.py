@@ -245,6 +245,8 @@ class DifEmbedder:
         """What every launch hands its kernel (include/dif.h: dif_net_op_describe), one dict per launch of ``op_table()``.
         'x', 'res', 'y', 'y2' are None or dicts {'root': (H, W, C), 'coff', 'oy', 'ox', 'view': (H, W, C)}; 'k' and 'pad' are
         pairs; 'bn', 'bn2', 'pre_bn' are None or (prefix, eps); 'w', 'bias', 'alpha', 'alpha2' parameter names or None;
+        a 'gdctail' launch alone also has 'w_pw' and 'w_dense' (parameter names), an 'lrn' launch alone 'lrn' = (radius, bias,
+        alpha, beta);
         the other numeric keys are ints ('const_alpha' a float), 'kind', 'name', 'act', 'act2', 'pre_act', 'pool' strings.
         Needs no device: it reads the launch list, before or after the net is finalized."""
         rows = []
@@ -267,6 +269,11 @@ class DifEmbedder:
                     d[key] = None if val == '-' else (val.rsplit(',', 1)[0], float(val.rsplit(',', 1)[1]))
                 elif key in ('w', 'bias', 'alpha', 'alpha2'):
                     d[key] = None if val == '-' else val
+                elif key in ('w_pw', 'w_dense', 'lrn'):
+                    if val == '-':                       # keys of one kind only: absent from every other launch's dict
+                        continue
+                    v = val.split(',')
+                    d[key] = (int(v[0]), float(v[1]), float(v[2]), float(v[3])) if key == 'lrn' else val
                 elif key in ('kind', 'name', 'act', 'act2', 'pre_act', 'pool'):
                     d[key] = val
                 elif key == 'const_alpha':

@@ -570,7 +570,11 @@ int dif_net_embed_profile(dif_net* net, const void* x_dev, int n, int layout, in
  *   x, res, y, y2: "-" or nine integers -- the ROOT tensor's H,W,C, then the view window coff,oy,ox and the view's H,W,C;
  *   k=KH,KW stride pad=top,left cin cin_true cout; act act2 pre_act (none relu prelu relu6) const_alpha res_stride y_sub
  *   chw_flatten k_order; pool (max l2 avg) zero_pad ceil; w bias alpha alpha2: parameter NAMES (dif_net_param_info) or "-";
- *   bn bn2 pre_bn: "-" or "<prefix>,<eps>" with parameters <prefix>/gamma, /beta, /moving_mean, /moving_variance.
+ *   bn bn2 pre_bn: "-" or "<prefix>,<eps>" with parameters <prefix>/gamma, /beta, /moving_mean, /moving_variance;
+ *   w_pw w_dense: kind=gdctail's 1x1 convolution [1,1,512,emd] and dense layer [emd,emd] behind the depthwise `w`, parameter
+ *   names; "-" elsewhere;  lrn=radius,bias,alpha,beta: the constants kind=lrn hands lrn_kernel (%.9g); "-" elsewhere.
+ * `kernel` of dif_net_op_info names the form a gdctail launch ran: gdc_tail_kernel<KSPLIT=8>, gdc_tail_kernel<KSPLIT=2> or
+ * gdc_tail_a_kernel+gdc_tail_b_kernel.
  * dif_net_embed_tap: one forward of n in [1, max_batch] images on a single lane (as dif_net_embed_profile) which, right after
  * launch i is enqueued, copies the first n images of the root buffers of that launch's x, res, y and y2 -- the memory the
  * kernel was handed, [n,H,W,C] of the root -- device to device on `stream` into x_tap .. y2_tap (null, or an operand the

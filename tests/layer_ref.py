@@ -11,6 +11,15 @@ Bounds (u = 2^-24; derivations: DESIGN 4l).  With A~ = |scale| conv(|x~|, |w|) +
   Winograd forms     B = (Cin + 16 + 8) u A~w,  A~w = |scale| |A^T| (sum_c |G g G^T| (|B^T| |x~| |B|)) |A| + |shift| + |res|
   split-bf16 tiers   B = (K u + eps_t) A~,  eps_3 = 2^-22 (six products kept), eps_2 = 3 * 2^-16 (three kept)
 y2 = act2(y scale2 + shift2) is held to the same form on A~2 = |scale2| A~ + |shift2|.
+
+The heads and NN4's own layers return (ref, B), B elementwise and stated on what was summed:
+  dwfull             B = (HW + 8) u A~,  A~ = |scale| sum |x| |w| + |beta| + |mean scale|  (the shift by its parts, as dwconv_layer)
+  gdc tail           the bound propagated stage by stage through depthwise, 1x1, dense and the normalisation (gdc_tail_layer)
+  l2norm             B = (D / 2 + 4) u |ref|
+  lrn                B = (P + 12) u |ref|,  P = POWF_ULP
+  pool l2 / avg      B = (k^2 + 4) u |ref|  /  (k^2 + 2) u sum |x| / k^2;  max stays bit-exact
+The worst-case chain of the tail is loose (a float32 run sits at 1e-4 of it), so these also pass the tight gate in units of B
+(gate_in_B): max |y - ref| / B <= 8 max(max |y32 - ref| / B, max 2 u |ref| / B), y32 the same layer in float32.
 """
 import torch
 
@@ -246,18 +255,43 @@ def input_convert(x, layout_nchw, scale, bias, bgr=False, hflip=False):
     return torch.nn.functional.pad(y, (0, 1))
 
 
-def pool_layer(desc, params, x):
-    """maxpool_kernel in 'max' mode, exact: taps outside the map are skipped (-inf), or count as 0 with zero_pad; windows
-    may hang over the bottom / right edge (ceil).  y2 = act2(fma(y, scale2, shift2)) in float32 arithmetic.  x float32."""
-    if desc['pool'] != 'max':
-        raise NotUnderstood('pool mode %r' % desc['pool'])
+def pool_layer(desc, params, x, dtype=torch.float64):
+    """maxpool_kernel -> (y, y2, B).  Taps outside the map are skipped in every mode; windows may hang over the bottom /
+    right edge (ceil).
+    'max': exact (B None), skipped taps are -inf, or count as 0 with zero_pad; y2 = act2(fma(y, scale2, shift2)) in float32.
+    'l2':  sqrt((sum_taps x^2 (1 / k^2)) k^2) -- the divisor is k^2 whatever the window holds, and is multiplied back.
+           B = (k^2 + 4) u |ref|: k^2 fused terms, the two scalings, and the root.
+    'avg': (sum_taps x) (1 / k^2).  B = (k^2 + 2) u sum |x| / k^2.
+    A zero tap adds nothing to either sum, so zero_pad changes nothing there.  x float32 ('max') or any float dtype."""
+    mode = desc['pool']
+    if mode not in ('max', 'l2', 'avg'):
+        raise NotUnderstood('pool mode %r' % mode)
     _whole(desc['x'], 'x')
     k, s = desc['k'][0], desc['stride']
+    if desc['k'][1] != k:
+        raise NotUnderstood('pool window %r' % (desc['k'],))
     pt, pl = desc['pad']
     Ho, Wo = desc['y']['view'][:2]
     n, H, W, C = x.shape
     pb = max((Ho - 1) * s + k - H - pt, 0)
     pr = max((Wo - 1) * s + k - W - pl, 0)
+    if mode != 'max':
+        if desc['y2'] is not None:
+            raise NotUnderstood('a second output on an %s pool: the library builds none' % mode)
+        xp = torch.nn.functional.pad(x.to(dtype), (0, 0, pl, pr, pt, pb))
+        acc = torch.zeros((n, Ho, Wo, C), dtype=dtype, device=x.device)
+        mag = torch.zeros((n, Ho, Wo, C), dtype=torch.float64, device=x.device)
+        for kh in range(k):
+            for kw in range(k):
+                win = xp[:, kh:kh + (Ho - 1) * s + 1:s, kw:kw + (Wo - 1) * s + 1:s, :]
+                acc = acc + (win * win if mode == 'l2' else win)
+                mag = mag + win.abs().to(torch.float64)
+        inv = torch.tensor(1.0 / (k * k), dtype=dtype, device=x.device)            # rounded in the yardstick as in the kernel
+        if mode == 'l2':
+            y = torch.sqrt((acc * inv) * (k * k))
+            return y, None, (k * k + 4) * U * y.abs().to(torch.float64)
+        y = acc * inv
+        return y, None, (k * k + 2) * U * mag / (k * k)
     xp = torch.nn.functional.pad(x, (0, 0, pl, pr, pt, pb), value=0.0 if desc['zero_pad'] else float('-inf'))
     y = None
     for kh in range(k):
@@ -269,7 +303,7 @@ def pool_layer(desc, params, x):
         one = torch.ones(C, dtype=torch.float32, device=x.device)
         s2, sh2 = fold32(params, desc['bn2'], C, x.device) if desc['bn2'] is not None else (one, 0 * one)
         y2 = act((y.to(torch.float64) * s2.to(torch.float64) + sh2.to(torch.float64)).to(torch.float32), desc['act2'])
-    return y, y2
+    return y, y2, None
 
 
 def fold32(params, bn, C, device):
@@ -319,6 +353,121 @@ def dwconv_layer(desc, params, x, dtype=torch.float64):
     return act(v * scale + shift, desc['act']), mag * scale.abs() + parts
 
 
+# ----------------------------------------------------------------------------------------------- heads, LRN
+L2_EPS = 1e-12                # l2norm_kernel / gdc_tail_*: x rsqrt(max(sum x^2, 1e-12)), as the kernels document
+# The maximum ULP error of the device powf.  The toolchain ships no copy of the HIP math-API accuracy table, so this is the
+# OpenCL limit for pow the device library is built to (OpenCL C 3.0, 7.4: pow <= 16 ulp) -- not read off the kernel's output.
+POWF_ULP = 16
+
+
+def _depthwise_full(desc, params, x, dtype):
+    """a = (sum_p x[p, c] w[p, c]) scale + shift over the whole map, and A~ = |scale| sum |x| |w| + |beta| + |mean scale|
+    (float64) -- the shift by the parts it is folded from, as dwconv_layer and for its reason."""
+    _whole(desc['x'], 'x')
+    xt = x.to(dtype)
+    n, H, W, C = xt.shape
+    if desc['k'] != (H, W):
+        raise NotUnderstood('depthwise kernel %r on a %d x %d map' % (desc['k'], H, W))
+    w = _p(params, desc['w'], xt).reshape(H * W, C)
+    scale, shift = fold(params, desc['bn'], None, C, xt)
+    xr = xt.reshape(n, H * W, C)
+    a = (xr * w).sum(1) * scale + shift
+    x64, w64 = xr.to(torch.float64), w.to(torch.float64)
+    s64, sh64 = fold(params, desc['bn'], None, C, x64)
+    parts = sh64.abs()
+    if desc['bn'] is not None:
+        parts = _p(params, desc['bn'][0] + '/beta', x64).abs() + (_p(params, desc['bn'][0] + '/moving_mean', x64) * s64).abs()
+    return a, (x64.abs() * w64.abs()).sum(1) * s64.abs() + parts
+
+
+def dwfull_layer(desc, params, x, dtype=torch.float64):
+    """dwfull_kernel: the depthwise convolution whose kernel is the whole map, + BN -> ([n, 1, 1, C], B = (HW + 8) u A~)."""
+    a, A = _depthwise_full(desc, params, x, dtype)
+    n, C = a.shape
+    HW = desc['k'][0] * desc['k'][1]
+    return a.reshape(n, 1, 1, C), ((HW + 8) * U * A).reshape(n, 1, 1, C)
+
+
+def gdc_tail_layer(desc, params, x, dtype=torch.float64, eps=L2_EPS):
+    """gdc_tail_kernel<KSPLIT> / gdc_tail_a_kernel + gdc_tail_b_kernel: a as dwfull_layer, b = a Wpw (K = 512), o = b Wd
+    (K = E), y = o / sqrt(max(sum o^2, eps)) -> ([n, 1, 1, E], B).  The bound goes stage by stage, in float64:
+        da = (HW + 8) u A~a
+        db = da |Wpw| + 512 u (|a| |Wpw|)
+        do = db |Wd| + E u (|b| |Wd|)
+        B  = do / ||o|| + |y| ||do||_2 / ||o|| + (E / 2 + 4) u |y|
+    (the error of o carried through the division, through the norm -- | ||o + d|| - ||o|| | <= ||d|| --, and the
+    normalisation's own rounding as l2norm_layer).  With every o zero and do zero (a zero dense kernel) B is 0: the clamp
+    makes the row exactly 0.  B is of the float64 run whatever `dtype` computes the chain in."""
+    if desc['kind'] != 'gdctail':
+        raise NotUnderstood('gdc_tail_layer on %r' % desc['kind'])
+    E = desc['cout']
+    HW = desc['k'][0] * desc['k'][1]
+
+    def chain(dt):
+        a, A = _depthwise_full(desc, params, x, dt)
+        wpw = _p(params, desc['w_pw'], a).reshape(-1, E)
+        wd = _p(params, desc['w_dense'], a).reshape(E, E)
+        if wpw.shape[0] != a.shape[1]:
+            raise NotUnderstood('1x1 kernel %s on %d channels' % (tuple(wpw.shape), a.shape[1]))
+        b = a @ wpw
+        o = b @ wd
+        nrm = torch.sqrt((o * o).sum(1, keepdim=True).clamp_min(eps))
+        return a, A, wpw, wd, b, o, nrm, o / nrm
+
+    a, A, wpw, wd, b, o, nrm, y = chain(torch.float64)
+    da = (HW + 8) * U * A
+    db = da @ wpw.abs() + a.shape[1] * U * (a.abs() @ wpw.abs())
+    do = db @ wd.abs() + E * U * (b.abs() @ wd.abs())
+    B = do / nrm + y.abs() * do.norm(dim=1, keepdim=True) / nrm + (E / 2 + 4) * U * y.abs()
+    if dtype != torch.float64:
+        y = chain(dtype)[-1]
+    n = y.shape[0]
+    return y.reshape(n, 1, 1, E), B.reshape(n, 1, 1, E)
+
+
+def l2norm_layer(desc, x, dtype=torch.float64, eps=L2_EPS):
+    """l2norm_kernel: y = x / sqrt(max(sum x^2, eps)) over the D channels of a [n, 1, 1, D] row -> (y, B = (D / 2 + 4) u |ref|):
+    the sum's error enters the root by half, + the root, the reciprocal and the product."""
+    _whole(desc['x'], 'x')
+    if x.shape[1:3] != (1, 1) or x.shape[3] != desc['cout']:
+        raise NotUnderstood('l2norm over %s' % (tuple(x.shape),))
+    D = x.shape[3]
+    x64 = x.to(torch.float64)
+    ref = x64 / torch.sqrt((x64 * x64).sum(3, keepdim=True).clamp_min(eps))
+    B = (D / 2 + 4) * U * ref.abs()
+    if dtype == torch.float64:
+        return ref, B
+    xt = x.to(dtype)
+    return xt / torch.sqrt((xt * xt).sum(3, keepdim=True).clamp_min(eps)), B
+
+
+def lrn_layer(desc, x, dtype=torch.float64):
+    """lrn_kernel: y = x / (bias + alpha sum_{|j - c| <= r, 0 <= j < C} x_j^2) ^ beta with the constants of the describe line
+    (float32 values) -> (y, B = (P + 12) u |ref|): the up-to-11-term sum, the fma, the division and beta times the base's
+    error make the 12, P = POWF_ULP is the device powf's."""
+    _whole(desc['x'], 'x')
+    if desc.get('lrn') is None:
+        raise NotUnderstood('no lrn constants on %r' % desc['name'])
+    r = desc['lrn'][0]
+    bias, alpha, beta = (float(torch.tensor(v, dtype=torch.float32)) for v in desc['lrn'][1:])      # the float32 values the kernel gets
+    if 2 * r + 1 > 11:
+        raise NotUnderstood('lrn radius %d: the bound counts at most 11 terms' % r)
+    C = x.shape[3]
+
+    def run(dt):
+        xt = x.to(dt)
+        sq = torch.nn.functional.pad(xt * xt, (r, r))
+        s = torch.zeros_like(xt)
+        for j in range(2 * r + 1):
+            s = s + sq[..., j:j + C]
+        base = torch.tensor(bias, dtype=dt, device=x.device) + torch.tensor(alpha, dtype=dt, device=x.device) * s
+        return xt / torch.pow(base, torch.tensor(beta, dtype=dt, device=x.device))
+
+    ref = run(torch.float64)
+    B = (POWF_ULP + 12) * U * ref.abs()
+    return (ref if dtype == torch.float64 else run(dtype)), B
+
+
 # ----------------------------------------------------------------------------------------------- gates
 def worst(got, ref, denom):
     """max |got - ref| / denom and where: (ratio, (image, row, column, channel)).  Elements whose bound is 0 must be exact."""
@@ -342,3 +491,13 @@ TIGHT_FACTOR = 8.0
 def tight_limit(y32, ref, A):
     """8 * max(the float32 yardstick's own error on this input, 2 u), relative to A."""
     return TIGHT_FACTOR * max(rel_error(y32, ref, A), 2 * U)
+
+
+def gate_in_B(got, y32, ref, B):
+    """The tight gate in units of B, for the layers whose B is not a multiple of one magnitude:
+    (max |got - ref| / B, 8 max(max |y32 - ref| / B, max 2 u |ref| / B), where the kernel's worst sits)."""
+    r, at = worst(got, ref, B)
+    ry, _ = worst(y32, ref, B)
+    ok = B > 0
+    floor = float((2 * U * ref.abs().to(torch.float64)[ok] / B[ok]).max()) if bool(ok.any()) else 0.0
+    return r, TIGHT_FACTOR * max(ry, floor), at

@@ -5,6 +5,7 @@ read, and every element of every image of what it stored held to the gates:
   hard, per element      |y - ref| <= B (layer_ref.bound_factor x A~), y2 the same; exact layers bit for bit
   tight, per layer       max |y - ref| / A~ <= 8 max(max |y32 - ref| / A~, 2 u)   (f32 and Winograd forms; y32: the float32
                          yardstick on the same input -- the same sum over taps, or the Winograd order of operations)
+                         the fused GDC tail, l2norm and lrn: the same in units of B (layer_ref.gate_in_B)
   untouched forward      every tapped forward's outputs equal embed's, bit for bit
 
 Failures are collected, not raised: the caller asserts on the list, so one run names every failing layer."""
@@ -15,8 +16,6 @@ import torch
 import layer_ref as L
 
 WINO = ('conv_wino_kernel', 'conv_winow_kernel', 'conv_winox_kernel')
-# launches that keep their own head / whole-net tests (the issue's "what stays out"): no per-layer reference here
-STAY_OUT = ('gdctail', 'dwfull', 'l2norm', 'lrn')
 
 
 def kernel_form(kern):
@@ -41,10 +40,12 @@ def _fmt(name, kern, what, ratio, at, extra=''):
     return '%s [%s] %s: ratio %.3g at image %d, pixel (%d, %d), channel %d%s' % (name, kern, what, ratio, at[0], at[1], at[2], at[3], extra)
 
 
-def sweep(model, x, label='', record=None, verbose=False, params=None):
+def sweep(model, x, label='', record=None, verbose=False, params=None, kinds=None, names=None):
     """x: the input batch on the device (uint8 or float32, NHWC).  Returns (failures, kernel labels seen, launches checked).
     record: dict kernel label -> {'hard': (ratio, layer), 'tight': (kernel / yardstick ratio, layer)}, worst kept.
-    params: the reference's parameters, the model's own unless a test hands it others on purpose."""
+    params: the reference's parameters, the model's own unless a test hands it others on purpose.
+    kinds / names: only the launches of these kinds / whose name starts with one of these are tapped and compared (a head
+    case: a few launches of a whole net); the untouched-forward check runs for each of them."""
     params = model.get_weights() if params is None else params
     descs = model.op_describe()
     want_out = [t.clone() for t in _outs(model.embed(x))]
@@ -58,7 +59,22 @@ def sweep(model, x, label='', record=None, verbose=False, params=None):
             if key not in r or ratio > r[key][0]:
                 r[key] = (ratio, layer)
 
+    def gated(name, kern, got, yard, ref, B):
+        """A layer that returns (ref, B): the hard bound per element and the tight gate in units of B."""
+        r, lim, at = L.gate_in_B(got, yard, ref, B)
+        note(kern, 'hard', r, name)
+        note(kern, 'tight', r / (lim / L.TIGHT_FACTOR) if lim > 0 else (0.0 if r == 0 else float('inf')), name)
+        if verbose:
+            print('%s %s [%s]: |y - ref| / B %.4g, tight limit %.4g' % (label, name, kern, r, lim))
+        if not r <= 1.0:
+            fails.append(_fmt(name, kern, '|y - ref| / B', r, at))
+        if not r <= lim:
+            fails.append(_fmt(name, kern, 'tight gate: |y - ref| / B = %.3g, limit %.3g; kernel / yardstick' % (r, lim),
+                              r / (lim / L.TIGHT_FACTOR) if lim > 0 else float('inf'), at))
+
     for i, d in enumerate(descs):
+        if (kinds is not None and d['kind'] not in kinds) or (names is not None and not d['name'].startswith(tuple(names))):
+            continue
         tap = model.tap(x, i)
         name, kern, _ = model.op_table()[i]
         seen.add(kern)
@@ -66,8 +82,6 @@ def sweep(model, x, label='', record=None, verbose=False, params=None):
         if len(got_out) != len(want_out) or not all(torch.equal(a, b) for a, b in zip(got_out, want_out)):
             fails.append('%s [%s]: the tapped forward\'s outputs differ from embed\'s' % (name, kern))
         kind = d['kind']
-        if kind in STAY_OUT:
-            continue
         checked += 1
         try:
             if kind == 'input':
@@ -75,8 +89,29 @@ def sweep(model, x, label='', record=None, verbose=False, params=None):
                 if not torch.equal(tap['y'], ref):
                     r, at = L.worst(tap['y'], ref, torch.zeros_like(ref, dtype=torch.float64))
                     fails.append(_fmt(name, kern, 'not bit-exact', r, at))
+            elif kind == 'maxpool' and d['pool'] != 'max':
+                ref, _, B = L.pool_layer(d, params, tap['x'])
+                r, at = L.worst(L.window(d['y'], tap['y']), ref, B)
+                note(kern + '[' + d['pool'] + ']', 'hard', r, name)
+                if not r <= 1.0:
+                    fails.append(_fmt(name, kern, '%s pool |y - ref| / B' % d['pool'], r, at))
+            elif kind == 'dwfull':
+                ref, B = L.dwfull_layer(d, params, tap['x'])
+                r, at = L.worst(L.window(d['y'], tap['y']), ref, B)
+                note(kern, 'hard', r, name)
+                if not r <= 1.0:
+                    fails.append(_fmt(name, kern, '|y - ref| / B', r, at))
+            elif kind == 'gdctail':
+                ref, B = L.gdc_tail_layer(d, params, tap['x'])
+                gated(name, kern, L.window(d['y'], tap['y']), L.gdc_tail_layer(d, params, tap['x'], torch.float32)[0], ref, B)
+            elif kind == 'l2norm':
+                ref, B = L.l2norm_layer(d, tap['x'])
+                gated(name, kern, L.window(d['y'], tap['y']), L.l2norm_layer(d, tap['x'], torch.float32)[0], ref, B)
+            elif kind == 'lrn':
+                ref, B = L.lrn_layer(d, tap['x'])
+                gated(name, kern, L.window(d['y'], tap['y']), L.lrn_layer(d, tap['x'], torch.float32)[0], ref, B)
             elif kind == 'maxpool':
-                y, y2 = L.pool_layer(d, params, tap['x'])
+                y, y2, _ = L.pool_layer(d, params, tap['x'])
                 for key, ref in (('y', y), ('y2', y2)):
                     if ref is None:
                         continue

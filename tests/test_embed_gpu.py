@@ -645,5 +645,5 @@ def test_gdc_tail_one_and_two_images(cuda):
         np.testing.assert_allclose(got, three[:n], atol=2e-6)
         for _ in range(3):
             assert np.array_equal(model.predict_on_batch(x[:n]), got)
-    assert 'gdc_tail_kernel' in [k for _, k, _, _ in model.profile(torch.from_numpy(x).cuda())]
+    assert 'gdc_tail_kernel<KSPLIT=2>' in [k for _, k, _, _ in model.profile(torch.from_numpy(x).cuda())]
     model.close()

@@ -7,6 +7,9 @@
    a-priori bound (printed: the worst |y32 - ref| / B).
 3. Five planted defects in a float32 layer (2 images, 6 x 10 x 32 -> 64), each of the size a slipped index leaves in ONE
    place, each rejected by a gate of tests/test_layer_taps_gpu.py.
+3b. The heads, LRN and the L2 / average pools (dwfull_layer, gdc_tail_layer, l2norm_layer, lrn_layer, pool_layer): each equals
+   the oracle's pieces in float64 to 2e-15, its float32 yardstick passes both gates, and eight planted one-place defects each
+   break the gate the test names.
 4. For every arch the library builds: each describe line parses, every parameter it names exists with the shape the
    geometry implies, and the launch list is op_table()'s.
 """
@@ -234,7 +237,7 @@ def test_pool_reference_is_the_oracles_pool(zero_pad, ceil):
     else:
         desc = D(T(7, 9, 8), T(4, 5, 8), (3, 3), 2, (1, 1), kind='maxpool', zero_pad=zero_pad, y2=T(4, 5, 8), bn2=('bn2', EPS), act2='relu')
         want = nets.maxpool(x, 3, 2, (1, 1, 1, 1), 0.0 if zero_pad else -np.inf)
-    y, y2 = L.pool_layer(desc, p, torch.from_numpy(x))
+    y, y2, _ = L.pool_layer(desc, p, torch.from_numpy(x))
     assert np.array_equal(y.numpy(), want)
     if not ceil:
         sc = (p['bn2/gamma'] / np.sqrt(p['bn2/moving_variance'] + np.float32(EPS))).astype(np.float32)
@@ -331,6 +334,256 @@ def test_planted_defect_breaks_a_gate(defect):
     assert rel > lim
 
 
+# ------------------------------------------------------------------------------------------------- heads, LRN, L2 / avg pools
+REL64 = 2e-15
+
+
+def _rel(got, want):
+    return float(np.abs(np.asarray(got) - want).max() / max(np.abs(want).max(), 1e-300))
+
+
+def _tail_case(n=3, hw=3, E=40, seed=17):
+    """A GDC tail on a PReLU-like map: desc, float32 parameters, x [n, hw, hw, 512]."""
+    rng = np.random.default_rng(seed + 1000 * hw + E)
+    x = rng.standard_normal((n, hw, hw, 512))
+    x = np.where(x > 0, x, 0.25 * x).astype(np.float32)
+    p = {'head_dw/depthwise_kernel': rng.standard_normal((hw, hw, 512, 1)) / hw,
+         'head_pw/kernel': rng.standard_normal((1, 1, 512, E)) * np.sqrt(1 / 512.),
+         'head_dense/kernel': rng.standard_normal((E, E)) * np.sqrt(1. / E)}
+    p.update(bn_params(rng, 'head_bn2', 512))
+    p = {k: np.asarray(v, np.float32) for k, v in p.items()}
+    desc = D(T(hw, hw, 512), T(1, 1, E), (hw, hw), kind='gdctail', w='head_dw/depthwise_kernel', bn=('head_bn2', EPS),
+             w_pw='head_pw/kernel', w_dense='head_dense/kernel')
+    return desc, p, x
+
+
+def _oracle_tail(x, q, stop=None):
+    """oracle.nets.head_gdc from head_dw on, in x's dtype."""
+    y = np.einsum('nhwc,hwc->nc', x, q['head_dw/depthwise_kernel'][..., 0])[:, None, None, :]
+    y = nets.batchnorm(y, q, 'head_bn2', EPS)
+    if stop == 'dw':
+        return y
+    y = nets.conv2d(y, q['head_pw/kernel'])
+    y = y.reshape(y.shape[0], -1) @ q['head_dense/kernel']
+    return nets.l2_normalize(y)
+
+
+@pytest.mark.parametrize('hw,E', [(1, 8), (3, 40), (2, 136), (7, 512), (3, 1000)])
+def test_tail_references_equal_the_oracles_v2_head(hw, E):
+    """dwfull_layer and gdc_tail_layer against oracle.nets.head_gdc from head_dw on, both in float64; l2norm_layer against
+    oracle.nets.l2_normalize."""
+    desc, p, x = _tail_case(3, hw, E)
+    p64 = nets.cast_params(p, np.float64)
+    y, B = L.gdc_tail_layer(desc, p, torch.from_numpy(x))
+    want = _oracle_tail(x.astype(np.float64), p64)
+    assert tuple(y.shape) == (3, 1, 1, E) and _rel(y.numpy().reshape(3, E), want) <= REL64
+    assert bool((B > 0).all())
+    a, Ba = L.dwfull_layer(dict(desc, kind='dwfull', y=T(1, 1, 512), cout=512), p, torch.from_numpy(x))
+    assert _rel(a.numpy(), _oracle_tail(x.astype(np.float64), p64, 'dw')) <= REL64 and bool((Ba > 0).all())
+    rows = np.random.default_rng(E).standard_normal((3, 1, 1, E)).astype(np.float32)
+    ln, _ = L.l2norm_layer(D(T(1, 1, E), T(1, 1, E), (1, 1), kind='l2norm'), torch.from_numpy(rows))
+    assert _rel(ln.numpy().reshape(3, E), nets.l2_normalize(rows.reshape(3, E).astype(np.float64))) <= REL64
+
+
+NN4_MAPS = [(5, 5, 192), (3, 3, 736)]
+LRN_CONST = (5, 1.0, float('%.9g' % np.float32(1e-4)), 0.75)           # as the describe line prints them
+
+
+@pytest.mark.parametrize('shape', NN4_MAPS)
+def test_nn4_references_equal_the_oracles_pieces(shape):
+    """lrn_layer, and pool_layer in 'l2' and 'avg' mode, against oracle.nets.lrn / _l2pool / avgpool in float64."""
+    h, w, c = shape
+    x = np.random.default_rng(c).standard_normal((2,) + shape).astype(np.float32) * 1.5
+    x64 = x.astype(np.float64)
+    y, B = L.lrn_layer(D(T(*shape), T(*shape), (1, 1), kind='lrn', lrn=LRN_CONST), torch.from_numpy(x))
+    assert _rel(y.numpy(), nets.lrn(x64, 5, 1.0, float(np.float32(1e-4)), 0.75)) <= REL64
+    l2, _, Bl = L.pool_layer(D(T(*shape), T(h // 3, w // 3, c), (3, 3), 3, kind='maxpool', pool='l2'), None, torch.from_numpy(x))
+    assert _rel(l2.numpy(), nets._l2pool(x64)) <= REL64
+    av, _, Ba = L.pool_layer(D(T(*shape), T(h - 2, w - 2, c), (3, 3), 1, kind='maxpool', pool='avg'), None, torch.from_numpy(x))
+    assert _rel(av.numpy(), nets.avgpool(x64, 3, 1)) <= REL64
+    assert bool((B > 0).all() and (Bl > 0).all() and (Ba > 0).all())
+
+
+def _both_gates(label, got, y32, ref, B):
+    r, lim, at = L.gate_in_B(got, y32, ref, B)
+    print('%s: worst |y - ref| / B = %.3g at %s; tight limit %.3g (x %.3g of it)' % (label, r, at, lim, r / lim if lim else float('nan')))
+    return r, lim
+
+
+@pytest.mark.parametrize('hw,E', [(1, 8), (1, 1024), (3, 40), (2, 136), (7, 512), (7, 8), (3, 1000)])
+def test_tail_float32_chain_sits_far_inside_the_worst_case_bound(hw, E):
+    """The float32 chain of the tail (the yardstick, and the oracle's own float32 run) against the float64 reference: the
+    stage-by-stage worst-case bound is loose -- the float32 chains measure 8e-5 .. 4e-4 of it over these shapes -- which is why
+    the tail is also held to the tight gate in units of B."""
+    desc, p, x = _tail_case(3, hw, E)
+    ref, B = L.gdc_tail_layer(desc, p, torch.from_numpy(x))
+    y32, _ = L.gdc_tail_layer(desc, p, torch.from_numpy(x), torch.float32)
+    o32 = torch.from_numpy(_oracle_tail(x, p).astype(np.float32).reshape(3, 1, 1, E))
+    for label, got in (('yardstick', y32), ('float32 oracle', o32)):
+        r, lim = _both_gates('tail HW %d E %d, %s' % (hw * hw, E, label), got, y32, ref, B)
+        assert r <= 1.0 and r <= lim
+        assert r < 2e-3                         # the looseness itself: a float32 chain nowhere near the bound
+
+
+def _np_tail(p, x, ksplit=2, defect=None, prev=None):
+    """The fused tail in float32 NumPy in the kernels' shape: the depthwise sum + BN, two matrix-vector products in `ksplit` K
+    slices added in slice order, the normalisation per image.  `defect` plants one slip; `prev`: what y held before."""
+    f = np.float32
+    n, H, W, C = x.shape
+    E = p['head_pw/kernel'].shape[-1]
+    sc = (p['head_bn2/gamma'] / np.sqrt(p['head_bn2/moving_variance'] + f(EPS))).astype(f)
+    sh = (p['head_bn2/beta'] - p['head_bn2/moving_mean'] * sc).astype(f)
+    a = ((x.reshape(n, H * W, C) * p['head_dw/depthwise_kernel'].reshape(H * W, C)).sum(1, dtype=f) * sc + sh).astype(f)
+
+    def gemv(v, Wm, first):
+        K = Wm.shape[0]
+        kn = K // ksplit
+        parts = np.stack([v[:, s * kn:(s + 1) * kn] @ Wm[s * kn:(s + 1) * kn] for s in range(ksplit)]).astype(f)
+        if first and defect == 'one product dropped from one output of the first gemv':
+            parts[1, 1, 7] -= v[1, 2 * kn - 1] * Wm[2 * kn - 1, 7]          # slice 1's last product, image 1, output 7
+        out = parts[0]
+        for s in range(1, ksplit):
+            out = out + parts[s]
+        return out.astype(f)
+
+    b = gemv(a, p['head_pw/kernel'].reshape(C, E), True)
+    o = gemv(b, p['head_dense/kernel'], False)
+    ss = (o * o).sum(1, dtype=f)
+    if defect == "image 1 normalised with image 0's sum":
+        ss[1] = ss[0]
+    y = (o * (f(1) / np.sqrt(np.maximum(ss, f(1e-12))))[:, None]).astype(f)
+    if defect == 'the last image of an odd batch left stale':
+        y[n - 1] = prev[n - 1]
+    return y.reshape(n, 1, 1, E)
+
+
+TAIL_DEFECTS = ['one product dropped from one output of the first gemv', "image 1 normalised with image 0's sum",
+                'the last image of an odd batch left stale']
+
+
+@pytest.mark.parametrize('defect', [None] + TAIL_DEFECTS)
+def test_tail_planted_defects(defect):
+    """n = 3, HW = 9, E = 40.  The clean float32 emulation passes both gates.  A wrong norm and a stale row break the hard
+    bound by two to three orders; ONE dropped product of 512 moves one b by 1 / 512 of its terms and every output by a 40th
+    of that -- it stays INSIDE the worst-case bound (measured 0.5 x B) and is caught by the tight gate alone, 250 x above
+    its limit (2 000 x the float32 yardstick; the wrong norm 154 x B, the stale row 592 x B)."""
+    desc, p, x = _tail_case(3, 3, 40)
+    ref, B = L.gdc_tail_layer(desc, p, torch.from_numpy(x))
+    y32, _ = L.gdc_tail_layer(desc, p, torch.from_numpy(x), torch.float32)
+    prev = _np_tail(p, x[::-1].copy())                    # the rows an earlier call on other images left in the buffer
+    got = torch.from_numpy(_np_tail(p, x, 2, defect, prev))
+    r, lim = _both_gates('tail, %s' % (defect or 'clean'), got, y32, ref, B)
+    if defect is None:
+        assert r <= 1.0 and r <= lim
+    elif defect.startswith('one product'):
+        assert r > lim                                     # the tight gate; the hard bound alone misses it
+        assert r <= 1.0, 'the hard bound now sees the dropped product too: say so above'
+    else:
+        assert r > 1.0 and r > lim
+
+
+def _np_lrn(x, radius=5, short_last=False):
+    f = np.float32
+    n, H, W, C = x.shape
+    y = np.empty_like(x)
+    for c in range(C):
+        lo, hi = max(c - radius, 0), min(c + radius, C - 1)
+        if short_last and c == C - 1:
+            lo += 1
+        s = (x[..., lo:hi + 1] * x[..., lo:hi + 1]).sum(-1, dtype=f)
+        y[..., c] = x[..., c] / np.power(f(1) + f(1e-4) * s, f(0.75))
+    return y
+
+
+@pytest.mark.parametrize('defect', [None, 'the window of channel C - 1 one short', 'radius 4'])
+def test_lrn_yardstick_and_planted_defects(defect):
+    """2 x 3 x 3 x 24, radius 5, |v| around 1.  A missing term moves the base by alpha v^2 = 1e-4 and the output by 0.75e-4
+    relative: 40 x the hard bound (28 u = 1.7e-6), and further past the tight limit."""
+    rng = np.random.default_rng(24)
+    x = (rng.choice([-1.0, 1.0], (2, 3, 3, 24)) * rng.uniform(0.8, 1.25, (2, 3, 3, 24))).astype(np.float32)
+    desc = D(T(3, 3, 24), T(3, 3, 24), (1, 1), kind='lrn', lrn=LRN_CONST)
+    ref, B = L.lrn_layer(desc, torch.from_numpy(x))
+    y32, _ = L.lrn_layer(desc, torch.from_numpy(x), torch.float32)
+    got = torch.from_numpy(_np_lrn(x, 4 if defect == 'radius 4' else 5, defect is not None and defect.startswith('the window')))
+    r, lim = _both_gates('lrn, %s' % (defect or 'clean'), got, y32, ref, B)
+    ry, _ = _both_gates('lrn yardstick', y32, y32, ref, B)
+    assert ry <= 1.0 and ry <= lim
+    if defect is None:
+        assert r <= 1.0 and r <= lim
+    else:
+        assert r > 1.0 and r > lim
+        bad = ((got.double() - ref).abs() > B)
+        if defect.startswith('the window'):
+            assert bool(bad[..., -1].all()) and not bool(bad[..., :-1].any())          # that channel, and no other
+
+
+def _np_pool(x, k, s, Ho, Wo, mode, defect=None):
+    f = np.float32
+    n, H, W, C = x.shape
+    y = np.zeros((n, Ho, Wo, C), f)
+    for ho in range(Ho):
+        for wo in range(Wo):
+            acc, cnt = np.zeros((n, C), f), 0
+            for kh in range(k):
+                for kw in range(k):
+                    hi, wi = ho * s + kh, wo * s + kw
+                    if hi >= H or wi >= W or (defect == 'one tap skipped' and (ho, wo, kh, kw) == (0, 0, 2, 1)):
+                        continue
+                    cnt += 1
+                    acc += x[:, hi, wi] * x[:, hi, wi] if mode == 'l2' else x[:, hi, wi]
+            back = cnt if defect == 'the divisor k^2 multiplied back by the taps inside the map' else k * k
+            y[:, ho, wo] = np.sqrt((acc * f(1. / (k * k))) * f(back)) if mode == 'l2' else acc * f(1. / (k * k))
+    return y
+
+
+@pytest.mark.parametrize('defect', [None, 'the divisor k^2 multiplied back by the taps inside the map', 'one tap skipped'])
+def test_l2_pool_yardstick_and_planted_defects(defect):
+    """A 5 x 5 map, k 3, stride 3, windows hanging over the bottom / right edge (2 x 2 outputs).  The kernel divides by k^2 and
+    multiplies k^2 back whatever the window holds; a version that multiplies back by the count of taps inside the map is off
+    by sqrt(6 / 9) .. sqrt(4 / 9) on the three edge windows, a skipped tap by about 1 / 18 of the value: both 1e4 x the hard
+    bound (13 u).  The average pool has its float32 run inside its bound on the same map."""
+    x = np.random.default_rng(55).standard_normal((2, 5, 5, 16)).astype(np.float32)
+    desc = D(T(5, 5, 16), T(2, 2, 16), (3, 3), 3, kind='maxpool', pool='l2', ceil=1)
+    ref, _, B = L.pool_layer(desc, None, torch.from_numpy(x))
+    y32, _, _ = L.pool_layer(desc, None, torch.from_numpy(x), torch.float32)
+    got = torch.from_numpy(_np_pool(x, 3, 3, 2, 2, 'l2', defect))
+    r, at = L.worst(got, ref, B)
+    ry, _ = L.worst(y32, ref, B)
+    print('l2 pool, %s: worst |y - ref| / B = %.3g at %s (yardstick %.3g)' % (defect or 'clean', r, at, ry))
+    assert ry <= 1.0
+    if defect is None:
+        assert r <= 1.0
+        da = dict(desc, pool='avg')
+        ra, _, Ba = L.pool_layer(da, None, torch.from_numpy(x))
+        for label, g in (('yardstick', L.pool_layer(da, None, torch.from_numpy(x), torch.float32)[0]), ('emulation', torch.from_numpy(_np_pool(x, 3, 3, 2, 2, 'avg')))):
+            rr, _ = L.worst(g, ra, Ba)
+            print('avg pool %s: worst |y - ref| / B = %.3g' % (label, rr))
+            assert rr <= 1.0
+    else:
+        assert r > 1.0
+        bad = ((got.double() - ref).abs() > B)
+        if defect == 'one tap skipped':
+            assert bool(bad[:, 0, 0].any()) and not bool(bad[:, 0, 1].any() or bad[:, 1].any())
+        else:
+            assert not bool(bad[:, 0, 0].any()) and bool(bad[:, 1, 1].any())
+
+
+@pytest.mark.parametrize('defect', [None, 'the sum taken over the first 64 channels only'])
+def test_l2norm_yardstick_and_planted_defect(defect):
+    """D = 72: one pass of the wave's 64 lanes and a second of 8.  Dropping the second pass leaves the norm short by the last 8
+    channels' share (about 1 / 18 relative): 1e4 x the hard bound (40 u)."""
+    x = np.random.default_rng(72).standard_normal((3, 1, 1, 72)).astype(np.float32)
+    desc = D(T(1, 1, 72), T(1, 1, 72), (1, 1), kind='l2norm')
+    ref, B = L.l2norm_layer(desc, torch.from_numpy(x))
+    y32, _ = L.l2norm_layer(desc, torch.from_numpy(x), torch.float32)
+    ss = (x[..., :64 if defect else 72] ** 2).sum(-1, dtype=np.float32, keepdims=True)
+    got = torch.from_numpy((x * (np.float32(1) / np.sqrt(np.maximum(ss, np.float32(1e-12))))).astype(np.float32))
+    r, lim = _both_gates('l2norm, %s' % (defect or 'clean'), got, y32, ref, B)
+    ry, _ = _both_gates('l2norm yardstick', y32, y32, ref, B)
+    assert ry <= 1.0 and ry <= lim
+    assert (r <= 1.0 and r <= lim) if defect is None else (r > 1.0 and r > lim)
+
+
 # ------------------------------------------------------------------------------------------------- op_describe
 ARCHS = [('resnet', 'v1', 128, (128, 256)), ('resnet', 'v2', 512, (112, 112)), ('resnet', 'v3', 512, (72, 104)),
          ('resnet', 'sv2', 128, (72, 104)), ('vgg16', 'v3', 512, (48, 80)), ('vgg16', 'sv2', 128, (96, 160)),
@@ -340,6 +593,8 @@ ARCHS = [('resnet', 'v1', 128, (128, 256)), ('resnet', 'v2', 512, (112, 112)), (
 KEYS = {'kind', 'name', 'x', 'res', 'y', 'y2', 'k', 'stride', 'pad', 'cin', 'cin_true', 'cout', 'act', 'act2', 'pre_act',
         'const_alpha', 'res_stride', 'y_sub', 'chw_flatten', 'k_order', 'pool', 'zero_pad', 'ceil', 'w', 'bias', 'alpha', 'alpha2',
         'bn', 'bn2', 'pre_bn'}
+# keys of one kind only
+KIND_KEYS = {'gdctail': {'w_pw', 'w_dense'}, 'lrn': {'lrn'}}
 KERNEL_OF = {'input': 'input_convert_kernel', 'maxpool': 'maxpool_kernel', 'dwfull': 'dwfull_kernel', 'l2norm': 'l2norm_kernel',
              'lrn': 'lrn_kernel', 'zero': 'memset', 'upsample': 'upsample2_kernel', 'copy': 'copy_to_view_kernel',
              'dwconv': 'dwconv_kernel', 'gdctail': 'gdc_tail'}
@@ -356,7 +611,7 @@ def test_op_describe_agrees_with_the_parameter_and_launch_tables(arch, head, emd
     assert [r['name'] for r in rows] == [name for name, _, _ in table] and len(rows) > 3
     used = set()
     for r, (_, kern, _) in zip(rows, table):
-        assert set(r) == KEYS, (r['name'], set(r) ^ KEYS)
+        assert set(r) == KEYS | KIND_KEYS.get(r['kind'], set()), (r['name'], set(r) ^ KEYS)
         assert kern.startswith(KERNEL_OF[r['kind']]) if r['kind'] != 'conv' else kern.startswith(('conv_', 'stem')), (r['name'], kern)
         assert r['act'] in ('none', 'relu', 'prelu', 'relu6') and r['pool'] in ('max', 'l2', 'avg')
         for key in ('x', 'res', 'y', 'y2'):
@@ -365,7 +620,7 @@ def test_op_describe_agrees_with_the_parameter_and_launch_tables(arch, head, emd
                 continue
             (rh, rw, rc), (vh, vw, vc) = t['root'], t['view']
             assert 0 <= t['oy'] and t['oy'] + vh <= rh and 0 <= t['ox'] and t['ox'] + vw <= rw and 0 <= t['coff'] and t['coff'] + vc <= rc, (r['name'], key, t)
-        names = [r[k] for k in ('w', 'bias', 'alpha', 'alpha2') if r[k]]
+        names = [r[k] for k in ('w', 'bias', 'alpha', 'alpha2', 'w_pw', 'w_dense') if r.get(k)]
         for k, c in (('bn', r['cout'] if r['kind'] != 'gdctail' else r['cin']), ('bn2', r['cout']), ('pre_bn', r['cin'])):
             if r[k]:
                 assert r[k][1] > 0
@@ -392,6 +647,9 @@ def test_op_describe_agrees_with_the_parameter_and_launch_tables(arch, head, emd
                 assert r['res']['view'][2] == r['cout']
         if r['kind'] == 'dwconv':
             assert spec[r['w']] == (r['k'][0], r['k'][1], r['cin'], 1)
-    unused = sorted(set(spec) - used)
-    # what no describe line names belongs to the fused head tail (its 1x1 and dense kernels): nothing of a convolution
-    assert all(any(r['kind'] == 'gdctail' for r in rows) for _ in unused) and len(unused) <= 2, unused
+        if r['kind'] == 'gdctail':
+            assert spec[r['w_pw']] == (1, 1, 512, r['cout']) and spec[r['w_dense']] == (r['cout'], r['cout'])
+        if r['kind'] == 'lrn':
+            assert r['lrn'] == (5, 1.0, float('%.9g' % np.float32(1e-4)), 0.75)
+    # the fused tail names its 1x1 and dense kernels too: every parameter of the net is named by some launch
+    assert sorted(set(spec) - used) == []

@@ -37,10 +37,37 @@ class Env:
         os.environ.pop(k, None)
 
 
-def case(group, arch, head, emd, hw, n, opts=None, expect=(), absent=(), compute='f32', max_batch=None, name=''):
-    return {'id': '%s-%s-%dx%d-n%d%s' % (group, arch, hw[0], hw[1], n, ('-' + name) if name else ''), 'net': (arch, head, emd, hw),
-            'n': n, 'opts': dict(opts or {}), 'expect': tuple(expect), 'absent': tuple(absent), 'compute': compute,
-            'max_batch': max_batch or n}
+def case(group, arch, head, emd, hw, n, opts=None, expect=(), absent=(), compute='f32', max_batch=None, name='', **more):
+    """more: 'kinds' / 'names' (only these launches are swept), 'exact' ({launch name: the label it must have run}),
+    'every' (every launch of the net must have been checked), 'pools' ({mode: count} of the pool launches checked)."""
+    return dict({'id': '%s-%s-%dx%d-n%d%s' % (group, arch, hw[0], hw[1], n, ('-' + name) if name else ''), 'net': (arch, head, emd, hw),
+                 'n': n, 'opts': dict(opts or {}), 'expect': tuple(expect), 'absent': tuple(absent), 'compute': compute,
+                 'max_batch': max_batch or n}, **more)
+
+
+TAIL_KINDS = ('gdctail', 'dwfull', 'l2norm', 'conv')
+TAIL_NAMES = ('head_', 'norm_', 'embeddings')
+K8, K2, AB_TAIL = 'gdc_tail_kernel<KSPLIT=8>', 'gdc_tail_kernel<KSPLIT=2>', 'gdc_tail_a_kernel+gdc_tail_b_kernel'
+# the backbones that leave a last map of HW pixels
+MAP_OF = {1: ('mobilenet', (32, 32)), '1v': ('vgg16', (32, 32)), 4: ('resnet', (64, 64)), 9: ('resnet', (96, 96)),
+          49: ('mobilenet', (224, 224))}
+
+
+def tail_form(emd, n):
+    """What gdc_tail_run must dispatch (elementwise.hip), or None for the unfused tail (net.hip: build_heads)."""
+    if emd % 8 or emd > 1024:
+        return None
+    if n >= 3:
+        return K2
+    return AB_TAIL if emd % 32 == 0 else K8
+
+
+def tail_case(hw_key, emd, n, max_batch):
+    arch, hw = MAP_OF[hw_key]
+    form = tail_form(emd, n)
+    exact = {'head_tail': form} if form else {'head_dw': 'dwfull_kernel', 'norm_embedding': 'l2norm_kernel'}
+    return case('tail', arch, 'v2', emd, hw, n, expect=() if form else ('conv_',), max_batch=max_batch, name='emd%d-mb%d' % (emd, max_batch),
+                kinds=TAIL_KINDS, names=TAIL_NAMES, exact=exact)
 
 
 def build_cases():
@@ -77,6 +104,26 @@ def build_cases():
         cases.append(case('bf16', 'vgg16', 'v3', 512, (48, 80), 16, None, ('split-bf16', 'patch128+Bdirect', 'patch8x8+Bdirect'), compute=compute,
                           max_batch=37, name=compute))
         cases.append(case('bf16', 'resnet', 'v3', 512, (96, 64), 37, None, ('split-bf16', 'patch128+Bdirect'), compute=compute, max_batch=37, name=compute))
+    # 5. NN4.small2, every launch: lrn_kernel, the L2 / average pools, the concat views and their zero fills
+    for n in (1, 3, 7):
+        cases.append(case('nn4', 'nn4', 'v2', 128, (96, 96), n, expect=('lrn_kernel', 'l2norm_kernel', 'maxpool_kernel', 'memset', 'conv_'), max_batch=7,
+                          every=True, pools={'l2': 3, 'avg': 1, 'max': 6}))
+    # 6. the GDC tail in every form.  Every emd at HW 9; every HW at emd 512 and 136; each form at each of its batch sizes; max_batch
+    # above n (8) in half of the one- and two-image cases.
+    for emd, rows in [(8, [(1, 1), (2, 8), (3, 8)]), (40, [(1, 8), (2, 2), (5, 8)]), (136, [(1, 1), (2, 8), (8, 8)]),
+                      (1000, [(1, 8), (2, 2), (3, 8), (5, 8)]), (32, [(1, 1), (2, 8), (3, 8)]), (512, [(1, 8), (2, 2), (5, 8), (8, 8)]),
+                      (1024, [(1, 1), (2, 8), (3, 8)]), (100, [(1, 1), (3, 8)]), (1032, [(1, 8), (3, 3)])]:
+        cases += [tail_case(9, emd, n, mb) for n, mb in rows]
+    for key, emd, rows in [(1, 512, [(1, 8), (3, 8)]), ('1v', 136, [(2, 8), (5, 8)]), (4, 512, [(2, 2), (8, 8)]), (4, 136, [(1, 8), (3, 8)]),
+                           (49, 512, [(1, 1), (3, 3)]), (49, 136, [(2, 8), (5, 8)])]:
+        cases += [tail_case(key, emd, n, mb) for n, mb in rows]
+    # IResNet-50 at 112 x 112 (a 7 x 7 last map): its own head is one dense layer over the map, not the GDC tail (net.hip), so of
+    # the tail kinds it runs l2norm_kernel at D = 512; the fused tail at HW 49 is MobileNetV2's at 224 x 224 above
+    cases.append(case('tail', 'iresnet50', 'v2', 512, (112, 112), 3, max_batch=129, kinds=TAIL_KINDS, names=TAIL_NAMES,
+                      exact={'norm_embedding': 'l2norm_kernel'}))
+    # 7. the v1 and sv2 heads, every launch: 2 x 2 pools, the whole-map valid convolution, the dense layer behind a BN
+    cases.append(case('heads', 'resnet', 'v1', 128, (112, 112), 5, expect=('maxpool_kernel', 'conv_'), every=True))
+    cases.append(case('heads', 'vgg16', 'sv2', 128, (96, 96), 2, expect=('maxpool_kernel', 'conv_'), every=True))
     return cases
 
 
@@ -89,7 +136,22 @@ def run_case(zoo, c, env, verbose=False):
     m = zoo.net(arch, head, emd, hw, c['max_batch'], compute=c['compute'], streams=1, monkeypatch=env)
     x = torch.from_numpy(zoo.pool(hw, max(c['n'], 40))[:c['n']]).cuda()
     with options(m, **c['opts']):
-        fails, seen, checked = layer_sweep.sweep(m, x, c['id'], RECORD, verbose)
+        fails, seen, checked = layer_sweep.sweep(m, x, c['id'], RECORD, verbose, kinds=c.get('kinds'), names=c.get('names'))
+    descs, table = m.op_describe(), {name: kern for name, kern, _ in m.op_table()}
+    for name, kern in c.get('exact', {}).items():
+        if table.get(name) != kern:
+            fails.append('%s: %s ran %r, this shape and batch dictate %r' % (c['id'], name, table.get(name), kern))
+    if 'kinds' in c:
+        want = sum(d['kind'] in c['kinds'] and d['name'].startswith(c['names']) for d in descs)
+        if checked != want or checked < len(c['exact']):
+            fails.append('%s: %d launches checked, %d match kinds / names' % (c['id'], checked, want))
+        return fails, seen, checked
+    if c.get('every') and checked != len(descs):
+        fails.append('%s: %d launches checked of %d' % (c['id'], checked, len(descs)))
+    for mode, count in c.get('pools', {}).items():
+        got = sum(d['kind'] == 'maxpool' and d['pool'] == mode for d in descs)
+        if got != count:
+            fails.append('%s: %d pools of mode %s in the launch list, %d expected' % (c['id'], got, mode, count))
     for k in c['expect']:
         if not any(k in s for s in seen):
             fails.append('%s: no launch ran %s (ran: %s)' % (c['id'], k, sorted(seen)))
@@ -117,6 +179,60 @@ def test_every_launch_against_its_float64_layer(zoo, monkeypatch, c):
     assert not fails, '%d failures\n' % len(fails) + '\n'.join(fails)
 
 
+def test_nn4_lrn_inputs_are_large_enough_to_see_a_short_window(zoo, monkeypatch):
+    """A window one channel short moves an LRN output by 0.75e-4 v^2 relative (v: the missing value): against the bound's
+    28 u = 1.7e-6 that shows for |v| above 0.15.  The synthetic weights give the maps tapped at lrn_1 and lrn_2 a median
+    nonzero |x| of 0.64 and 0.92 (the float32 oracle on these inputs): no rescaling of bn1 / bn3 is needed, and this holds it."""
+    m = zoo.net('nn4', 'v2', 128, (96, 96), 7, streams=1, monkeypatch=monkeypatch)
+    x = torch.from_numpy(zoo.pool((96, 96), 40)[:7]).cuda()
+    names = [d['name'] for d in m.op_describe()]
+    for layer in ('lrn_1', 'lrn_2'):
+        t = m.tap(x, names.index(layer))['x']
+        med = float(t[t != 0].abs().median())
+        print('%s: median nonzero |x| %.3f, %.0f %% nonzero, max %.2f' % (layer, med, 100 * float((t != 0).float().mean()), float(t.abs().max())))
+        assert med >= 0.5
+
+
+def _fresh(arch, emd, hw, max_batch, env, zero_dense=False):
+    from deep_insight_face.networks.triplet import DifEmbedder
+    env.setenv('DIF_STREAMS', '1')
+    m = DifEmbedder(arch, 'v2', emd, hw + (3,), max_batch=max_batch).init_synthetic(2024)
+    if zero_dense:
+        p = m.get_weights()
+        p['head_dense/kernel'] = 0 * p['head_dense/kernel']
+        m.set_weights(p)
+    m.set_input_transform(scale=1 / 255.)
+    m._finalize()
+    env.delenv('DIF_STREAMS')
+    return m
+
+
+@pytest.mark.parametrize('emd,n,label', [(40, 2, K8), (512, 2, AB_TAIL), (512, 3, K2), (100, 3, 'l2norm_kernel')])
+def test_zero_dense_kernel_gives_exact_zero_rows(zoo, monkeypatch, emd, n, label):
+    """head_dense/kernel all zero: every o is 0, sum o^2 = 0, and max(sum, eps) makes the row 0 * 1e6 = 0.0 exactly -- in each
+    of the three fused forms and in l2norm_kernel -- with nothing non-finite.  Ordinary arithmetic: no fault is provoked."""
+    m = _fresh('vgg16', emd, (32, 32), 3, monkeypatch, zero_dense=True)
+    try:
+        y = m.embed(torch.from_numpy(zoo.pool((32, 32), 40)[:n]).cuda())
+        table = {name: kern for name, kern, _ in m.op_table()}
+        assert table['head_tail' if emd % 8 == 0 else 'norm_embedding'] == label, table
+        assert y.shape == (n, emd) and bool(torch.isfinite(y).all()) and bool((y == 0).all())
+    finally:
+        m.close()
+
+
+def test_two_image_tail_twice_is_bit_identical(zoo, monkeypatch):
+    """gdc_tail_a_kernel + gdc_tail_b_kernel draw a ticket per block; the last taker clears it.  Two consecutive calls at two
+    images give the same bits (a ticket left above zero would let an earlier block normalise half-written rows), and rows of
+    unit norm."""
+    m = zoo.net('resnet', 'v2', 512, (96, 96), 2, streams=1, monkeypatch=monkeypatch)
+    x = torch.from_numpy(zoo.pool((96, 96), 40)[:2]).cuda()
+    a = m.embed(x).clone()
+    b = m.embed(x).clone()
+    assert dict((name, kern) for name, kern, _ in m.op_table())['head_tail'] == AB_TAIL
+    assert torch.equal(a, b) and bool(((a.double() ** 2).sum(1) - 1).abs().max() < 1e-6)
+
+
 def test_sweep_is_live_on_the_device(zoo, monkeypatch):
     """The comparison on the device has teeth: a reference handed ONE bias value off by 2^-10 -- the layer's outputs are of
     order 1, and the kernels run on the true weights -- fails that layer, at that channel, and no other layer; the same sweep
@@ -130,6 +246,23 @@ def test_sweep_is_live_on_the_device(zoo, monkeypatch):
     assert fails and all(f.startswith('block3_conv2 ') and 'channel 17' in f for f in fails), fails
 
 
+def test_tail_sweep_is_live_on_the_device(zoo, monkeypatch):
+    """The tail's gates have teeth on the device too: a reference handed the 1x1 kernel with ONE weight zeroed -- the largest
+    product of output 7 of image 0, what a kernel that dropped that product would have computed -- fails head_tail and
+    nothing else; the hard bound alone would pass it (tests/test_layer_ref.py), the tight gate is what fails."""
+    m = zoo.net('resnet', 'v2', 40, (96, 96), 8, streams=1, monkeypatch=monkeypatch)
+    x = torch.from_numpy(zoo.pool((96, 96), 40)[:3]).cuda()
+    descs = m.op_describe()
+    i = [d['name'] for d in descs].index('head_tail')
+    p = {k: v.copy() for k, v in m.get_weights().items()}
+    a, _ = layer_sweep.L._depthwise_full(descs[i], p, m.tap(x, i)['x'], torch.float64)
+    k = int((a[0].cpu() * torch.from_numpy(p['head_pw/kernel'][0, 0, :, 7]).double()).abs().argmax())
+    p['head_pw/kernel'][0, 0, k, 7] = 0
+    fails, _, checked = layer_sweep.sweep(m, x, 'live', None, params=p, kinds=TAIL_KINDS, names=TAIL_NAMES)
+    print('\n'.join(fails))
+    assert checked == 2 and fails and all(f.startswith('head_tail ') for f in fails) and any('tight gate' in f for f in fails), fails
+
+
 # every family the cases are there for (the issue's list); a label matches by containing the text
 FAMILIES = ['conv_mt_kernel<16x16,pointwise,4 waves>', 'conv_mt_kernel<16x16,gather,8 waves>', 'conv_mt_kernel<16x16,pointwise,preact,16 waves>',
             'conv_sk_kernel', 'conv_skp_kernel', '+reduce', 'conv_igemm_kernel<128x32', 'conv_igemm_kernel<64x64,gather>', 'stem3x3_kernel',
@@ -137,7 +270,8 @@ FAMILIES = ['conv_mt_kernel<16x16,pointwise,4 waves>', 'conv_mt_kernel<16x16,gat
             'patch128+Bdirect', 'patch168+Bdirect', 'conv_wino_kernel<F(2x2,3x3),32 tiles x 64>', 'conv_wino_kernel<F(2x2,3x3),64 tiles x 64>',
             'conv_winow_kernel<F(2x2,3x3),32 tiles x 64>', 'conv_winow_kernel<F(2x2,3x3),64 tiles x 64>',
             'conv_winox_kernel<F(2x2,3x3),32 tiles x 64,odd>', 'conv_winox_kernel<F(2x2,3x3),32 tiles x 64,ysub>',
-            'conv_igemm_kernel[split-bf16]', 'input_convert_kernel', 'maxpool_kernel', 'dwconv_kernel', 'upsample2_kernel', 'copy_to_view_kernel']
+            'conv_igemm_kernel[split-bf16]', 'input_convert_kernel', 'maxpool_kernel', 'dwconv_kernel', 'upsample2_kernel', 'copy_to_view_kernel',
+            K8, K2, AB_TAIL, 'dwfull_kernel', 'l2norm_kernel', 'lrn_kernel', 'memset']
 # what the cases ran on the MI355X (split-K factors left out: layer_sweep.family); conv_tn_kernel's third patch size, patch256,
 # is reached by ResNet50V2 64 x 96
 OBSERVED = ['conv_bdp_kernel<64x64,patch168+Bdirect>', 'conv_bdp_kernel<64x64,patch8x8+Bdirect>',
@@ -163,7 +297,8 @@ OBSERVED = ['conv_bdp_kernel<64x64,patch168+Bdirect>', 'conv_bdp_kernel<64x64,pa
             'conv_wino_kernel<F(2x2,3x3),64 tiles x 64>', 'conv_winow_kernel<F(2x2,3x3),32 tiles x 64>',
             'conv_winow_kernel<F(2x2,3x3),64 tiles x 64>', 'conv_winox_kernel<F(2x2,3x3),32 tiles x 64,odd>',
             'conv_winox_kernel<F(2x2,3x3),32 tiles x 64,ysub>', 'copy_to_view_kernel', 'dwconv_kernel', 'input_convert_kernel',
-            'l2norm_kernel', 'maxpool_kernel', 'stem3x3_kernel', 'stem_mfma_kernel', 'upsample2_kernel']
+            'l2norm_kernel', 'maxpool_kernel', 'stem3x3_kernel', 'stem_mfma_kernel', 'upsample2_kernel',
+            'dwfull_kernel', K8, K2, AB_TAIL, 'lrn_kernel', 'memset']
 
 
 def test_union_of_kernel_labels():

@@ -5,7 +5,9 @@ figures and where they occurred.
 
 Per kernel label (op_table()'s `family<tile, operand form>`):
   hard   worst |y - ref| / B over every element of every image of every layer the form ran (B: the a-priori bound)
-  tight  worst (max |y - ref| / A~) / max(max |y32 - ref| / A~, 2 u): the kernel against the float32 yardstick (gate: 8)
+  tight  worst (max |y - ref| / A~) / max(max |y32 - ref| / A~, 2 u): the kernel against the float32 yardstick (gate: 8);
+         for the GDC tail, l2norm_kernel and lrn_kernel the same in units of B.  The L2 / average pools are listed as
+         maxpool_kernel[l2] / maxpool_kernel[avg] (hard only; 'max' mode is bit-exact and has no row).
 Needs the MI355X.  DESIGN 4l holds the table this writes.
 """
 import json
