@@ -100,7 +100,7 @@ int dif_gallery_destroy(dif_gallery* h) {
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
                   (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min, (void*)g.cluster_parent,
-                  (void*)g.cluster_bad, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins})
+                  (void*)g.cluster_bad, (void*)g.dbscan_degree, (void*)g.dbscan_anchor, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -246,7 +246,7 @@ int dif_gallery_set_option(dif_gallery* h, const char* key, int value) {
     return 0;
   }
   if (std::string(key) == "cluster_round") {
-    // probes per round of dif_gallery_cluster (0: a sixteenth of the rows, at least 2048).  Same answers: tests force several rounds
+    // probes per round of dif_gallery_cluster and dif_gallery_dbscan (0: a sixteenth of the rows, at least 2048).  Same answers: tests force several rounds
     if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'cluster_round' takes 0 or a multiple of 128");
     h->g.cluster_round = value;
     return 0;
@@ -405,6 +405,19 @@ int dif_gallery_cluster(dif_gallery* h, int metric, float tolerance, int64_t fir
   if (!n_clusters_dev || (g.n > 0 && !labels_out_dev)) return set_error("dif_gallery_cluster: null pointer");
   if (g.n >= 0x7fffffffLL) return set_error("dif_gallery_cluster: at most 2^31-1 rows");
   return cluster_run(&h->g, metric, tolerance, first_row, labels_in_dev, labels_out_dev, n_clusters_dev, (hipStream_t)stream);
+}
+
+int dif_gallery_dbscan(dif_gallery* h, int metric, float tolerance, int min_samples, int64_t* labels_out_dev,
+                       int32_t* degree_out_dev, int64_t* counts_dev, void* stream) {
+  if (!h) return set_error("dif_gallery_dbscan: null handle");
+  if (check_metric(metric)) return -1;
+  if (tolerance != tolerance) return set_error("dif_gallery_dbscan: the tolerance is NaN");
+  if (min_samples < 1) return set_error("dif_gallery_dbscan: min_samples must be at least 1 (got %d)", min_samples);
+  const Gallery& g = h->g;
+  if (g.d % 32 != 0) return set_error("dif_gallery_dbscan: embedding size must be a multiple of 32 (got %d)", g.d);
+  if (!counts_dev || (g.n > 0 && !labels_out_dev)) return set_error("dif_gallery_dbscan: null pointer");
+  if (g.n >= 0x7fffffffLL) return set_error("dif_gallery_dbscan: at most 2^31-1 rows");
+  return dbscan_run(&h->g, metric, tolerance, min_samples, labels_out_dev, degree_out_dev, counts_dev, (hipStream_t)stream);
 }
 
 int dif_match_roc(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* probe_labels_dev,

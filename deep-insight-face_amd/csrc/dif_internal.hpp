@@ -77,6 +77,12 @@ struct Gallery {
   size_t cluster_parent_cap = 0;             // ... in rows
   int* cluster_bad = nullptr;
   int cluster_round = 0;                     // "cluster_round": probes per round of dif_gallery_cluster (0: a sixteenth of the rows, at least 2048)
+  // dif_gallery_dbscan (csrc/match_within.hip) shares the census, its thresholds and cluster_parent (stream-ordered calls) and
+  // adds, per row, the number of rows within the tolerance and the nearest core row; each grows against a capacity of its own
+  int* dbscan_degree = nullptr;
+  size_t dbscan_degree_cap = 0;              // ... in rows
+  unsigned long long* dbscan_anchor = nullptr;   // float bits of the distance << 32 | core row, ~0: none
+  size_t dbscan_anchor_cap = 0;              // ... in rows
   // dif_match_roc's workspace (csrc/match_roc.hip), its own; every buffer grows against a capacity of its own
   unsigned* roc_mask = nullptr;              // [gallery tile][probe][4]: the 128-bit mask of the borderline rows
   size_t roc_mask_cap = 0;                   // ... in masks of 16 bytes
@@ -105,6 +111,8 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
 int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
 int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
                 int64_t* n_clusters, hipStream_t st);
+int dbscan_run(Gallery* g, int metric, float tolerance, int min_samples, int64_t* labels_out, int* degree_out, int64_t* counts,
+               hipStream_t st);
 int roc_run(Gallery* g, const float* probes, int B, int metric, const int64_t* probe_labels, const int64_t* row_labels,
             const int64_t* first_row, const float* thresholds, int nT, int64_t* accept_out, int64_t* totals_out, hipStream_t st);
 int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D, int metric, float* out,

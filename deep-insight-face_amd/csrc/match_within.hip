@@ -1,7 +1,8 @@
 // Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), the rank of
 // one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel), and the k nearest rows in order
 // (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), and the connected components
-// of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find).
+// of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find),
+// and density clustering with noise on the same edges (dif_gallery_dbscan; its section starts at dbscan_init_kernel).
 // hipcc-flags: -ffp-contract=off
 // (the resolve stage restates the reference's float32 operations one by one, as match.hip's re-rank does)
 //
@@ -934,6 +935,218 @@ int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, cons
   }
   hipLaunchKernelGGL(cluster_flatten_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, n, g->index_base, g->cluster_bad,
                      labels_out, n_clusters);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Density clustering with noise (dif_gallery_dbscan): DBSCAN on the edge set of dif_gallery_cluster.
+//   E = {(i, j): j < i and distance(rows[i][None, :], rows[j][None, :], metric) <= t}      row i is the probe; no self pairs
+//   degree[i] = 1 + edges of E that contain i;  core[i] = degree[i] >= min_samples
+//   clusters  = connected components of (core rows, edges of E between two core rows);  label = index_base + smallest row
+//   a non-core row with a core neighbour takes the label of the NEAREST one (the edge's float32 value, ties to the lower row)
+//   every other row is noise: label -1
+// Two sweeps of the lower triangle with cluster_run's round loop; every edge is seen exactly once per sweep, by its probe i:
+//   dbscan_init_kernel     parent[i] = i, degree[i] = 1, anchor[i] = ~0, counts = {0, 0}
+//   degree sweep, per round: within_prep_kernel, within_census_kernel (both unchanged), dbscan_degree_kernel: the walk of
+//                          cluster_resolve_kernel; an edge adds 1 to degree[i] (summed per wave first) and to degree[j]
+//   link sweep, per round: the census again (kept when one round covers the gallery: same probes, same thresholds), then
+//                          dbscan_link_kernel: the same walk, the same ref_distance values, and per edge
+//                            both ends core         cl_unite(i, j)
+//                            one end core (c), b    atomicMin(&anchor[b], float_bits(d) << 32 | c)
+//                            neither                nothing
+//   dbscan_flatten_kernel  core: index_base + cl_find(i); anchored: index_base + cl_find(anchor & 0xffffffff); else -1;
+//                          counts[0] = core rows that are roots, counts[1] = noise rows: one integer atomicAdd per block each
+// Why the result is a function of the edge set alone.  degree is a sum of integer atomicAdds: order-free, and complete when
+// the degree sweep's last kernel has ended, which is before the first link kernel reads it (one stream).  So `core` is fixed
+// throughout the link sweep.  Unions happen among core rows only, parent[x] <= x still holds, and facts (a)-(c) above carry
+// over word for word: a core row's root is the smallest row of its core component.  A non-core row is never hooked and never
+// a hook's target: it stays its own root and no core row's path passes through it.  anchor[b] is the minimum over a SET of
+// 64-bit words, one per (edge, core end): a minimum does not depend on the order its operands arrive in, nor on which thread
+// brings them.  Both metrics only give distances >= +0 (a pairwise sum of squares; acos(.) / pi), so the float's bit pattern
+// orders like its value and the word orders by (distance, row): the nearest core neighbour, exact ties to the lower row.
+// d is ref_distance's value, the same bits in both sweeps (the same operands in the same order).  min_samples = 1 makes every
+// row core: the labels are dif_gallery_cluster's and nothing is noise.
+constexpr unsigned long long DBSCAN_NONE = ~0ull;             // no core neighbour: above every anchor word (a row is < 2^31)
+
+__global__ __launch_bounds__(256) void dbscan_init_kernel(int* __restrict__ parent, int* __restrict__ degree,
+                                                          unsigned long long* __restrict__ anchor, int64_t G,
+                                                          int64_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < 2) counts[i] = 0;
+  if (i >= G) return;
+  parent[i] = (int)i;
+  degree[i] = 1;                                              // the row itself, whatever distance(i, i) evaluates to
+  anchor[i] = DBSCAN_NONE;
+}
+
+// The walk of cluster_resolve_kernel: probe i's census words in ascending tile order up to i's own tile; every tile with a
+// sure or a borderline row (every tile for a probe outside the bound's validity) is evaluated row by row, a wave per row
+// j < i, and lane 0 of that wave calls edge(j, d) where d <= t.  Block-uniform control flow; a wave owns its rows.
+template <class F>
+__device__ __forceinline__ void dbscan_walk(const unsigned short* __restrict__ census, int B, const f32x4* __restrict__ thr,
+                                            const float* __restrict__ gallery, int64_t i, int D, int metric, float t,
+                                            int clamp, const SumPlan& plan, float (*scratch)[NP_SCRATCH],
+                                            unsigned short* s_word, F&& edge) {
+  constexpr int NT = 64 * WITHIN_NW;
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* q = gallery + i * D;
+  const int64_t gtiles = i / WITHIN_BM + 1;                   // up to the probe's own tile
+  const bool all = thr[p][3] != 0.f;
+  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
+    s_word[tid] = w;
+    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
+    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
+    for (int j = 0; j < nw; ++j) {
+      if (!(all || s_word[j] != 0)) continue;
+      const int64_t g0 = (t0 + j) * WITHIN_BM;
+      const int rows = i - g0 < WITHIN_BM ? (int)(i - g0) : WITHIN_BM;   // rows j < i only: no self pair
+      for (int r = wave; r < rows; r += WITHIN_NW) {
+        float d;
+        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+        if (lane == 0 && d <= t) edge((int)(g0 + r), d);      // NaN: not an edge
+      }
+    }
+    __syncthreads();                                          // s_word is rewritten by the next round
+  }
+}
+
+// One block per probe i = p0 + blockIdx.x; `census` rows are B words apart and cover tiles 0 .. (p0 + B - 1) / 128.
+__global__ __launch_bounds__(64 * WITHIN_NW) void dbscan_degree_kernel(const unsigned short* __restrict__ census, int B,
+                                                                     const f32x4* __restrict__ thr,
+                                                                     const float* __restrict__ gallery, int64_t p0, int D,
+                                                                     int metric, float t, int clamp, const SumPlan plan,
+                                                                     int* __restrict__ degree) {
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned short s_word[64 * WITHIN_NW];
+  const int64_t i = p0 + blockIdx.x;
+  int mine = 0;                                               // lane 0: edges this wave found for probe i
+  dbscan_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word, [&](int j, float) {
+    ++mine;
+    atomicAdd(degree + j, 1);                                 // integer: order-free
+  });
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(degree + i, mine);
+}
+
+__global__ __launch_bounds__(64 * WITHIN_NW) void dbscan_link_kernel(const unsigned short* __restrict__ census, int B,
+                                                                   const f32x4* __restrict__ thr,
+                                                                   const float* __restrict__ gallery, int64_t p0, int D,
+                                                                   int metric, float t, int clamp, const SumPlan plan,
+                                                                   int min_samples, const int* __restrict__ degree,
+                                                                   int* __restrict__ parent,
+                                                                   unsigned long long* __restrict__ anchor) {
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned short s_word[64 * WITHIN_NW];
+  const int64_t i = p0 + blockIdx.x;
+  const bool core_i = degree[i] >= min_samples;               // (final: the degree sweep ended before this kernel began)
+  unsigned long long best = DBSCAN_NONE;                      // lane 0: the nearest core row this wave found for a non-core i
+  dbscan_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word, [&](int j, float d) {
+    const bool core_j = degree[j] >= min_samples;
+    const unsigned long long hi = (unsigned long long)__builtin_bit_cast(unsigned, d) << 32;   // d >= +0: ordered like d
+    if (core_i && core_j) {
+      cl_unite(parent, (int)i, j);
+    } else if (core_i) {
+      atomicMin(anchor + j, hi | (unsigned)i);                // a minimum over a set: order-free
+    } else if (core_j) {
+      const unsigned long long w = hi | (unsigned)j;
+      best = w < best ? w : best;
+    }
+  });
+  if ((threadIdx.x & 63) == 0 && best != DBSCAN_NONE) atomicMin(anchor + i, best);
+}
+
+__global__ __launch_bounds__(256) void dbscan_flatten_kernel(int* __restrict__ parent, const int* __restrict__ degree,
+                                                             const unsigned long long* __restrict__ anchor, int64_t G,
+                                                             int min_samples, int64_t index_base,
+                                                             int64_t* __restrict__ labels_out, int* __restrict__ degree_out,
+                                                             int64_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool is_root = false, is_noise = false;
+  if (i < G) {
+    const int deg = degree[i];
+    const unsigned long long a = anchor[i];
+    int64_t label = -1;                                       // noise, whatever index_base is
+    if (deg >= min_samples) {
+      const int root = cl_find<false>(parent, (int)i);
+      is_root = root == (int)i;
+      label = index_base + root;
+    } else if (a != DBSCAN_NONE) {
+      label = index_base + cl_find<false>(parent, (int)(a & 0xffffffffull));
+    } else {
+      is_noise = true;
+    }
+    labels_out[i] = label;
+    if (degree_out) degree_out[i] = deg;
+  }
+  const int roots = __syncthreads_count(is_root), noise = __syncthreads_count(is_noise);
+  if (threadIdx.x != 0) return;
+  if (roots) atomicAdd(reinterpret_cast<unsigned long long*>(counts), (unsigned long long)roots);       // integer: order-free
+  if (noise) atomicAdd(reinterpret_cast<unsigned long long*>(counts + 1), (unsigned long long)noise);
+}
+
+int dbscan_run(Gallery* g, int metric, float tolerance, int min_samples, int64_t* labels_out, int* degree_out, int64_t* counts,
+               hipStream_t st) {
+  const int64_t n = g->n;
+  if (n <= 0) {
+    DIF_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
+    return 0;
+  }
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  const int clamp = g->clamp_nan ? 1 : 0;
+  const int64_t gtiles = (n + WITHIN_BM - 1) / WITHIN_BM;
+  // probes per round: cluster_run's rule ("cluster_round")
+  int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
+  if (per < 128) per = 128;
+  int64_t want = g->cluster_round;
+  if (want <= 0) {
+    want = ((n + 15) / 16 + 127) / 128 * 128;
+    if (want < 2048) want = 2048;
+  }
+  if (want < per) per = want;
+  const size_t need_t = (size_t)(per < n ? per : n), need_c = (size_t)gtiles * need_t;
+  if (need_c > g->within_census_cap || need_t > g->within_thr_cap || (size_t)n > g->cluster_parent_cap ||
+      (size_t)n > g->dbscan_degree_cap || (size_t)n > g->dbscan_anchor_cap) {
+    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
+    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
+    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
+    if (grow(&g->cluster_parent, &g->cluster_parent_cap, (size_t)n, sizeof(int))) return -1;
+    if (grow(&g->dbscan_degree, &g->dbscan_degree_cap, (size_t)n, sizeof(int))) return -1;
+    if (grow(&g->dbscan_anchor, &g->dbscan_anchor_cap, (size_t)n, sizeof(unsigned long long))) return -1;
+  }
+  const unsigned nblk = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(dbscan_init_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, g->dbscan_degree, g->dbscan_anchor, n,
+                     counts);
+  DIF_HIP(hipGetLastError());
+  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
+  const bool one_round = per >= n;
+  for (int link = 0; link < 2; ++link) {
+    for (int64_t b0 = 0; b0 < n; b0 += per) {
+      const int nb = (int)(n - b0 < per ? n - b0 : per);
+      const float* pr = g->rows + b0 * g->d;
+      if (!(link && one_round)) {                             // one round: the degree sweep's census is the link sweep's
+        hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
+                           g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
+        DIF_HIP(hipGetLastError());
+        const int64_t limit = b0 + nb;                        // the triangle: no probe of this round looks past its last row
+        const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st, limit); });
+        if (rc) return rc;
+      }
+      if (!link) {
+        hipLaunchKernelGGL(dbscan_degree_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, nb,
+                           reinterpret_cast<const f32x4*>(g->within_thr), g->rows, b0, g->d, metric, tolerance, clamp, plan,
+                           g->dbscan_degree);
+      } else {
+        hipLaunchKernelGGL(dbscan_link_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, nb,
+                           reinterpret_cast<const f32x4*>(g->within_thr), g->rows, b0, g->d, metric, tolerance, clamp, plan,
+                           min_samples, g->dbscan_degree, g->cluster_parent, g->dbscan_anchor);
+      }
+      DIF_HIP(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(dbscan_flatten_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, g->dbscan_degree, g->dbscan_anchor,
+                     n, min_samples, g->index_base, labels_out, degree_out, counts);
   DIF_HIP(hipGetLastError());
   return 0;
 }

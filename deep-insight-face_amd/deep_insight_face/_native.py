@@ -67,6 +67,7 @@ SIGNATURES = {
     'dif_gallery_set_option': (c_int, [c_void_p, c_char_p, c_int]),
     'dif_gallery_get_stat': (c_int, [c_void_p, c_char_p, P(c_int64), c_void_p]),
     'dif_gallery_cluster': (c_int, [c_void_p, c_int, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dif_gallery_dbscan': (c_int, [c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dif_match': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dif_match_within': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dif_match_rank': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -39,6 +39,19 @@ class FrameFaces(typing.NamedTuple):
         from .. import oneshot
         return oneshot.cluster(self.emb, tolerance, distance_metric)[0]
 
+    def dbscan(self, tolerance, min_samples: int = 3, distance_metric: int = 1) -> torch.Tensor:
+        """The distinct people of the batch with false detections set apart: labels [M] int64 on the device from
+        ``oneshot.Gallery.dbscan`` on the M embeddings.  A face with at least ``min_samples`` faces (itself included) within
+        ``tolerance`` is a core face; ``labels[i]`` = the smallest core row of i's cluster, a face that only lies next to a
+        core face takes the nearest one's label and bridges nothing, and every other face is -1 (noise).  ``M == 0`` gives an
+        empty tensor."""
+        if self.emb is None:
+            raise ValueError('FrameFaces.dbscan needs the embeddings (embed_and_match, or a pipeline\'s faces())')
+        if self.emb.shape[0] == 0:
+            return torch.empty((0,), dtype=torch.int64, device=self.emb.device)
+        from .. import oneshot
+        return oneshot.dbscan(self.emb, tolerance, min_samples, distance_metric)[0]
+
 
 def _tensor(x):
     return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))

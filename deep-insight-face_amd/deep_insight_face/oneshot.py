@@ -140,7 +140,7 @@ class Gallery:
         beyond +-1); the default 0 reports NaN like the reference.  The arg-min is unaffected.
         'topk_seed': tiles of 128 rows the seed stage of `topk` evaluates per probe -- 0 (default): k of them; same results
         for every value (include/dif.h).
-        'cluster_round': probes per round of `cluster`, a multiple of 128 -- 0 (default): a sixteenth of the rows, at least 2048; same
+        'cluster_round': probes per round of `cluster` and `dbscan`, a multiple of 128 -- 0 (default): a sixteenth of the rows, at least 2048; same
         results for every value (include/dif.h).
         'roc_round': probes per round of `roc`, a multiple of 128 -- 0 (default): what its workspace allows; same results for
         every value (include/dif.h).
@@ -435,6 +435,59 @@ class Gallery:
         self.cluster_into(tolerance, distance_metric, out, n, first_row, prev)
         return out, n
 
+    def dbscan_into(self, tolerance, min_samples, distance_metric, labels, degree, counts):
+        """Allocation-free form of `dbscan`: results written into the caller's CUDA tensors labels [G] int64, degree [G] int32
+        (or None: not wanted) and counts [2] int64."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        tolerance = float(tolerance)
+        if tolerance != tolerance:
+            raise ValueError('dbscan: the tolerance is NaN')
+        min_samples = int(min_samples)
+        if min_samples < 1:
+            raise ValueError('dbscan: min_samples must be at least 1, got %d' % min_samples)
+        G = len(self)
+        for name, t, dt in (('labels', labels, torch.int64), ('degree', degree, torch.int32), ('counts', counts, torch.int64)):
+            if t is None and name == 'degree':
+                continue
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('dbscan_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
+        if tuple(labels.shape) != (G,):
+            raise ValueError('dbscan_into: labels must have shape [%d], got %s' % (G, tuple(labels.shape)))
+        if degree is not None and tuple(degree.shape) != (G,):
+            raise ValueError('dbscan_into: degree must have shape [%d], got %s' % (G, tuple(degree.shape)))
+        if tuple(counts.shape) != (2,):
+            raise ValueError('dbscan_into: counts must have shape [2], got %s' % (tuple(counts.shape),))
+        N.check(N.lib.dif_gallery_dbscan(self._h, distance_metric, tolerance, min_samples, N.ptr(labels) if G else None,
+                                         N.ptr(degree) if degree is not None and G else None, N.ptr(counts), N.stream_ptr()),
+                ValueError)
+
+    def dbscan(self, tolerance, min_samples=3, distance_metric=1):
+        """Which enrolled rows are the same person, and which are nobody: exact density clustering with noise (DBSCAN) at
+        `tolerance`.  -> (labels [G] int64, degree [G] int32, counts [2] int64), all on the device; nothing of size G x G is
+        kept and nothing is read back.
+
+        The edges are `cluster`'s: rows i > j with ``evaluation.utility.distance(rows[i][None, :], rows[j][None, :], metric) <=
+        tolerance`` (row i is the probe; inclusive; NaN is no edge; same units, edge cases and 'clamp_nan' rule as `cluster`).
+        degree[i] = 1 + the number of edges at row i (the row itself always counts).  A row is a CORE row when degree[i] >=
+        min_samples.  Clusters are the connected components of the core rows under the edges between two core rows, and
+        labels[c] = index_base + the smallest row of c's component.  A row that is no core but has a core row within the
+        tolerance is a BORDER row: it takes the label of the nearest such core row (the edge's float32 distance; exact ties
+        go to the lower row number) and joins nothing else, so it cannot bridge two people the way it does under `cluster`.
+        Every other row is NOISE: labels[x] = -1, whatever index_base is.  counts = (number of clusters, number of noise rows).
+
+        The result is canonical: two calls, or other 'cluster_round' values, give identical tensors.  min_samples = 1 gives
+        `cluster`'s labels bit for bit and no noise; min_samples > G gives G noise rows.
+
+        There is no incremental form and `first_row` is not offered: enrolling a row changes the degrees of the rows already
+        there, and with them which rows are core.  Costs two sweeps of `cluster`'s lower triangle."""
+        G = len(self)
+        labels = torch.empty((G,), dtype=torch.int64, device=self._dev)
+        degree = torch.empty((G,), dtype=torch.int32, device=self._dev)
+        counts = torch.empty((2,), dtype=torch.int64, device=self._dev)
+        self.dbscan_into(tolerance, min_samples, distance_metric, labels, degree, counts)
+        return labels, degree, counts
+
     def roc_into(self, probes, probe_labels, row_labels, first_row, thresholds, distance_metric, accept, totals):
         """Allocation-free form of `roc`, the library's own terms: `probes` [B, d] float32, `probe_labels` [B] int64,
         `row_labels` [len(self)] int64, `first_row` [B] int64 or None, `thresholds` [T] float32 NON-DECREASING -- all CUDA;
@@ -579,6 +632,19 @@ def cluster(embeddings, tolerance, distance_metric=1):
         labels, n = g.cluster(tolerance, distance_metric)
         torch.cuda.current_stream().synchronize()   # the temporary gallery is freed below: the work must have ended
         return labels, n
+    finally:
+        if g is not embeddings:
+            g.close()
+
+
+def dbscan(embeddings, tolerance, min_samples=3, distance_metric=1):
+    """One-call form of Gallery.dbscan on a temporary gallery of `embeddings` [M, d]: density clustering with noise
+    -> (labels[M] int64, -1 = noise; degree[M] int32; counts[2] int64: clusters, noise rows), on the device."""
+    g = embeddings if isinstance(embeddings, Gallery) else Gallery(embeddings)
+    try:
+        out = g.dbscan(tolerance, min_samples, distance_metric)
+        torch.cuda.current_stream().synchronize()   # the temporary gallery is freed below: the work must have ended
+        return out
     finally:
         if g is not embeddings:
             g.close()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round"; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round"; + dif_gallery_dbscan; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -272,7 +272,7 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * "topk_seed": 0 (default) the seed stage of dif_match_topk evaluates the k gallery tiles with the smallest search keys
  * per probe; n > 0 makes it n tiles (1: a loose first tolerance, the sweep stage does the work).  Same answers for every
  * value (tests, A/B).
- * "cluster_round": 0 (default) dif_gallery_cluster takes a sixteenth of the rows as the probes of one round, in whole blocks
+ * "cluster_round": 0 (default) dif_gallery_cluster (and each sweep of dif_gallery_dbscan) takes a sixteenth of the rows as the probes of one round, in whole blocks
  * of 128 and at least 2048 (a round's MFMA pass stops at its last probe's row: sixteen rounds do 17 / 32 of the square, one
  * round all of it); n > 0, a multiple of 128, makes it n probes.  Either way at most what the census workspace allows (2^27
  * words / the number of 128-row tiles).  Same answers for every value (tests: several rounds on a small gallery).
@@ -402,6 +402,39 @@ int dif_match_topk(dif_gallery* g, const float* probes_dev, int n, int metric, i
 int dif_gallery_cluster(dif_gallery* g, int metric, float tolerance, int64_t first_row,
                         const int64_t* labels_in_dev /* [first_row], or NULL when first_row == 0 */,
                         int64_t* labels_out_dev /* [n] */, int64_t* n_clusters_dev /* [1] */, void* stream);
+/* density clustering with noise (DBSCAN) of the gallery's own rows, exact, on the edges of dif_gallery_cluster: a row is the
+ * core of a person only if at least min_samples rows, itself included, lie within `tolerance`; clusters grow through cores
+ * only; a row that is no core but has one within the tolerance (a border row) joins that core's cluster and spreads it no
+ * further, so it cannot bridge two people; every other row is noise.  With n = dif_gallery_size:
+ *     E = {(i, j) : j < i and utility.distance(rows[i][None, :], rows[j][None, :], metric) <= tolerance}
+ *                                                    row i is the probe; the reference's float32 values; inclusive;
+ *                                                    NaN <= t is False; self pairs are not edges
+ *     degree[i] = 1 + number of edges of E that contain i           the row itself always counts, whatever distance(i, i) is
+ *     core[i]   = degree[i] >= min_samples
+ *     clusters  = connected components of the graph (core rows, edges of E with both ends core)
+ *     label[c]  = index_base + smallest row of c's component         for a core row c
+ *     label[b]  = label[a(b)]                                        for a row b that is no core and has a core neighbour:
+ *                                                    a(b) = the core neighbour with the smallest float32 distance, the value
+ *                                                    of the edge as E evaluated it; exact ties go to the lower row number
+ *     label[x]  = -1                                                 for every other row (noise), whatever index_base is
+ *     counts_dev[0] = number of clusters;  counts_dev[1] = number of noise rows
+ *   labels_out_dev[i] = label[i];  degree_out_dev[i] = degree[i] when the pointer is not NULL.
+ *   The result is a function of the edge set and its distance values alone: degrees are integer sums, a cluster's label is
+ *   its smallest core row, and a border row's cluster is a minimum over (distance, row) -- none depends on thread order or on
+ *   the order in which edges are found; two calls, or other round sizes, give identical arrays.  min_samples = 1 gives
+ *   dif_gallery_cluster's labels bit for bit and no noise; min_samples > n gives n noise rows and no cluster; tolerance < 0
+ *   gives degree 1 everywhere.
+ * Units, arithmetic and NaN rule: dif_gallery_cluster's (dif_match_within's), under the handle's "clamp_nan".
+ * There is no incremental form: a new row changes the degrees of the rows already enrolled, and with them which rows are core.
+ * An empty gallery writes counts = {0, 0}.  Fails where dif_gallery_cluster fails -- a metric other than 0 / 1, a NaN
+ *   tolerance, an embedding size that is not a multiple of 32, a NULL handle, labels or counts -- and for min_samples < 1.
+ * Costs two sweeps of dif_gallery_cluster's lower triangle -- degrees first, links second; the second keeps the first one's
+ *   census when one round covers the gallery -- i.e. about twice dif_gallery_cluster; nothing of size n x n is kept; no host
+ *   synchronisation in steady state.  Workspace: dif_gallery_cluster's (shared; calls on one stream are ordered) plus 12 bytes
+ *   per row.  Probes go in rounds (gallery option "cluster_round"). */
+int dif_gallery_dbscan(dif_gallery* g, int metric, float tolerance, int min_samples, int64_t* labels_out_dev /* [n] */,
+                       int32_t* degree_out_dev /* [n], or NULL */, int64_t* counts_dev /* [2]: clusters, noise */,
+                       void* stream);
 /* all-pairs verification counts at every threshold, exact: how many genuine (equal labels) and impostor (different labels) pairs
  * of (probe, enrolled row) have a distance below each of T thresholds -- the numerators and denominators of TAR / VAL and FAR
  * over EVERY pair (deep_insight_face/evaluation/verification.py), where utility.calculate_val_far sees a list of pairs.
