@@ -36,6 +36,7 @@ class DifEmbedder:
             raise ValueError("compute must be 'f32' (the reference's arithmetic), 'bf16x3' (split-bf16 throughput mode: three "
                              "bf16 terms per operand, six products) or 'bf16x2' (two terms, three products)")
         self.compute = compute
+        self.bf_terms = 2 if compute == 'bf16x2' else 3       # the library's option "bf_terms" as last set (set_option keeps it)
         if compute in ('bf16x3', 'bf16x2'):
             N.check(N.lib.dif_net_set_option(self._h, b'bf16x3', 1), ValueError)
             N.check(N.lib.dif_net_set_option(self._h, b'bf_terms', 3 if compute == 'bf16x3' else 2), ValueError)
@@ -124,6 +125,8 @@ class DifEmbedder:
     def set_option(self, key, value):
         """Execution option of the library (include/dif.h: dif_net_set_option), e.g. ``('pipe', 0)``."""
         N.check(N.lib.dif_net_set_option(self._h, key.encode(), int(value)), ValueError)
+        if key == 'bf_terms':
+            self.bf_terms = int(value)
 
     def embed_flipped_concat(self, x, layout=None):
         """[embed(x), embed(mirror(x))] concatenated along the feature axis -> [N, 2*emd]: the

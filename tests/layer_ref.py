@@ -12,6 +12,17 @@ Bounds (u = 2^-24; derivations: DESIGN 4l).  With A~ = |scale| conv(|x~|, |w|) +
   split-bf16 tiers   B = (K u + eps_t) A~,  eps_3 = 2^-22 (six products kept), eps_2 = 3 * 2^-16 (three kept)
 y2 = act2(y scale2 + shift2) is held to the same form on A~2 = |scale2| A~ + |shift2|.
 
+The split-bf16 tiers are also held to the sum of the terms they keep (`conv_layer(..., bf_terms=t)`): every operand as t
+bf16 planes by repeated round-to-nearest-even (bf_planes: what bf3_split and net.hip's f32_to_bf16_rne do, bit for bit), the
+linear part the sum over the kept pairs of planes (BF_KEPT) of the sum over taps.  In float64 that is the SPLIT REFERENCE S --
+what a kernel of the tier computes but for its float32 accumulation; the truncation the tier commits on purpose is on both
+sides and leaves the comparison.  In float32, the products added in the kernel's order (32-channel slice, tap, 16-channel half,
+pair), it is the yardstick.  Against S:
+  hard, per element  |y - S| <= (NQ K M + 8) u A~,  NQ = 6 / 3 products per multiply-add, M = 1 + 2^-6 + 2^-13 (BF_MAG: the planes'
+                     absolute values add up to at most (1 + 2^-7 + 2^-16) |x|, for both operands)
+  tight, max         max |y - S| / A~ <= 8 max(yardstick's, 2 u)
+  tight, rms         rms((y - S) / A~) <= RMS_MARGIN x the yardstick's rms: the statistic that tells the tiers apart
+
 The heads and NN4's own layers return (ref, B), B elementwise and stated on what was summed:
   dwfull             B = (HW + 8) u A~,  A~ = |scale| sum |x| |w| + |beta| + |mean scale|  (the shift by its parts, as dwconv_layer)
   gdc tail           the bound propagated stage by stage through depthwise, 1x1, dense and the normalisation (gdc_tail_layer)
@@ -26,6 +37,16 @@ import torch
 U = 2.0 ** -24
 EPS_BF3 = 2.0 ** -22          # hi.hi + hi.mid + mid.hi + mid.mid + hi.lo + lo.hi kept; mid.lo, lo.mid, lo.lo and both residuals dropped
 EPS_BF2 = 3 * 2.0 ** -16      # hi.hi + hi.mid + mid.hi kept; mid.mid and the two residuals (2^-16 each) dropped
+# the kept products as (activation plane, weight plane), 0 = hi, 1 = mid, 2 = lo, in the order conv_bf_mainloop.hpp issues
+# them per 16 k (small terms first)
+BF_KEPT = {3: ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)), 2: ((1, 0), (0, 1), (0, 0))}
+BF_MAG = 1 + 2.0 ** -6 + 2.0 ** -13   # sum over kept pairs of |x_p| |w_q| <= (1 + 2^-7 + 2^-16)^2 |x| |w| < BF_MAG |x| |w|
+BF_SLICE, BF_HALF = 32, 16    # the mainloop's K order: 32-channel slices, nine taps each, two 16-channel MFMAs a tap
+# rms((y - S) / A~) of a kernel over that of the float32 yardstick.  Above 1: another order of summation (MFMA sums of 16,
+# stream-K shares).  Below the smallest ratio a lost plane leaves on the layers of tests/test_layer_ref.py (mid.mid dropped
+# everywhere at K = 4608: x 4.43; every lo product dropped: x 5.56; at K = 576 x 10.4 and x 12.7 -- the table
+# test_split_gates_planted_defects prints): the geometric middle of 1 and 4.43.
+RMS_MARGIN = 2.1
 CHUNK_ELEMS = 1 << 26         # elements of one padded input chunk (images are independent: the sum over taps is chunked)
 
 
@@ -111,6 +132,54 @@ def taps_sum(x, w, stride, pad_t, pad_l, Ho, Wo):
     return out
 
 
+# ----------------------------------------------------------------------------------------------- split-bf16
+def bf_planes(t, n):
+    """A float32 tensor as n bf16-valued float32 planes by repeated round-to-nearest-even: hi = bf16(t), mid = bf16(t - hi),
+    lo = bf16(t - hi - mid) (gemm_core.hpp: bf3_split on the activations, net.hip: f32_to_bf16_rne on the HWIO kernel).  Each
+    remainder is exact in float32."""
+    if t.dtype != torch.float32:
+        raise NotUnderstood('bf_planes of a %s tensor: the kernels split float32 operands' % (t.dtype,))
+    out, r = [], t
+    for _ in range(n):
+        p = r.to(torch.bfloat16).to(torch.float32)
+        out.append(p)
+        r = r - p
+    return out
+
+
+def split_taps_sum(xp, wp, pairs, stride, pad_t, pad_l, Ho, Wo, kernel_order=False):
+    """sum over the kept (p, q) of taps_sum(xp[p], wp[q]) in the planes' dtype.  kernel_order: product by product as
+    gemm_mainloop_patch_bf3 / _bf2t add them into ONE accumulator -- per 32-channel slice the taps row by row, per tap two halves
+    of 16 channels, per half the pairs in BF_KEPT's order (the float32 yardstick); otherwise pair by pair (float64: the order is
+    immaterial at 2^-53)."""
+    if not kernel_order:
+        acc = None
+        for p, q in pairs:
+            t = taps_sum(xp[p], wp[q], stride, pad_t, pad_l, Ho, Wo)
+            acc = t if acc is None else acc + t
+        return acc
+    n, H, W, C = xp[0].shape
+    KH, KW, _, co = wp[0].shape
+    pb = max((Ho - 1) * stride + KH - H - pad_t, 0)
+    pr = max((Wo - 1) * stride + KW - W - pad_l, 0)
+    out = torch.empty((n, Ho, Wo, co), dtype=xp[0].dtype, device=xp[0].device)
+    per = len(xp) * (H + pad_t + pb) * (W + pad_l + pr) * max(C, co)
+    step = max(1, CHUNK_ELEMS // per)
+    for s in range(0, n, step):
+        pads = [torch.nn.functional.pad(x[s:s + step], (0, 0, pad_l, pr, pad_t, pb)) for x in xp]
+        acc = torch.zeros((pads[0].shape[0] * Ho * Wo, co), dtype=out.dtype, device=out.device)
+        for c0 in range(0, C, BF_SLICE):
+            for kh in range(KH):
+                for kw in range(KW):
+                    wins = [t[:, kh:kh + (Ho - 1) * stride + 1:stride, kw:kw + (Wo - 1) * stride + 1:stride, c0:c0 + BF_SLICE].reshape(-1, min(BF_SLICE, C - c0))
+                            for t in pads]
+                    for h0 in range(0, wins[0].shape[1], BF_HALF):
+                        for p, q in pairs:
+                            acc = acc + wins[p][:, h0:h0 + BF_HALF] @ wp[q][kh, kw, c0 + h0:c0 + h0 + BF_HALF]
+        out[s:s + step] = acc.reshape(-1, Ho, Wo, co)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- Winograd F(2x2,3x3)
 _G = [[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]]
 
@@ -167,14 +236,17 @@ def window(t, root):
     return root[:, t['oy']:t['oy'] + h, t['ox']:t['ox'] + w, t['coff']:t['coff'] + c]
 
 
-def conv_layer(desc, params, x, res=None, dtype=torch.float64, form='direct'):
+def conv_layer(desc, params, x, res=None, dtype=torch.float64, form='direct', bf_terms=0):
     """One OP_CONV launch.  x, res: the ROOT tensors the kernel read ([n, H, W, C], any float dtype).  Returns (y, y2, A, A2)
     shaped as the layer's output map [n, Ho, Wo, Cout] (None where the layer has no such output; `stored(desc, ...)` cuts them
     to what the kernel stores): in `dtype`, in the fused order the kernels document (conv_splitk.hpp: SkEpi / conv_epilogue)
         x~ = pre_act(pre_bn(x));  v = conv(x~, w);  y = act(v scale + shift) (+ res at res_stride);  y2 = act2(y scale2 + shift2)
     and the magnitudes A = |scale| conv(|x~|, |w|) + |shift| + |res|, A2 = |scale2| A + |shift2|.
     form 'direct' sums the taps; 'wino' runs the Winograd kernels' order of operations (the float32 yardstick) and takes A
-    through the transforms in absolute value."""
+    through the transforms in absolute value.
+    bf_terms 3 / 2 (form 'direct'): the linear part is the sum over BF_KEPT[bf_terms] of the tap sums of the bf16 planes of
+    x~ and of the HWIO kernel, both split from their float32 values -- in float64 the split reference, in float32 and in the
+    kernel's order of products the yardstick of the split-bf16 tiers.  Everything else, A included, is untouched."""
     if desc['kind'] != 'conv':
         raise NotUnderstood('conv_layer on %r' % desc['kind'])
     _whole(desc['x'], 'x')
@@ -197,6 +269,15 @@ def conv_layer(desc, params, x, res=None, dtype=torch.float64, form='direct'):
         # the reference proper stays the plain sum over taps; the yardstick (any narrower dtype) takes the kernels' order
         v = wino_any(xt, w) if dtype != torch.float64 else taps_sum(xt, w, 1, 1, 1, Ho, Wo)
         mag = wino_any(xt.abs(), w, absolute=True)
+    elif bf_terms:
+        if bf_terms not in BF_KEPT or form not in ('direct', 'bf16'):
+            raise NotUnderstood('%r bf16 terms in form %r' % (bf_terms, form))
+        # the kernel splits the float32 values it holds: x~ formed in float32 (today no split-bf16 layer has a pre_bn: x~ = x),
+        # the kernel as the parameters store it
+        xp = [t.to(dtype) for t in bf_planes(xt.to(torch.float32), bf_terms)]
+        wp = [t.to(dtype) for t in bf_planes(kernel_hwio(desc, params, xt.to(torch.float32)), bf_terms)]
+        v = split_taps_sum(xp, wp, BF_KEPT[bf_terms], desc['stride'], desc['pad'][0], desc['pad'][1], Ho, Wo, dtype != torch.float64)
+        mag = taps_sum(xt.abs(), w.abs(), desc['stride'], desc['pad'][0], desc['pad'][1], Ho, Wo)
     else:
         v = taps_sum(xt, w, desc['stride'], desc['pad'][0], desc['pad'][1], Ho, Wo)
         mag = taps_sum(xt.abs(), w.abs(), desc['stride'], desc['pad'][0], desc['pad'][1], Ho, Wo)
@@ -237,6 +318,12 @@ def bound_factor(desc, form, bf_terms=0):
     if form == 'bf16':
         return K * U + (EPS_BF3 if bf_terms == 3 else EPS_BF2)
     return (K + 8) * U
+
+
+def split_bound_factor(desc, bf_terms):
+    """B / A~ of a split-bf16 tier against its split reference: NQ K products in one float32 sum of magnitude <= BF_MAG A~."""
+    KH, KW = desc['k']
+    return (len(BF_KEPT[bf_terms]) * KH * KW * desc['cin_true'] * BF_MAG + 8) * U
 
 
 # ----------------------------------------------------------------------------------------------- the exact layers
@@ -491,6 +578,20 @@ TIGHT_FACTOR = 8.0
 def tight_limit(y32, ref, A):
     """8 * max(the float32 yardstick's own error on this input, 2 u), relative to A."""
     return TIGHT_FACTOR * max(rel_error(y32, ref, A), 2 * U)
+
+
+def rms_error(got, ref, A):
+    """rms over the elements with A > 0 of (got - ref) / A."""
+    ok = A > 0
+    if not bool(ok.any()):
+        return 0.0
+    e = (got.to(torch.float64) - ref.to(torch.float64))[ok] / A[ok]
+    return float((e * e).mean().sqrt())
+
+
+def rms_limit(y32, ref, A):
+    """RMS_MARGIN x the float32 yardstick's rms on this input, relative to A (no floor: a yardstick at 0 asks for 0)."""
+    return RMS_MARGIN * rms_error(y32, ref, A)
 
 
 def gate_in_B(got, y32, ref, B):

@@ -6,6 +6,12 @@ read, and every element of every image of what it stored held to the gates:
   tight, per layer       max |y - ref| / A~ <= 8 max(max |y32 - ref| / A~, 2 u)   (f32 and Winograd forms; y32: the float32
                          yardstick on the same input -- the same sum over taps, or the Winograd order of operations)
                          the fused GDC tail, l2norm and lrn: the same in units of B (layer_ref.gate_in_B)
+  split-bf16 tiers       the hard bound above against the true layer, and against the SPLIT reference S of the tier in force (the
+                         float64 sum of the six / three kept products of the bf16 planes: layer_ref.conv_layer(bf_terms=t)):
+                           hard   |y - S| <= (NQ K M + 8) u A~ per element (layer_ref.split_bound_factor)
+                           max    max |y - S| / A~ <= 8 max(yardstick's, 2 u); the yardstick: the same sum in float32 in the
+                                  kernel's order of products
+                           rms    rms((y - S) / A~) <= layer_ref.RMS_MARGIN x the yardstick's rms
   untouched forward      every tapped forward's outputs equal embed's, bit for bit
 
 Failures are collected, not raised: the caller asserts on the list, so one run names every failing layer."""
@@ -40,9 +46,13 @@ def _fmt(name, kern, what, ratio, at, extra=''):
     return '%s [%s] %s: ratio %.3g at image %d, pixel (%d, %d), channel %d%s' % (name, kern, what, ratio, at[0], at[1], at[2], at[3], extra)
 
 
-def sweep(model, x, label='', record=None, verbose=False, params=None, kinds=None, names=None):
+def sweep(model, x, label='', record=None, verbose=False, params=None, kinds=None, names=None, labels=None, ref_terms=None, details=None):
     """x: the input batch on the device (uint8 or float32, NHWC).  Returns (failures, kernel labels seen, launches checked).
-    record: dict kernel label -> {'hard': (ratio, layer), 'tight': (kernel / yardstick ratio, layer)}, worst kept.
+    record: dict kernel label -> {'hard': (ratio, layer), 'tight': (kernel / yardstick ratio, layer)}, worst kept; a split-bf16
+    label also 'split<t>_hard' (|y - S| / B), 'split<t>_max' and 'split<t>_rms' (kernel / yardstick), t the tier that ran.
+    labels: only the launches whose kernel label in the untapped forward of x holds one of these texts.
+    ref_terms: the tier of the split reference, where a test hands the gates another than the one in force on purpose.
+    details: a list that takes (name, kernel label, describe line) of every launch checked.
     params: the reference's parameters, the model's own unless a test hands it others on purpose.
     kinds / names: only the launches of these kinds / whose name starts with one of these are tapped and compared (a head
     case: a few launches of a whole net); the untouched-forward check runs for each of them."""
@@ -50,7 +60,9 @@ def sweep(model, x, label='', record=None, verbose=False, params=None, kinds=Non
     descs = model.op_describe()
     want_out = [t.clone() for t in _outs(model.embed(x))]
     scale, bias, bgr, hflip = getattr(model, '_transform', (1.0, (0.0, 0.0, 0.0), False, False))
-    bf_terms = {'bf16x3': 3, 'bf16x2': 2}.get(model.compute, 0)
+    # the tier in force: dif_net_set_option("bf_terms") moves it at any time, DifEmbedder.set_option keeps count
+    bf_terms = model.bf_terms if model.compute != 'f32' else 0
+    before = model.op_table()                  # the kernels the untapped forward ran
     fails, seen, checked = [], set(), 0
 
     def note(kern, key, ratio, layer):
@@ -75,8 +87,12 @@ def sweep(model, x, label='', record=None, verbose=False, params=None, kinds=Non
     for i, d in enumerate(descs):
         if (kinds is not None and d['kind'] not in kinds) or (names is not None and not d['name'].startswith(tuple(names))):
             continue
+        if labels is not None and not any(t in before[i][1] for t in labels):
+            continue
         tap = model.tap(x, i)
         name, kern, _ = model.op_table()[i]
+        if details is not None:
+            details.append((name, kern, d))
         seen.add(kern)
         got_out = _outs(tap['out'])
         if len(got_out) != len(want_out) or not all(torch.equal(a, b) for a, b in zip(got_out, want_out)):
@@ -143,10 +159,42 @@ def sweep(model, x, label='', record=None, verbose=False, params=None, kinds=Non
                 y32 = y32_2 = None
                 if form != 'bf16':
                     y32, y32_2, _, _ = L.conv_layer(d, params, tap['x'], tap.get('res'), torch.float32, form)
+                split = {}
+                if form == 'bf16':
+                    terms = ref_terms or bf_terms
+                    if terms not in L.BF_KEPT:
+                        raise L.NotUnderstood('a split-bf16 kernel with %r terms in force' % (terms,))
+                    sy, sy2, _, _ = L.conv_layer(d, params, tap['x'], tap.get('res'), torch.float64, form, terms)
+                    yy, yy2, _, _ = L.conv_layer(d, params, tap['x'], tap.get('res'), torch.float32, form, terms)
+                    split, fs, tag = {'y': (sy, yy), 'y2': (sy2, yy2)}, L.split_bound_factor(d, terms), 'split%d_' % terms
                 for key, ref, mag, yard in (('y', ry, A, y32), ('y2', ry2, A2, y32_2)):
                     if ref is None:
                         continue
                     got = L.window(d[key], tap[key])
+                    if key in split:
+                        S, Y = (L.stored(d, key, t) for t in split[key])
+                        m = L.stored(d, key, mag)
+                        if got.shape != S.shape:
+                            raise L.NotUnderstood('%s stored as %s, reference %s' % (key, tuple(got.shape), tuple(S.shape)))
+                        r, at = L.worst(got, S, fs * m)
+                        rel, lim, yrel = L.rel_error(got, S, m), L.tight_limit(Y, S, m), L.rel_error(Y, S, m)
+                        rms, yrms = L.rms_error(got, S, m), L.rms_error(Y, S, m)
+                        ratio = rms / yrms if yrms > 0 else (0.0 if rms == 0 else float('inf'))
+                        if ref_terms is None:
+                            note(kern, tag + 'hard', r, name)
+                            note(kern, tag + 'max', rel / max(yrel, 2 * L.U), name)
+                            note(kern, tag + 'rms', ratio, name)
+                        if verbose:
+                            print('%s %s [%s] %s, %d terms: |y - S| / B %.4g, max %.3g (yardstick %.3g), rms %.3g (yardstick %.3g, x %.3g)'
+                                  % (label, name, kern, key, terms, r, rel, yrel, rms, yrms, ratio))
+                        if not r <= 1.0:
+                            fails.append(_fmt(name, kern, 'split reference, %d terms: |%s - S| / B' % (terms, key), r, at))
+                        if not rel <= lim:
+                            fails.append(_fmt(name, kern, 'max gate on %s against the split reference, %d terms: |y - S| / A~ = %.3g, limit %.3g; kernel / yardstick'
+                                              % (key, terms, rel, lim), rel / (lim / L.TIGHT_FACTOR), at))
+                        if not ratio <= L.RMS_MARGIN:
+                            fails.append(_fmt(name, kern, 'rms gate on %s against the split reference, %d terms: rms (y - S) / A~ = %.3g, yardstick %.3g, margin %.3g; kernel / yardstick'
+                                              % (key, terms, rms, yrms, L.RMS_MARGIN), ratio, at))
                     ref, mag = L.stored(d, key, ref), L.stored(d, key, mag)
                     if got.shape != ref.shape:
                         raise L.NotUnderstood('%s stored as %s, reference %s' % (key, tuple(got.shape), tuple(ref.shape)))

@@ -477,8 +477,11 @@ def test_embed_bf16x3_mode_vs_oracle(cuda, arch, head, emd, n, compute):
     """The split-bf16 throughput modes -- "bf16x3": three bf16 terms per f32 operand, six MFMA products; "bf16x2" (round 4):
     two terms, three products -- f32 accumulation, against the float32 path on the whole batch and against the oracle on
     spot rows, at the same gates: cosine gap < 1e-5 (oracle) / 1e-6 (f32 path), pairwise cosine distances within 1e-5.
-    The batches are large enough for the mode to engage (conv.hip: bf3_pays -- short or small layers stay on
-    the f32 kernels), including the halo-patch 3x3 path; `launches` below checks that it did."""
+    Which layers take the mode is decided by shape alone (net.hip at finalize and conv.hip: conv_bf3p_form / bf3p_applies --
+    3x3 / stride 1 / pad 1 layers without a pre-activation BN, of at least 64 filters, whose map fits the 128-pixel linear halo
+    patch or has sides that are multiples of 8, with a plain output view and a same-size shortcut; every other layer stays on
+    the f32 kernels); `launches` below checks that it engaged.  The tiers are told apart layer by layer in
+    tests/test_layer_taps_gpu.py: this test's gates are the same for both."""
     from deep_insight_face.networks.triplet import DifEmbedder
     u8 = crops_u8(n, seed=31)
     f32 = DifEmbedder(arch, head, emd, (112, 112, 3), max_batch=n).init_synthetic(2024)

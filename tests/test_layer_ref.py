@@ -10,6 +10,10 @@
 3b. The heads, LRN and the L2 / average pools (dwfull_layer, gdc_tail_layer, l2norm_layer, lrn_layer, pool_layer): each equals
    the oracle's pieces in float64 to 2e-15, its float32 yardstick passes both gates, and eight planted one-place defects each
    break the gate the test names.
+3c. The split-bf16 tiers: bf_planes reproduces the library's round-to-nearest-even split bit for bit; conv_layer(bf_terms=t) is the
+   sum of the kept products of the planes; a clean float32 emulation of conv_bf_mainloop.hpp passes the three gates against that
+   split reference, and five planted slips are each held against them and against the a-priori bound the tiers had before
+   (the table the tests print is in DESIGN 4l).
 4. For every arch the library builds: each describe line parses, every parameter it names exists with the shape the
    geometry implies, and the launch list is op_table()'s.
 """
@@ -333,6 +337,202 @@ def test_planted_defect_breaks_a_gate(defect):
     assert bad >= 1 and hard > 1.0
     assert rel > lim
 
+
+
+# ------------------------------------------------------------------------------------------------- split-bf16: the split reference
+def _rne_bits(f):
+    """net.hip's f32_to_bf16_rne on an array of float32, in integer arithmetic -> the bf16 values as float32."""
+    u = np.ascontiguousarray(f, np.float32).view(np.uint32).astype(np.uint64)
+    b = ((u + 0x7fff + ((u >> 16) & 1)) >> 16) & 0xffff
+    return (b << 16).astype(np.uint32).view(np.float32)
+
+
+def test_bf_planes_reproduce_the_librarys_rounding_bit_for_bit():
+    """bf_planes against f32_to_bf16_rne applied three times to the running remainder (net.hip: the w3f planes; bf3_split's
+    v_cvt_pk_bf16_f32 rounds the same way): random values of both signs and many exponents, ties to even in both directions
+    (1 + 2^-8 -> 1, 1 + 3 * 2^-8 -> 1 + 2^-6, and the same one plane down), values whose mid plane is zero (a bf16 value; a
+    bf16 value + 2^-20) and zero itself."""
+    rng = np.random.default_rng(16)
+    special = [0.0, 1.0, -1.0, 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), 1 + 2.0 ** -10 + 2.0 ** -18, 1 + 2.0 ** -10 + 3 * 2.0 ** -18,
+               1.5, 3.140625, 1 + 2.0 ** -20, -(0.75 + 2.0 ** -21), 2.0 ** -100, 1e30]
+    x = np.concatenate([np.asarray(special, np.float32), (rng.standard_normal(4096) * np.exp2(rng.integers(-30, 30, 4096))).astype(np.float32)])
+    planes = L.bf_planes(torch.from_numpy(x), 3)
+    r = x.copy()
+    for k, p in enumerate(planes):
+        want = _rne_bits(r)
+        assert np.array_equal(p.numpy().view(np.uint32), want.view(np.uint32)), 'plane %d' % k
+        r = (r - want).astype(np.float32)
+    hi, mid, lo = (p.numpy() for p in planes)
+    assert hi[3] == 1.0 and hi[4] == np.float32(1 + 2.0 ** -6) and mid[3] == np.float32(2.0 ** -8)        # ties went to even
+    assert hi[6] == hi[7] == 1.0 and mid[6] == np.float32(2.0 ** -10) and lo[6] == np.float32(2.0 ** -18)          # ... one plane down
+    assert mid[7] == np.float32(2.0 ** -10 + 2.0 ** -16) and lo[7] == np.float32(-2.0 ** -18)
+    assert mid[8] == 0 and lo[8] == 0 and mid[10] == np.float32(2.0 ** -20) and lo[10] == 0      # a bf16 value: mid is zero; 1 + 2^-20: lo is
+    assert np.all(np.abs(x.astype(np.float64) - hi.astype(np.float64) - mid - lo) <= 2.0 ** -24 * np.abs(x))
+    assert [tuple(t.shape) for t in L.bf_planes(torch.from_numpy(x), 2)] == [x.shape] * 2
+    with pytest.raises(L.NotUnderstood):
+        L.bf_planes(torch.from_numpy(x).double(), 3)
+
+
+def test_split_reference_is_the_sum_of_its_kept_terms():
+    """conv_layer(bf_terms=t) in float64 equals sum over BF_KEPT[t] of the oracle's convolution of the planes, with the epilogue
+    (BN, shortcut, second output behind a PReLU, a sub-sampled first output) and A~ those of the plain layer; the truncation it
+    carries against the true layer is inside the tier's a-priori eps (2^-22 / 3 * 2^-16) A~."""
+    desc, p, x, res, _ = make_case('second output, first one sub-sampled')
+    p = dict(p, alpha2=np.random.default_rng(1).uniform(0.1, 0.4, 12).astype(np.float32))
+    desc = dict(desc, act2='prelu', alpha2='alpha2')
+    ty, ty2, A, A2 = run_ref(desc, p, x, res)
+    p64 = nets.cast_params(p, np.float64)
+    for terms in (3, 2):
+        y, y2, As, A2s = L.conv_layer(desc, p, torch.from_numpy(x), torch.from_numpy(res), torch.float64, 'direct', terms)
+        xp = [t.numpy().astype(np.float64) for t in L.bf_planes(torch.from_numpy(x), terms)]
+        wp = [t.numpy().astype(np.float64) for t in L.bf_planes(torch.from_numpy(p['layer/kernel']), terms)]
+        v = sum(nets.conv2d(xp[a], wp[b], None, 1, (1, 1, 1, 1)) for a, b in L.BF_KEPT[terms])
+        wy = nets.batchnorm(v, p64, 'bn', EPS) + res
+        wy2 = nets.prelu(nets.batchnorm(wy, p64, 'bn2', EPS), p64['alpha2'])
+        assert np.abs(y.numpy() - wy).max() <= 1e-13 and np.abs(y2.numpy() - wy2).max() <= 1e-13
+        assert torch.equal(L.stored(desc, 'y', As), A) and torch.equal(A2s, A2)
+        gap = float(((L.stored(desc, 'y', y) - ty).abs() / A).max())
+        print('%d terms: max |S - true| / A~ = %.3g (eps %.3g)' % (terms, gap, L.EPS_BF3 if terms == 3 else L.EPS_BF2))
+        assert 0 < gap <= (L.EPS_BF3 if terms == 3 else L.EPS_BF2)
+        y32 = L.conv_layer(desc, p, torch.from_numpy(x), torch.from_numpy(res), torch.float32, 'direct', terms)[0]
+        assert y32.dtype == torch.float32 and float((y32.double() - y).abs().max()) <= 64 * L.U * float(As.max())
+
+
+# ------------------------------------------------------------------------------------------------- split-bf16: planted defects
+def _split_layer(ci):
+    """3 images of 7 x 7 (147 pixels: a 128-pixel tile spans three images) x ci -> 64, ReLU'd input, He-scaled kernel, BN,
+    shortcut, and a second output behind a BN and a PReLU: IResNet's epilogue."""
+    rng = np.random.default_rng(ci)
+    n, H, W, co = 3, 7, 7, 64
+    x = np.maximum(rng.standard_normal((n, H, W, ci)), 0).astype(np.float32)
+    res = rng.standard_normal((n, H, W, co)).astype(np.float32)
+    p = {'layer/kernel': (rng.standard_normal((3, 3, ci, co)) * np.sqrt(2 / (9 * ci))).astype(np.float32),
+         'alpha2': rng.uniform(0.1, 0.4, co).astype(np.float32)}
+    p.update({k: np.asarray(v, np.float32) for k, v in bn_params(rng, 'bn', co).items()})
+    p.update({k: np.asarray(v, np.float32) for k, v in bn_params(rng, 'bn2', co).items()})
+    desc = D(T(H, W, ci), T(H, W, co), (3, 3), 1, (1, 1), bn=('bn', EPS), res=T(H, W, co), y2=T(H, W, co), bn2=('bn2', EPS),
+             act2='prelu', alpha2='alpha2')
+    return desc, p, x, res
+
+
+def _trunc_planes(t, n):
+    """The planes by TRUNCATION (the low 16 bits cut): what a split by shifts instead of v_cvt_pk_bf16_f32 would give."""
+    out, r = [], t
+    for _ in range(n):
+        p = torch.from_numpy((r.numpy().view(np.uint32) & np.uint32(0xffff0000)).view(np.float32).copy())
+        out.append(p)
+        r = r - p
+    return out
+
+
+SPLIT_DEFECTS = ['mid.hi dropped for one 32-channel slice on one 32-pixel tile', 'every lo product dropped', 'mid.mid dropped everywhere',
+                 'activation planes by truncation', 'the halo column of one slice read as zeros']
+
+
+def _split_emulation(p, x, res, terms, defect=None):
+    """The layer in float32 torch in the order of conv_bf_mainloop.hpp: planes by repeated rounding, one accumulator per output,
+    per 32-channel slice the nine taps, per tap two 16-channel halves, per half the kept products small terms first; then the
+    float32 epilogue.  `defect` plants one slip.  Rows of the accumulator are the pixels in (image, row, column) order."""
+    f = torch.float32
+    xt, k = torch.from_numpy(x), torch.from_numpy(p['layer/kernel'])
+    n, H, W, ci = x.shape
+    co = k.shape[3]
+    xp = (_trunc_planes if defect == SPLIT_DEFECTS[3] else L.bf_planes)(xt, terms)
+    wp = L.bf_planes(k, terms)
+    pads = [torch.nn.functional.pad(t, (0, 0, 1, 1, 1, 1)) for t in xp]
+    # two stream-K shares (the first and the second half of the slices), handed over in float32; the 16 products of one MFMA
+    # summed exactly and rounded once: an order the yardstick does not have
+    shares = [torch.zeros((n * H * W, co), dtype=f), torch.zeros((n * H * W, co), dtype=f)]
+    for c0 in range(0, ci, 32):
+        acc = shares[c0 >= ci // 2]
+        for kh in range(3):
+            for kw in range(3):
+                wins = [t[:, kh:kh + H, kw:kw + W, c0:c0 + 32].clone() for t in pads]
+                if defect == SPLIT_DEFECTS[4] and c0 == 32 and kw == 2:
+                    for t in wins:
+                        t[1, :, W - 2, :] = 0                 # image 1: the column right of the tile's last one, this slice only
+                wins = [t.reshape(-1, 32) for t in wins]
+                for h0 in (0, 16):
+                    for a, b in L.BF_KEPT[terms]:
+                        t = (wins[a][:, h0:h0 + 16].double() @ wp[b][kh, kw, c0 + h0:c0 + h0 + 16].double()).to(f)
+                        if defect == SPLIT_DEFECTS[0] and (a, b) == (1, 0) and c0 == 32:
+                            t[32:64] = 0
+                        if (defect == SPLIT_DEFECTS[1] and 2 in (a, b)) or (defect == SPLIT_DEFECTS[2] and (a, b) == (1, 1)):
+                            continue
+                        acc += t
+    acc = shares[0] + shares[1]
+    q = {key: torch.from_numpy(v) for key, v in p.items()}
+    sc = q['bn/gamma'] / torch.sqrt(q['bn/moving_variance'] + np.float32(EPS))
+    sh = q['bn/beta'] - q['bn/moving_mean'] * sc
+    y = acc.reshape(n, H, W, co) * sc + sh + torch.from_numpy(res)
+    sc2 = q['bn2/gamma'] / torch.sqrt(q['bn2/moving_variance'] + np.float32(EPS))
+    sh2 = q['bn2/beta'] - q['bn2/moving_mean'] * sc2
+    v2 = y * sc2 + sh2
+    return y, torch.where(v2 >= 0, v2, v2 * q['alpha2'])
+
+
+def _split_figures(desc, p, x, res, terms, got, got2):
+    """-> per output the figures of the three new gates and of the old hard bound: dicts of ratios to their limits' parts."""
+    tx, tr = torch.from_numpy(x), torch.from_numpy(res)
+    true = L.conv_layer(desc, p, tx, tr, torch.float64)
+    S = L.conv_layer(desc, p, tx, tr, torch.float64, 'direct', terms)
+    Y = L.conv_layer(desc, p, tx, tr, torch.float32, 'direct', terms)
+    out = []
+    for i, g in ((0, got), (1, got2)):
+        A = S[2 + i]
+        hard, _ = L.worst(g, S[i], L.split_bound_factor(desc, terms) * A)
+        old, _ = L.worst(g, true[i], L.bound_factor(desc, 'bf16', terms) * A)
+        out.append({'hard': hard, 'old': old, 'max': L.rel_error(g, S[i], A), 'max_lim': L.tight_limit(Y[i], S[i], A),
+                    'max_yard': L.rel_error(Y[i], S[i], A), 'rms': L.rms_error(g, S[i], A), 'rms_yard': L.rms_error(Y[i], S[i], A)})
+    return out
+
+
+def _split_passes(f):
+    return f['hard'] <= 1.0 and f['max'] <= f['max_lim'] and f['rms'] <= L.RMS_MARGIN * f['rms_yard']
+
+
+def _split_row(label, f):
+    return ('%-66s hard %8.3g  max %.2e / yardstick %.2e = %6.3g (gate 8)  rms %.2e / %.2e = %6.3g (gate %.3g)  old hard bound %8.3g: %s'
+            % (label, f['hard'], f['max'], f['max_yard'], f['max'] / max(f['max_yard'], 2 * L.U), f['rms'], f['rms_yard'],
+               f['rms'] / f['rms_yard'], L.RMS_MARGIN, f['old'], 'passes' if f['old'] <= 1.0 else 'fails'))
+
+
+@pytest.mark.parametrize('terms', [3, 2])
+@pytest.mark.parametrize('ci', [64, 512])
+def test_split_gates_clean_emulation_passes(ci, terms):
+    desc, p, x, res = _split_layer(ci)
+    y, y2 = _split_emulation(p, x, res, terms)
+    for key, f in zip(('y', 'y2'), _split_figures(desc, p, x, res, terms, y, y2)):
+        print(_split_row('K %d, %d terms, clean, %s' % (9 * ci, terms, key), f))
+        assert _split_passes(f) and f['old'] <= 1.0
+
+
+# (the two-term tier has no lo plane and keeps no mid.mid: defects 1 and 2 do not exist there)
+SPLIT_PLANTED = [(ci, terms, d) for ci in (64, 512) for terms in (3, 2) for d in SPLIT_DEFECTS if terms == 3 or d not in SPLIT_DEFECTS[1:3]]
+
+
+@pytest.mark.parametrize('ci,terms,defect', SPLIT_PLANTED)
+def test_split_gates_planted_defects(ci, terms, defect):
+    """Each slip breaks at least one of the three gates against the split reference, on both outputs; printed with it: whether
+    the a-priori bound against the true layer (the only gate these kernels had) would have passed it.  It passes the lost
+    planes and the truncation at both K and the dropped slice at K = 4608; it fails the dropped slice at K = 576 and the halo column.
+    NOT rejected, at either K: the activation planes by truncation in the THREE-term tier.  Three truncated planes of 8 bits
+    hold all 24 significand bits of a float32, as three rounded ones do to 2^-24: the six kept products then differ from S's by
+    the dropped mid.lo, lo.mid, lo.lo of either split, 2^-24 |x| |w| a product and of random sign over the taps -- K 576:
+    max x 0.50, rms x 0.69 of the yardstick's; K 4608: x 0.63, x 0.72.  No loss of accuracy, so nothing for a gate against the
+    kept terms to see: asserted to PASS, so that this note stays true.  In the two-term tier the same slip leaves 2^-15 |x|
+    unrepresented instead of 2^-17 and fails the rms gate 27 .. 70 fold."""
+    desc, p, x, res = _split_layer(ci)
+    y, y2 = _split_emulation(p, x, res, terms, defect)
+    figs = _split_figures(desc, p, x, res, terms, y, y2)
+    for key, f in zip(('y', 'y2'), figs):
+        print(_split_row('K %d, %d terms, %s, %s' % (9 * ci, terms, defect, key), f))
+    if terms == 3 and defect == SPLIT_DEFECTS[3]:
+        assert _split_passes(figs[0]) and _split_passes(figs[1]), 'the gates now see three truncated planes: say so above'
+        return
+    assert not _split_passes(figs[0]) and not _split_passes(figs[1])
+    if defect in SPLIT_DEFECTS[1:3]:                        # a lost plane: the rms gate is the one that sees it
+        assert all(f['rms'] > L.RMS_MARGIN * f['rms_yard'] and f['hard'] <= 1.0 and f['old'] <= 1.0 for f in figs)
 
 # ------------------------------------------------------------------------------------------------- heads, LRN, L2 / avg pools
 REL64 = 2e-15

@@ -7,6 +7,11 @@ convolution) and holds every element of every image to the a-priori rounding bou
 8 x that of a float32 run of the same reference (tests/layer_sweep.py states the gates; tests/test_layer_ref.py shows on
 the CPU that they pass float32 arithmetic and reject five planted one-place defects).
 
+The split-bf16 tiers are held, besides, to the float64 sum of the products they keep (the split reference: hard, max and rms
+gates of tests/layer_sweep.py), the tier read from the model as it stands; SPLIT_CASES sweep only the launches that ran a
+split-bf16 kernel, on IResNet-50, YOLOv3, a sub-sampled first output, the two-term tile under three terms, a model switched
+3 -> 2 -> 3, and two liveness runs hand a tier the OTHER tier's reference.
+
 Cases: the smallest shapes the existing tests use to reach each kernel form (tests/test_nonsquare_gpu.py,
 tests/test_winograd_kstep_gpu.py), every net on ONE lane (the tap is single-lane by construction), odd batches so the
 last blocks are partial.  Each case asserts by kernel label that its forms ran; the last test holds the union of labels
@@ -261,6 +266,144 @@ def test_tail_sweep_is_live_on_the_device(zoo, monkeypatch):
     fails, _, checked = layer_sweep.sweep(m, x, 'live', None, params=p, kinds=TAIL_KINDS, names=TAIL_NAMES)
     print('\n'.join(fails))
     assert checked == 2 and fails and all(f.startswith('head_tail ') for f in fails) and any('tight gate' in f for f in fails), fails
+
+
+# ------------------------------------------------------------------------------------------------- split-bf16, term by term
+SPLIT = 'split-bf16'
+WIDE_LIN, WIDE_8X8 = '[split-bf16]<128x128,patch128+Bdirect>', '[split-bf16]<128x128,patch8x8+Bdirect>'
+NARROW_LIN, NARROW_8X8 = '[split-bf16]<128x64,patch128+Bdirect>', '[split-bf16]<128x64,patch8x8+Bdirect>'
+# IResNet-50: every 3x3 / stride 1 layer behind the stem -- conv1 and conv2 of every block but the stride-2 conv2 that opens a stage
+IRES_BLOCKS = ((1, 3), (2, 4), (3, 14), (4, 3))
+IRES_SPLIT = ['layer%d_%d_conv%d' % (s, b, k) for s, nb in IRES_BLOCKS for b in range(nb) for k in (1, 2) if (b, k) != (0, 2)]
+IRES_F32 = ['conv1'] + ['layer%d_0_conv2' % s for s, _ in IRES_BLOCKS]
+
+
+def ires_label(name, side):
+    """The form conv_bf3p_form gives a layer of IResNet-50 on a `side` x `side` input: the linear patch where the 128-pixel
+    tile's halo patch fits its 232 entries on the m x m map the layer reads (m <= 28), else two 8x8 sub-tiles; 64 columns at 64
+    filters, else 128."""
+    stage, block, k = (int(t) for t in name.replace('layer', '').replace('conv', '').split('_'))
+    m = side >> (stage - 1 if (block, k) == (0, 1) else stage)
+    lin = 127 + 2 * (126 // m + 1) + (m + 2) * (126 // (m * m) + 1) + 2 * (m + 2) + 4 <= 232
+    return '[split-bf16]<128x%d,%s+Bdirect>' % (64 if stage == 1 else 128, 'patch128' if lin else 'patch8x8')
+
+
+# YOLOv3 64 x 160: the 3x3 / stride 1 layers of at least 64 filters on maps 32 x 80 .. 4 x 10 (leaky ReLU; the backbone's with a
+# shortcut, the heads' without); the 2 x 5 maps are too small -- a 128-pixel tile would wrap rows and images 288 patch entries'
+# worth, 232 fit -- and stay on the f32 kernels
+YOLO_SPLIT = ['conv_%d' % i for i in (3, 6, 8, 11, 13, 15, 17, 19, 21, 23, 25, 28, 30, 32, 34, 36, 38, 40, 42, 61, 63, 65, 69, 71, 73)]
+YOLO_F32 = ['conv_%d' % i for i in (45, 47, 49, 51, 53, 55, 57)]
+YOLO_LABEL = dict({'conv_3': NARROW_8X8, 'conv_6': WIDE_8X8, 'conv_8': WIDE_8X8}, **{n: WIDE_LIN for n in YOLO_SPLIT[3:]})
+VGG_SPLIT = ['block1_conv2', 'block2_conv1', 'block2_conv2', 'block3_conv1', 'block3_conv2', 'block3_conv3', 'block4_conv1', 'block4_conv2', 'block4_conv3']
+RES_SPLIT = ['conv2_block1_2_conv', 'conv2_block2_2_conv', 'conv3_block1_2_conv', 'conv3_block2_2_conv', 'conv3_block3_2_conv']
+
+
+def split_case(arch, head, emd, hw, n, compute, engaged, f32=(), label_of=None, opts=None, max_batch=None, name='', **want):
+    """engaged: the launches that must have run a split-bf16 kernel -- these and no others are swept; f32: launches that must NOT
+    have; label_of: {launch: text its label holds}; want: 'res', 'y2', 'prelu', 'leaky', 'y_sub' -> the engaged launches whose
+    describe line has it (a list of names, compared exactly)."""
+    return {'id': 'bf16-%s-%dx%d-n%d-%s%s' % (arch, hw[0], hw[1], n, compute, ('-' + name) if name else ''), 'net': (arch, head, emd, hw), 'n': n,
+            'compute': compute, 'engaged': list(engaged), 'f32': list(f32), 'label_of': dict(label_of or {}), 'opts': dict(opts or {}),
+            'max_batch': max_batch or n, 'want': want}
+
+
+def build_split_cases():
+    cases = []
+    for compute in ('bf16x3', 'bf16x2'):
+        # IResNet-50 112 x 112: 56 x 56 (8x8 form; 64 and 128 columns), 28 / 14 / 7 (linear; at 7 x 7 a tile spans three images);
+        # conv2 of a block: BN, shortcut, and the next block's BN as the second output; conv1: BN + PReLU; the last conv2 of a
+        # stage stores the even pixels of its first output (the stride-2 shortcut's input)
+        conv2 = [n for n in IRES_SPLIT if n.endswith('conv2')]
+        cases.append(split_case('iresnet50', 'v2', 512, (112, 112), 3, compute, IRES_SPLIT, IRES_F32, {n: ires_label(n, 112) for n in IRES_SPLIT},
+                                res=conv2, y2=conv2, prelu=[n for n in IRES_SPLIT if n.endswith('conv1')],
+                                y_sub=['layer1_2_conv2', 'layer2_3_conv2', 'layer3_13_conv2']))
+        cases.append(split_case('yolov3', 'v3', 1, (64, 160), 3, compute, YOLO_SPLIT, YOLO_F32, YOLO_LABEL, res=YOLO_SPLIT[:19], leaky=YOLO_SPLIT))
+        # the smallest net with a sub-sampled first output in this mode: IResNet-50 at 32 x 32 (maps 16 .. 2) -- the last conv2 of
+        # stages 1 and 2 (16 x 16 x 64: 64 columns; 8 x 8 x 128), epilogue variant 2; stage 3's 4 x 4 map stays on the f32 kernels
+        small = [n for n in IRES_SPLIT if n < 'layer3_0_conv2' or n == 'layer3_0_conv1']
+        cases.append(split_case('iresnet50', 'v2', 512, (32, 32), 3, compute, small, [n for n in IRES_SPLIT if n not in small] + IRES_F32,
+                                {n: ires_label(n, 32) for n in small}, name='ysub', y_sub=['layer1_2_conv2', 'layer2_3_conv2']))
+    # three terms on the two-term tile (dbg 128: Tile<4, 1, 1, 4> takes the linear 128-column layers): six products
+    cases.append(split_case('resnet', 'v3', 512, (96, 64), 37, 'bf16x3', RES_SPLIT, opts={'dbg': 128}, name='bf2-tile'))
+    return cases
+
+
+SPLIT_CASES = build_split_cases()
+
+
+def run_split_case(zoo, c, env, verbose=False):
+    """-> (failures, labels seen, launches checked): the sweep of the launches that ran a split-bf16 kernel, and what the case
+    states about them."""
+    arch, head, emd, hw = c['net']
+    m = zoo.net(arch, head, emd, hw, c['max_batch'], compute=c['compute'], streams=1, monkeypatch=env)
+    x = torch.from_numpy(zoo.pool(hw, max(c['n'], 40))[:c['n']]).cuda()
+    det = []
+    with options(m, **c['opts']):
+        fails, seen, checked = layer_sweep.sweep(m, x, c['id'], RECORD, verbose, labels=(SPLIT,), details=det)
+        table = {name: kern for name, kern, _ in m.op_table()}
+    ran = [name for name, _, _ in det]
+    if checked < 1 or ran != c['engaged'] or not all(SPLIT in kern for _, kern, _ in det):
+        fails.append('%s: the split-bf16 launches checked are %s, the case states %s' % (c['id'], ran, c['engaged']))
+    fails += ['%s: %s ran %s, a split-bf16 kernel' % (c['id'], n, table[n]) for n in c['f32'] if SPLIT in table.get(n, SPLIT)]
+    fails += ['%s: %s ran %s, the case states %s' % (c['id'], n, table.get(n), t) for n, t in c['label_of'].items() if t not in table.get(n, '')]
+    has = {'res': lambda d: d['res'] is not None, 'y2': lambda d: d['y2'] is not None, 'prelu': lambda d: d['act'] == 'prelu' and d['alpha'],
+           'leaky': lambda d: d['act'] == 'prelu' and not d['alpha'] and d['const_alpha'] > 0, 'y_sub': lambda d: d['y_sub'] == 1}
+    for key, names in c['want'].items():
+        got = [name for name, _, d in det if has[key](d)]
+        if got != list(names) or not got:
+            fails.append('%s: the checked launches with %s are %s, the case states %s' % (c['id'], key, got, list(names)))
+    return fails, seen, checked
+
+
+@pytest.mark.parametrize('c', SPLIT_CASES, ids=[c['id'] for c in SPLIT_CASES])
+def test_split_bf16_launches_against_their_kept_terms(zoo, monkeypatch, c):
+    fails, seen, checked = run_split_case(zoo, c, monkeypatch)
+    SEEN.update(seen)
+    print('%s: %d split-bf16 launches checked' % (c['id'], checked))
+    assert checked >= 1
+    assert not fails, '%d failures\n' % len(fails) + '\n'.join(fails)
+
+
+def _vgg_split(zoo, monkeypatch, compute):
+    m = zoo.net('vgg16', 'v3', 512, (48, 80), 3, compute=compute, streams=1, monkeypatch=monkeypatch)
+    return m, torch.from_numpy(zoo.pool((48, 80), 40)[:3]).cuda()
+
+
+def test_bf_terms_switched_on_one_model(zoo, monkeypatch):
+    """dif_net_set_option("bf_terms") on ONE built model, 3 -> 2 -> 3: each setting passes the gates of ITS tier (the sweep
+    reads the tier in force from the model), the two three-term outputs are bit-identical, and the two-term one is another."""
+    m, x = _vgg_split(zoo, monkeypatch, 'bf16x3')
+    outs = []
+    try:
+        for terms in (3, 2, 3):
+            m.set_option('bf_terms', terms)
+            assert m.bf_terms == terms
+            det = []
+            fails, _, checked = layer_sweep.sweep(m, x, 'terms %d' % terms, None, labels=(SPLIT,), details=det)
+            assert [name for name, _, _ in det] == VGG_SPLIT and checked == len(VGG_SPLIT)
+            assert not fails, '%d terms: %d failures\n' % (terms, len(fails)) + '\n'.join(fails)
+            outs.append(m.embed(x).clone())
+    finally:
+        m.set_option('bf_terms', 3)
+    assert torch.equal(outs[0], outs[2]) and not torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.parametrize('compute,ref_terms', [('bf16x2', 3), ('bf16x3', 2)])
+def test_split_sweep_tells_the_tiers_apart_on_the_device(zoo, monkeypatch, compute, ref_terms):
+    """No defect is planted in any kernel: a model running one tier is swept -- every launch of the net -- against the OTHER
+    tier's split reference.  Every split-bf16 launch fails the rms gate; every failure is a gate against the split reference
+    (rms, and max where the gap of 2^-17 |x| |w| a product passes 8 x the yardstick's worst element) of a split-bf16 launch:
+    the a-priori bounds, against the true layer and against S, still hold, and no other launch fails.  The same sweeps against
+    their own tier pass (the cases above)."""
+    m, x = _vgg_split(zoo, monkeypatch, compute)
+    det = []
+    fails, _, checked = layer_sweep.sweep(m, x, 'live', None, ref_terms=ref_terms, details=det)
+    print('\n'.join(fails))
+    split = [name for name, kern, _ in det if SPLIT in kern]
+    assert split == VGG_SPLIT and checked == len(m.op_describe())
+    for name in split:
+        assert any(f.startswith(name + ' ') and 'rms gate' in f for f in fails), name
+    assert all(f.split(' ')[0] in split and 'against the split reference' in f and ('rms gate' in f or 'max gate' in f) for f in fails), fails
 
 
 # every family the cases are there for (the issue's list); a label matches by containing the text

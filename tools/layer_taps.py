@@ -8,6 +8,9 @@ Per kernel label (op_table()'s `family<tile, operand form>`):
   tight  worst (max |y - ref| / A~) / max(max |y32 - ref| / A~, 2 u): the kernel against the float32 yardstick (gate: 8);
          for the GDC tail, l2norm_kernel and lrn_kernel the same in units of B.  The L2 / average pools are listed as
          maxpool_kernel[l2] / maxpool_kernel[avg] (hard only; 'max' mode is bit-exact and has no row).
+  split<t>_hard, split<t>_max, split<t>_rms  (split-bf16 labels, t = 3 / 2 terms) against the split reference S, the float64 sum
+         of the tier's kept products: worst |y - S| / B (gate 1), worst max-error and worst rms-error ratio of the kernel to the
+         float32 yardstick in the kernel's order of products (gates 8 and layer_ref.RMS_MARGIN).
 Needs the MI355X.  DESIGN 4l holds the table this writes.
 """
 import json
@@ -30,13 +33,13 @@ def main():
     if '--out' in args:
         out = args[args.index('--out') + 1]
         del args[args.index('--out'):args.index('--out') + 2]
-    cases = [c for c in T.CASES if not args or any(a in c['id'] for a in args)]
+    cases = [c for c in T.CASES + T.SPLIT_CASES if not args or any(a in c['id'] for a in args)]
     zoo, env = Zoo(), T.Env()
     failures, per_case = [], []
     try:
         for c in cases:
             t0 = time.time()
-            fails, seen, checked = T.run_case(zoo, c, env)
+            fails, seen, checked = (T.run_split_case if 'engaged' in c else T.run_case)(zoo, c, env)
             per_case.append({'case': c['id'], 'launches': checked, 'failures': len(fails), 'seconds': round(time.time() - t0, 2)})
             failures += ['%s: %s' % (c['id'], f) for f in fails]
             print('%-48s %3d launches %2d failures %.1f s' % (c['id'], checked, len(fails), time.time() - t0), flush=True)
@@ -44,7 +47,9 @@ def main():
         zoo.close()
     forms = {k: {key: {'ratio': float('%.4g' % v[0]), 'layer': v[1]} for key, v in rec.items()} for k, rec in sorted(T.RECORD.items())}
     doc = {'what': 'worst per-layer figures of the layer-tap sweep per kernel form: hard = |y - ref| / B (gate 1), '
-                   'tight = kernel error / float32 yardstick error, both relative to A~ (gate 8)',
+                   'tight = kernel error / float32 yardstick error, both relative to A~ (gate 8); split-bf16 labels, per tier t: '
+                   'split<t>_hard = |y - S| / B against the float64 sum S of the kept products (gate 1), split<t>_max and split<t>_rms = '
+                   'kernel / yardstick of max and rms (y - S) / A~ (gates 8 and %g)' % T.layer_sweep.L.RMS_MARGIN,
            'cases': per_case, 'forms': forms, 'failures': failures}
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, 'w') as fh:
@@ -54,6 +59,11 @@ def main():
     for k, rec in forms.items():
         print('%-72s %10.4g %10s' % (k, rec.get('hard', {}).get('ratio', float('nan')),
                                      '%.3g' % rec['tight']['ratio'] if 'tight' in rec else '-'))
+    print('%-58s %5s %10s %8s %8s' % ('split-bf16 label', 'terms', '|y - S|/B', 'max', 'rms'))
+    for k, rec in forms.items():
+        for t in (3, 2):
+            if 'split%d_rms' % t in rec:
+                print('%-58s %5d %10.4g %8.3g %8.3g' % ((k, t) + tuple(rec['split%d_%s' % (t, key)]['ratio'] for key in ('hard', 'max', 'rms'))))
     print('%d cases, %d failures -> %s' % (len(cases), len(failures), out))
     return 1 if failures else 0
 
