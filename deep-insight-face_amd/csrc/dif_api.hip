@@ -100,7 +100,8 @@ int dif_gallery_destroy(dif_gallery* h) {
                   (void*)g.best_dist, (void*)g.flagged, (void*)g.nflag, (void*)g.sqmax_bits, (void*)g.hi,
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
                   (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min, (void*)g.cluster_parent,
-                  (void*)g.cluster_bad, (void*)g.dbscan_degree, (void*)g.dbscan_anchor, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins})
+                  (void*)g.cluster_bad, (void*)g.dbscan_degree, (void*)g.dbscan_anchor, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins,
+                  (void*)g.topk_ids_stat})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -343,6 +344,15 @@ int dif_gallery_get_stat(dif_gallery* h, const char* key, int64_t* out, void* st
     *out = (int64_t)v;
     return 0;
   }
+  if (k == "topk_ids_tiles") {                 // (probe, tile) pairs the last dif_match_topk_ids evaluated row by row
+    unsigned long long v = 0;
+    if (g.topk_ids_stat) {
+      DIF_HIP(hipMemcpyAsync(&v, g.topk_ids_stat, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      DIF_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
+    *out = (int64_t)v;
+    return 0;
+  }
   return set_error("dif_gallery_get_stat: unknown key '%s'", key);
 }
 
@@ -390,6 +400,20 @@ int dif_match_topk(dif_gallery* h, const float* probes_dev, int n, int metric, i
   if (n == 0) return 0;
   if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match_topk: null pointer");
   return topk_run(&h->g, probes_dev, n, metric, k, idx_out_dev, dist_out_dev, (hipStream_t)stream);
+}
+
+int dif_match_topk_ids(dif_gallery* h, const float* probes_dev, int n, int metric, int k, const int64_t* row_labels_dev,
+                       const int64_t* exclude_dev, int64_t* idx_out_dev, float* dist_out_dev, int64_t* label_out_dev,
+                       void* stream) {
+  if (!h) return set_error("dif_match_topk_ids: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_topk_ids: negative probe count");
+  if (k < 1 || k > DIF_TOPK_MAX) return set_error("dif_match_topk_ids: k %d outside [1, %d]", k, DIF_TOPK_MAX);
+  if (n == 0) return 0;
+  if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match_topk_ids: null pointer");
+  if (h->g.n > 0 && !row_labels_dev) return set_error("dif_match_topk_ids: null row labels");
+  return topk_ids_run(&h->g, probes_dev, n, metric, k, row_labels_dev, exclude_dev, idx_out_dev, dist_out_dev, label_out_dev,
+                      (hipStream_t)stream);
 }
 
 int dif_gallery_cluster(dif_gallery* h, int metric, float tolerance, int64_t first_row, const int64_t* labels_in_dev,

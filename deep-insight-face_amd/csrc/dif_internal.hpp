@@ -71,6 +71,8 @@ struct Gallery {
   float* topk_min = nullptr;
   size_t topk_min_cap = 0;                   // ... in floats
   int topk_seed = 0;                         // "topk_seed": tiles the seed of dif_match_topk evaluates per probe (0: k of them)
+  // dif_match_topk_ids shares topk_min (stream-ordered calls) and adds one counter: the (probe, tile) evaluations of the last call
+  unsigned long long* topk_ids_stat = nullptr;
   // dif_gallery_cluster (csrc/match_within.hip) shares the census and its thresholds (stream-ordered calls) and adds the
   // union-find's parent array, one int per row, and one int that tells cluster_flatten_kernel of a bad labels_in entry
   int* cluster_parent = nullptr;
@@ -109,6 +111,8 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
 int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
              float* mate_dist_out, hipStream_t st);
 int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
+int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, const int64_t* row_labels, const int64_t* exclude,
+                 int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st);
 int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
                 int64_t* n_clusters, hipStream_t st);
 int dbscan_run(Gallery* g, int metric, float tolerance, int min_samples, int64_t* labels_out, int* degree_out, int64_t* counts,

@@ -1,6 +1,7 @@
 // Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), the rank of
 // one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel), and the k nearest rows in order
-// (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), and the connected components
+// (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), the k nearest distinct
+// identities over a label per row (dif_match_topk_ids; its section follows topk_run), and the connected components
 // of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find),
 // and density clustering with noise on the same edges (dif_gallery_dbscan; its section starts at dbscan_init_kernel).
 // hipcc-flags: -ffp-contract=off
@@ -743,6 +744,276 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
     }
     hipLaunchKernelGGL(topk_select_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows, g->d,
                        metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k, dist_out + b0 * k);
+    DIF_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The k nearest distinct identities, each with its best row (dif_match_topk_ids).  Per probe q, with row_labels [G] and an
+// optional excluded label:
+//   d = distance(q[None, :], gallery, metric);  ok = ~isnan(d) & (row_labels >= 0) & (row_labels != exclude[p])
+//   order = np.argsort(d, kind='stable');  order = order[ok[order]]
+//   keep = the first row of every label in `order`, the first k of those;  idx, dist, label of keep, then the padding
+// The MFMA pass is dif_match_topk's, unchanged: a word is the minimum key over ALL rows of its tile -- excluded rows, negative
+// labels and duplicates included -- hence a lower bound of the minimum over the usable rows, and "word > T(t) + E(t) => no row
+// of the tile has a distance <= t" holds as it does there.  topk_ids_select_kernel differs from topk_select_kernel in three ways:
+//   usable   a row with a negative label or the probe's excluded label is never evaluated and never a candidate.
+//   list     the kept entries have distinct labels: after each evaluated tile the kept set is, for every label seen so far, its
+//            smallest word, and of those the k smallest.  The tile's candidates (words below the k-th kept one) and the kept
+//            entries stand in one LDS array with their labels beside them; every entry that finds a smaller word of its own
+//            label there is struck out, then the bitonic sort (labels moved with their words) and the cut to k.  The k-th
+//            kept word only ever decreases, so an entry pushed out can never matter again, a later smaller word of its label
+//            enters on its own, and the kept set is a function of the set of rows seen, not of their order.
+//   seed     with several rows per identity the s tiles with the smallest words hold few identities, and a single seed leaves
+//            t loose (or +inf) and the sweep long.  So the seed grows: s = "topk_seed" or k; loop { kappa = the s-th smallest
+//            word; evaluate the tiles not yet evaluated with word <= kappa; t = the k-th kept distance or +inf, thr_out =
+//            T(t) + E(t); n = the tiles with word > kappa that are not > thr_out (all of them when the probe is outside the
+//            bound's validity); leave when n <= s or every tile is evaluated; s *= 2 }.  Then the sweep over those n tiles.
+// Why it is exact.  Let d_k be the k-th smallest per-identity best distance over the usable rows (fewer than k identities: the
+// list is short, t = +inf and every tile is evaluated).  Whenever the list is full it holds k actual distances of k distinct
+// labels, each at least its label's best, so t >= d_k.  Every answer row has d <= d_k <= t, so it is not OUT at t, so its tile's
+// word is not > thr_out, so the tile is evaluated in a seed pass or in the sweep -- and t only decreases while the sweep runs,
+// which only tightens the pre-filter "candidate < k-th kept word", never thr_out.  The seed schedule decides how tight t is,
+// never the answer.
+constexpr long long TOPK_NOLABEL = -1;                        // the label of an empty slot: no usable row carries it
+
+// the integer image of the need-th smallest word of probe p (1 <= need <= gtiles): topk_select_kernel's radix select, one byte
+// per pass, as a function -- that kernel is left as it is
+__device__ __forceinline__ unsigned topk_ids_kappa(const float* __restrict__ words, int B, int p, int64_t gtiles,
+                                                   unsigned need, unsigned* s_hist, unsigned* s_sel) {
+  constexpr int NT = 64 * WITHIN_NW;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  unsigned prefix = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) s_hist[tid] = 0;
+    __syncthreads();
+    for (int64_t t = tid; t < gtiles; t += NT) {
+      const unsigned o = ord_f32(words[t * B + p]);
+      if ((unsigned)((unsigned long long)o >> (shift + 8)) == prefix) atomicAdd(&s_hist[(o >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (wave == 0) {                                          // four bins per lane, a scan over the lanes
+      unsigned c[4], sum = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        c[i] = s_hist[4 * lane + i];
+        sum += c[i];
+      }
+      unsigned incl = sum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+      }
+      const unsigned excl = incl - sum;
+      if (excl < need && need <= incl) {                      // exactly one lane: 1 <= need <= the total
+        unsigned r = need - excl;
+        int d = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          if (d == i && r > c[i]) {
+            r -= c[i];
+            d = i + 1;
+          }
+        s_sel[0] = (unsigned)(4 * lane + d);
+        s_sel[1] = r;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | s_sel[0];
+    need = s_sel[1];
+    // (s_sel is written again only behind the two barriers of the next pass, or of the next call)
+  }
+  return prefix;
+}
+
+// One block per probe, block-uniform control flow, as topk_select_kernel.  `tiles_stat` counts the (probe, tile) evaluations.
+__global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
+    const float* __restrict__ words, int64_t G, int B, const float* __restrict__ probes, const float* __restrict__ gallery, int D,
+    int metric, float cdot, const unsigned* __restrict__ sqmax_bits, int clamp, const SumPlan plan, int k, int seed,
+    int64_t index_base, const int64_t* __restrict__ row_labels, const int64_t* __restrict__ exclude,
+    int64_t* __restrict__ idx_out, float* __restrict__ dist_out, int64_t* __restrict__ label_out,
+    unsigned long long* __restrict__ tiles_stat) {
+  constexpr int NT = 64 * WITHIN_NW;
+  __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
+  __shared__ unsigned long long s_list[2 * TOPK_MAX];         // [0, k): kept, ascending; [TOPK_MAX, ..): the tile being merged
+  __shared__ long long s_lab[2 * TOPK_MAX];                   // the label of each word
+  __shared__ float s_word[NT];
+  __shared__ unsigned s_hist[256];
+  __shared__ unsigned s_sel[2];
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* q = probes + (int64_t)p * D;
+  const int64_t gtiles = (G + WITHIN_BM - 1) / WITHIN_BM;
+  const float inf = __builtin_inff();
+  const long long ex = exclude ? (long long)exclude[p] : TOPK_NOLABEL;   // negative: nothing excluded (usable labels are >= 0)
+  if (tid < 2 * TOPK_MAX) {
+    s_list[tid] = TOPK_NONE;
+    s_lab[tid] = TOPK_NOLABEL;
+  }
+  __syncthreads();
+
+  unsigned ntiles = 0;                                        // tiles this block evaluated row by row
+  if (gtiles > 0) {
+    const float s = probe_sq(q, D, lane);                     // the same in every thread
+    long long lo = -1;                                        // tiles with ord(word) <= lo are evaluated already
+    unsigned kappa = ~0u;
+    bool all = false;
+    float thr_out = inf;
+    int sd = seed;
+
+    // evaluates and merges the tiles the pass selects: a seed pass those with lo < ord(word) <= kappa, the sweep those with
+    // ord(word) > kappa that are not > thr_out
+    auto pass = [&](const bool sweep) {
+      auto sel = [&](const float w) {
+        const unsigned o = ord_f32(w);
+        return sweep ? (o > kappa && (all || !(w > thr_out))) : ((long long)o > lo && o <= kappa);
+      };
+      for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+        const float w = t0 + tid < gtiles ? words[(t0 + tid) * B + p] : inf;
+        s_word[tid] = w;
+        if (!__syncthreads_or(t0 + tid < gtiles && sel(w))) continue;   // (also the barrier between two rounds of words)
+        const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
+        for (int j = 0; j < nw; ++j) {
+          if (!sel(s_word[j])) continue;
+          ++ntiles;
+          const int64_t g0 = (t0 + j) * WITHIN_BM;
+          const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
+          const unsigned long long kth = s_list[k - 1];       // the kept labels are distinct: a word that is not below it cannot enter
+          bool any = false;
+          for (int r = wave; r < rows; r += WITHIN_NW) {
+            const long long lab = row_labels[g0 + r];
+            if (lab < 0 || lab == ex) continue;               // not usable: never a candidate
+            float d;
+            (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+            if (d == d) {                                     // a NaN distance is never listed
+              const unsigned long long cand = ((unsigned long long)ord_f32(d) << 32) | (unsigned)(g0 + r);
+              if (cand < kth) {
+                if (lane == 0) {
+                  s_list[TOPK_MAX + r] = cand;
+                  s_lab[TOPK_MAX + r] = lab;
+                }
+                any = true;
+              }
+            }
+          }
+          if (!__syncthreads_or(any)) continue;
+          // one entry per label: an entry that finds a smaller word of its own label is struck out.  The kept ones differ
+          // among themselves already, so they look at the tile's candidates only; broadcast reads, words are unique
+          bool dead = false;
+          if (tid < 2 * TOPK_MAX) {
+            const unsigned long long my = s_list[tid];
+            if (my != TOPK_NONE) {
+              const long long mylab = s_lab[tid];
+              if (tid >= TOPK_MAX)
+                for (int i = 0; i < k; ++i)
+                  if (s_lab[i] == mylab && s_list[i] < my) dead = true;
+              for (int i = TOPK_MAX; i < TOPK_MAX + rows; ++i)
+                if (s_lab[i] == mylab && s_list[i] < my) dead = true;
+            }
+          }
+          __syncthreads();
+          if (dead) {
+            s_list[tid] = TOPK_NONE;
+            s_lab[tid] = TOPK_NOLABEL;
+          }
+          __syncthreads();
+          // bitonic sort of the 2 * TOPK_MAX words, ascending, the labels with them; empty slots are above every candidate
+          for (int k2 = 2; k2 <= 2 * TOPK_MAX; k2 <<= 1) {
+            for (int h = k2 >> 1; h > 0; h >>= 1) {
+              if (tid < TOPK_MAX) {
+                const int i = ((tid & ~(h - 1)) << 1) | (tid & (h - 1)), l = i | h;
+                const unsigned long long a = s_list[i], b = s_list[l];
+                if ((a > b) == ((i & k2) == 0)) {
+                  const long long la = s_lab[i], lb = s_lab[l];
+                  s_list[i] = b;
+                  s_list[l] = a;
+                  s_lab[i] = lb;
+                  s_lab[l] = la;
+                }
+              }
+              __syncthreads();
+            }
+          }
+          if (tid >= k && tid < 2 * TOPK_MAX) {               // keep the smallest k
+            s_list[tid] = TOPK_NONE;
+            s_lab[tid] = TOPK_NOLABEL;
+          }
+          __syncthreads();
+        }
+        __syncthreads();                                      // s_word is rewritten by the next round
+      }
+    };
+
+    bool sweep = false;
+#pragma unroll 1
+    for (;;) {                                                // the seed passes, then the sweep: one call site of `pass`
+      if (!sweep) kappa = (int64_t)sd < gtiles ? topk_ids_kappa(words, B, p, gtiles, (unsigned)sd, s_hist, s_sel) : ~0u;
+      pass(sweep);
+      if (sweep || kappa == ~0u) break;                       // ~0u: every tile is evaluated (no word has a NaN's image)
+      const unsigned long long kth = s_list[k - 1];
+      const float t = kth == TOPK_NONE ? inf : unord_f32((unsigned)(kth >> 32));
+      const Band b = within_band(metric, t, s, D, cdot, sqmax_bits);
+      all = b.odd;
+      thr_out = b.T + b.E;
+      int left = 0;                                           // the tiles the sweep would evaluate at this tolerance
+      for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
+        bool mine = false;
+        if (t0 + tid < gtiles) {
+          const float w = words[(t0 + tid) * B + p];
+          mine = ord_f32(w) > kappa && (all || !(w > thr_out));
+        }
+        left += __syncthreads_count(mine);
+      }
+      if (left <= sd) {
+        sweep = true;
+      } else {
+        lo = kappa;
+        sd *= 2;                                              // (sd < gtiles < 2^24 here)
+      }
+    }
+  }
+
+  if (tid < k) {
+    const unsigned long long w = s_list[tid];
+    idx_out[(int64_t)p * k + tid] = w == TOPK_NONE ? -1 : (int64_t)(unsigned)w + index_base;
+    dist_out[(int64_t)p * k + tid] = w == TOPK_NONE ? __builtin_nanf("") : unord_f32((unsigned)(w >> 32));
+    if (label_out) label_out[(int64_t)p * k + tid] = w == TOPK_NONE ? -1 : (int64_t)s_lab[tid];
+  }
+  if (tid == 0 && ntiles) atomicAdd(tiles_stat, (unsigned long long)ntiles);
+}
+
+int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, const int64_t* row_labels, const int64_t* exclude,
+                 int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st) {
+  if (B <= 0) return 0;
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  const int clamp = g->clamp_nan ? 1 : 0;
+  const int seed = g->topk_seed > 0 ? g->topk_seed : k;
+  const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
+  // the rounds and the words are topk_run's
+  int64_t per = gtiles > 0 ? (int64_t)(TOPK_MIN_MAX / (size_t)gtiles) / 128 * 128 : B;
+  if (per < 128) per = 128;
+  if (per > B) per = B;
+  const size_t need = (size_t)gtiles * (size_t)per;
+  if (need > g->topk_min_cap) {
+    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read it
+    if (grow(&g->topk_min, &g->topk_min_cap, need, sizeof(float))) return -1;
+  }
+  if (!g->topk_ids_stat) DIF_HIP(hipMalloc(&g->topk_ids_stat, sizeof(unsigned long long)));
+  DIF_HIP(hipMemsetAsync(g->topk_ids_stat, 0, sizeof(unsigned long long), st));
+  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int nb = (int)(B - b0 < per ? B - b0 : per);
+    const float* pr = probes + b0 * g->d;
+    if (gtiles > 0) {
+      const int rc = with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(topk_ids_select_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows, g->d,
+                       metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, row_labels,
+                       exclude ? exclude + b0 : nullptr, idx_out + b0 * k, dist_out + b0 * k,
+                       label_out ? label_out + b0 * k : nullptr, g->topk_ids_stat);
     DIF_HIP(hipGetLastError());
   }
   return 0;

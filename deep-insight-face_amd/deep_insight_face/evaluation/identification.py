@@ -6,7 +6,10 @@ calculate_val; here evals.py, utility.py and csrc/evalproto.hip).  `cmc` and `op
 on whatever they are given -- NumPy in, NumPy out; a tensor in, a tensor on its device out, without a kernel of this
 library and without a host round trip.  Conventions (oneshot.Gallery.rank): rank is 0-based, -1 marks an unmated probe
 (nobody enrolled), a mate whose own distance is NaN has rank len(gallery) and a NaN mate_dist.  NaN compares False
-everywhere: a NaN distance passes no threshold."""
+everywhere: a NaN distance passes no threshold.
+
+With several rows per identity the honest rank-k rate counts identities, not rows: `identity_rank` reads a probe's rank off
+the identity-level lists of oneshot.Gallery.topk_ids and feeds `cmc` unchanged; `evaluate_identification_ids` is the run."""
 import numpy as np
 import torch
 
@@ -96,6 +99,56 @@ def evaluate_identification(gallery, probes, mates, distance_metric=1, max_rank=
             out['thresholds'] = _f64(thresholds, rank).reshape(-1)
             out['dir'], out['far'] = open_set_rates(rank, mate_dist, um, out['thresholds'], k=1)
         return out
+    finally:
+        if g is not gallery:
+            g.close()
+
+
+def identity_rank(label_lists, probe_labels, mated):
+    """Rank of the probe's identity in its identity-level list -> [B] int64: the position of probe_labels[b] in
+    label_lists[b] ([B, k], the `label` of Gallery.topk_ids: distinct per row, -1 padding), k when a mated probe's identity
+    is not listed (a miss at every rank the list covers), -1 for an unmated probe (mated[b] False).  Feeds `cmc`."""
+    if torch.is_tensor(label_lists):
+        ll = label_lists
+        pl = torch.as_tensor(probe_labels, device=ll.device).reshape(-1).to(ll.dtype)
+        m = torch.as_tensor(mated, device=ll.device).reshape(-1).to(torch.bool)
+        k = ll.shape[1]
+        hit = (ll == pl[:, None]) & (ll >= 0)
+        pos = torch.arange(k, device=ll.device, dtype=torch.int64)[None, :].expand(ll.shape[0], k)
+        first = torch.where(hit, pos, torch.full_like(pos, k)).amin(1) if k else torch.zeros(ll.shape[0], dtype=torch.int64,
+                                                                                             device=ll.device)
+        return torch.where(m, first, torch.full_like(first, -1))
+    ll = np.asarray(label_lists)
+    pl = np.asarray(probe_labels).reshape(-1)
+    m = np.asarray(mated, dtype=bool).reshape(-1)
+    k = ll.shape[1]
+    hit = (ll == pl[:, None]) & (ll >= 0)
+    first = np.where(hit, np.arange(k, dtype=np.int64)[None, :], k).min(1, initial=k).astype(np.int64)
+    return np.where(m, first, np.int64(-1))
+
+
+def evaluate_identification_ids(gallery, probes, probe_labels, row_labels, distance_metric=1, max_rank=10):
+    """One identity-level 1:N evaluation run: `gallery` an oneshot.Gallery (or the rows to enrol), `probes` [B, d],
+    `probe_labels` [B] and `row_labels` [len(gallery)] integer identities (a negative row label takes the row out).
+
+    One Gallery.topk_ids call with k = max_rank; a probe is mated when its label is among the non-negative row labels.
+    -> {'rank', 'cmc', 'idx', 'dist', 'label'}: rank [B] from `identity_rank` (max_rank: not among the max_rank nearest
+    identities), cmc [max_rank] over the mated probes, and the lists.  NumPy probes give NumPy results, CUDA tensors give
+    CUDA tensors."""
+    from .. import oneshot
+    g = gallery if isinstance(gallery, oneshot.Gallery) else oneshot.Gallery(gallery)
+    try:
+        idx, dist, label = g.topk_ids(probes, max_rank, row_labels, distance_metric)
+        if torch.is_tensor(label):
+            rl = torch.as_tensor(row_labels, device=label.device).reshape(-1).to(torch.int64)
+            pl = torch.as_tensor(probe_labels, device=label.device).reshape(-1).to(torch.int64)
+            mated = torch.isin(pl, rl[rl >= 0])
+        else:
+            rl = np.asarray(row_labels).reshape(-1)
+            pl = np.asarray(probe_labels).reshape(-1)
+            mated = np.isin(pl, rl[rl >= 0])
+        rank = identity_rank(label, pl, mated)
+        return {'rank': rank, 'cmc': cmc(rank, max_rank), 'idx': idx, 'dist': dist, 'label': label}
     finally:
         if g is not gallery:
             g.close()

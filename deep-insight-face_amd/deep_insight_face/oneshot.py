@@ -139,7 +139,7 @@ class Gallery:
         'clamp_nan': 1 reports distance 0 / 1 where the reference's distance is NaN (a similarity rounded
         beyond +-1); the default 0 reports NaN like the reference.  The arg-min is unaffected.
         'topk_seed': tiles of 128 rows the seed stage of `topk` evaluates per probe -- 0 (default): k of them; same results
-        for every value (include/dif.h).
+        for every value (include/dif.h).  `topk_ids` starts its growing seed there.
         'cluster_round': probes per round of `cluster` and `dbscan`, a multiple of 128 -- 0 (default): a sixteenth of the rows, at least 2048; same
         results for every value (include/dif.h).
         'roc_round': probes per round of `roc`, a multiple of 128 -- 0 (default): what its workspace allows; same results for
@@ -154,7 +154,8 @@ class Gallery:
         'frag_copy': 1 when the one-term copy is held in MFMA-fragment order (option 'frag': match_g1_kernel serves);
         'row_bytes': device bytes per row;
         'exact_probes': probes the last match sent to the exact whole-gallery search (synchronises);
-        'roc_resolved': pairs the last `roc` evaluated one by one, too close to a threshold to call (synchronises)."""
+        'roc_resolved': pairs the last `roc` evaluated one by one, too close to a threshold to call (synchronises);
+        'topk_ids_tiles': (probe, 128-row tile) pairs the last `topk_ids` evaluated row by row (synchronises)."""
         v = ctypes.c_int64(0)
         N.check(N.lib.dif_gallery_get_stat(self._h, key.encode(), ctypes.byref(v), N.stream_ptr()), ValueError)
         return int(v.value)
@@ -372,6 +373,80 @@ class Gallery:
         if was_np:
             idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
         return idx, dist
+
+    def topk_ids_into(self, probes, k, distance_metric, row_labels, exclude, idx, dist, label=None):
+        """Allocation-free form of `topk_ids`: `probes` [B, d] float32, `row_labels` [len(self)] int64 and `exclude` [B] int64
+        (or None) CUDA, results written into the caller's CUDA tensors idx [B, k] int64, dist [B, k] float32 and (optional)
+        label [B, k] int64."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        k = int(k)
+        if k < 1 or k > TOPK_MAX:
+            raise ValueError('k %d outside [1, %d]' % (k, TOPK_MAX))
+        if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
+            raise ValueError('probes must be a [B, %d] tensor, got %s' % (
+                self.emd_size, tuple(probes.shape) if hasattr(probes, 'shape') else type(probes).__name__))
+        B, G = probes.shape[0], len(self)
+        for name, t, dt, shape in (('probes', probes, torch.float32, None), ('row_labels', row_labels, torch.int64, (G,)),
+                                   ('exclude', exclude, torch.int64, (B,)), ('idx', idx, torch.int64, (B, k)),
+                                   ('dist', dist, torch.float32, (B, k)), ('label', label, torch.int64, (B, k))):
+            if t is None and name in ('exclude', 'label'):
+                continue
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('topk_ids_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError('topk_ids_into: %s must have shape %s, got %s' % (name, list(shape), tuple(t.shape)))
+        if B:
+            N.check(N.lib.dif_match_topk_ids(self._h, N.ptr(probes), B, distance_metric, k, N.ptr(row_labels) if G else None,
+                                             N.ptr(exclude) if exclude is not None else None, N.ptr(idx), N.ptr(dist),
+                                             N.ptr(label) if label is not None else None, N.stream_ptr()))
+
+    def topk_ids(self, probes, k, row_labels, distance_metric=1, exclude=None):
+        """The k nearest distinct IDENTITIES of each probe, each with its best row, in order, exact.
+        -> (idx[B, k] int64, dist[B, k] float32, label[B, k] int64); NumPy in -> NumPy out.  1 <= k <= 128.
+
+        `row_labels` [len(self)] holds the identity of every enrolled row in the gallery's row order (any integer dtype; the
+        gallery stores none; a negative label takes the row out, as in `roc`); `exclude` [B] (optional) names one identity
+        per probe to leave out, a negative entry none.  Per probe q: ``d = evaluation.utility.distance(q[None, :], gallery,
+        metric)``, the rows with a NaN distance, a negative label or the excluded label dropped, the rest in the order of
+        ``np.argsort(d, kind='stable')``; of every identity only its first -- nearest, on exact ties lowest -- row stays, and
+        the first k of those are listed: idx = row + index_base, dist = d[row], label = row_labels[row].  Fewer than k
+        identities pad with idx -1, dist NaN and label -1.  Distances, units and 'clamp_nan' are `topk`'s.
+
+        With ``exclude`` the probe's own identity the list holds the k nearest OTHER identities (k = 1: the hardest negative).
+        With all-distinct labels idx and dist are `topk`'s bit for bit; with one label the list has one entry, `match`'s row
+        where no distance is NaN.  `stat('topk_ids_tiles')` tells how many tiles the call evaluated row by row."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        k = int(k)
+        if k < 1 or k > TOPK_MAX:
+            raise ValueError('k %d outside [1, %d]' % (k, TOPK_MAX))
+        p, was_np = N.to_device_f32(probes, self._dev)
+        if p.dim() == 1:
+            p = p[None, :]
+        if p.dim() != 2 or p.shape[1] != self.emd_size:
+            raise ValueError('probes must be [B, %d], got %s' % (self.emd_size, tuple(p.shape)))
+        B, G = p.shape[0], len(self)
+
+        def ints(x, name, n):                                   # as `roc` converts its labels
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+            if t.numel() == 0:
+                t = t.to(torch.int64)
+            if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+                raise ValueError('%s must be integers, got %s' % (name, t.dtype))
+            if tuple(t.shape) != (n,):
+                raise ValueError('%s must have shape [%d], got %s' % (name, n, tuple(t.shape)))
+            return t.to(device=self._dev, dtype=torch.int64).contiguous()
+
+        rl = ints(row_labels, 'row_labels', G)
+        ex = None if exclude is None else ints(exclude, 'exclude', B)
+        idx = torch.empty((B, k), dtype=torch.int64, device=self._dev)
+        dist = torch.empty((B, k), dtype=torch.float32, device=self._dev)
+        label = torch.empty((B, k), dtype=torch.int64, device=self._dev)
+        self.topk_ids_into(p, k, distance_metric, rl, ex, idx, dist, label)
+        if was_np:
+            idx, dist, label = idx.cpu().numpy(), dist.cpu().numpy(), label.cpu().numpy()
+        return idx, dist, label
 
     def cluster_into(self, tolerance, distance_metric, labels, n_clusters, first_row=0, prev=None):
         """Allocation-free form of `cluster`: results written into the caller's CUDA tensors labels [G] int64 and n_clusters
@@ -619,6 +694,17 @@ def topk(probes, gallery, k, distance_metric=1):
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
         return g.topk(probes, k, distance_metric)
+    finally:
+        if g is not gallery:
+            g.close()
+
+
+def topk_ids(probes, gallery, k, row_labels, distance_metric=1, exclude=None):
+    """One-call form of Gallery.topk_ids: per probe, the k nearest distinct identities, each with its best row
+    -> (idx[B, k], dist[B, k], label[B, k])."""
+    g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
+    try:
+        return g.topk_ids(probes, k, row_labels, distance_metric, exclude)
     finally:
         if g is not gallery:
             g.close()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_gallery_cluster, gallery option "cluster_round"; + dif_gallery_dbscan; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_match_topk_ids; + dif_gallery_cluster, gallery option "cluster_round"; + dif_gallery_dbscan; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -271,7 +271,7 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * "bd_fill": 1 (default) .. 16: blocks of match_bd_kernel per resident slot (development; no effect measured).
  * "topk_seed": 0 (default) the seed stage of dif_match_topk evaluates the k gallery tiles with the smallest search keys
  * per probe; n > 0 makes it n tiles (1: a loose first tolerance, the sweep stage does the work).  Same answers for every
- * value (tests, A/B).
+ * value (tests, A/B).  dif_match_topk_ids starts its growing seed at the same number.
  * "cluster_round": 0 (default) dif_gallery_cluster (and each sweep of dif_gallery_dbscan) takes a sixteenth of the rows as the probes of one round, in whole blocks
  * of 128 and at least 2048 (a round's MFMA pass stops at its last probe's row: sixteen rounds do 17 / 32 of the square, one
  * round all of it); n > 0, a multiple of 128, makes it n probes.  Either way at most what the census workspace allows (2^27
@@ -288,7 +288,9 @@ int dif_gallery_set_option(dif_gallery* g, const char* key, int value);
  * "frag_copy": 1 when that copy is held in MFMA-fragment order (gallery option "frag");
  * "row_bytes": device bytes held per gallery row; "exact_probes": how many probes the
  * last dif_match on `stream` sent to the exact whole-gallery search (synchronises the stream); "roc_resolved": how many pairs the
- * last dif_match_roc on `stream` evaluated one by one, being too close to a threshold to call (synchronises the stream). */
+ * last dif_match_roc on `stream` evaluated one by one, being too close to a threshold to call (synchronises the stream);
+ * "topk_ids_tiles": how many (probe, 128-row tile) pairs the last dif_match_topk_ids on `stream` evaluated row by row, over
+ * all its probes (synchronises the stream). */
 int dif_gallery_get_stat(dif_gallery* g, const char* key, int64_t* out, void* stream);
 /* top-1 search of n probes [n][d]: idx_out_dev[n] = np.argmin over the reference's float32 distances
  * (int64 global index; first minimum; a row whose reference distance is NaN ranks first, as in
@@ -372,6 +374,38 @@ int dif_match_rank(dif_gallery* g, const float* probes_dev, int n, int metric, c
 #define DIF_TOPK_MAX 128
 int dif_match_topk(dif_gallery* g, const float* probes_dev, int n, int metric, int k, int64_t* idx_out_dev /* [n][k] */,
                    float* dist_out_dev /* [n][k] */, void* stream);
+/* identity-level top-k search of n probes [n][d]: the k nearest distinct IDENTITIES of each probe, each with its best row, in
+ * order, exact.  The gallery stores no labels: row_labels_dev [size] int64 holds them in local row order, as dif_match_roc
+ * takes them; exclude_dev [n] int64 (optional, may be NULL) names one identity per probe to leave out.  Per probe q
+ *     d     = utility.distance(q[None, :], gallery, metric)        the reference's float32 values
+ *     ok    = ~np.isnan(d) & (row_labels >= 0) & (row_labels != exclude[p])
+ *     order = np.argsort(d, kind='stable');  order = order[ok[order]]
+ *     first = order[np.sort(np.unique(row_labels[order], return_index=True)[1])]    each identity's first, i.e. best, row;
+ *     keep  = first[:k]                                                             exact ties go to the lower row
+ *     idx_out_dev[p][0 .. len(keep))   = keep + index_base          (dif_gallery_set's index_base: global indices)
+ *     dist_out_dev[p][0 .. len(keep))  = d[keep]
+ *     label_out_dev[p][0 .. len(keep)) = row_labels[keep]           (optional, may be NULL)
+ *   unused slots -- fewer than k identities with a usable row -- hold idx -1, dist NaN and label -1; an empty gallery gives all
+ *   padding (not an error).  A negative row label takes the row out, as in dif_match_roc.  exclude_dev NULL, or a negative
+ *   entry, excludes nothing; with the probe's own identity excluded the list holds the k nearest OTHER identities (k = 1: the
+ *   hardest negative).  Labels are compared as full int64.  k in [1, DIF_TOPK_MAX]; n = 0 is a no-op; a k outside the range, a
+ *   metric other than 0 / 1 or a NULL handle, probes, idx or dist output (or row labels with rows enrolled) fails.
+ * Units, arithmetic, "clamp_nan" and the NaN rule: dif_match_topk's -- metric 0 bit-identical to the reference; metric 1 up to
+ *   the arccos, so against NumPy two identities whose best distances lie within ~2e-6 of each other may swap, or an identity
+ *   may be reported with another of its rows that close to its best.  On the library's own distances the list is exact on both
+ *   metrics: dif_match_rank of idx_out[p][j] returns dist_out[p][j] as the mate's distance.
+ * Relations: with all-distinct labels the result is dif_match_topk's, bit for bit; with one label the list has one entry,
+ *   dif_match's row where no distance is NaN.
+ * Costs dif_match_topk's MFMA pass, unchanged (a tile's minimum key is taken over all its rows, a lower bound of the minimum
+ *   over the usable ones), plus the reference arithmetic on the tiles that can hold one of the k rows.  The seed stage grows:
+ *   it starts with "topk_seed" tiles (0: k) and doubles while more tiles than that remain below the tolerance of the list so
+ *   far, so a gallery with many rows per identity costs a few dozen tiles per probe, not hundreds.  Same answers for every
+ *   "topk_seed".  dif_gallery_get_stat "topk_ids_tiles" counts the tiles evaluated.  No host synchronisation in steady state;
+ *   shares dif_match_topk's workspace (calls on one stream are ordered) plus one 8-byte counter. */
+int dif_match_topk_ids(dif_gallery* g, const float* probes_dev, int n, int metric, int k,
+                       const int64_t* row_labels_dev /* [size] */, const int64_t* exclude_dev /* [n], or NULL */,
+                       int64_t* idx_out_dev /* [n][k] */, float* dist_out_dev /* [n][k] */,
+                       int64_t* label_out_dev /* [n][k], or NULL */, void* stream);
 /* which enrolled rows are the same person: exact single-linkage clustering of the gallery's own rows at a tolerance, i.e. the
  * connected components of the graph whose edges are the pairs of rows within `tolerance`.  With n = dif_gallery_size:
  *     for i in range(n):                                            every enrolled row is a probe
