@@ -388,7 +388,27 @@ int dif_match_rank(dif_gallery* h, const float* probes_dev, int n, int metric, c
   if (n < 0) return set_error("dif_match_rank: negative probe count");
   if (n == 0) return 0;
   if (!probes_dev || !mate_idx_dev || !rank_out_dev) return set_error("dif_match_rank: null pointer");
-  return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, rank_out_dev, mate_dist_out_dev, (hipStream_t)stream);
+  return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, nullptr, rank_out_dev, mate_dist_out_dev, (hipStream_t)stream);
+}
+
+int dif_match_mate_dist(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev,
+                        float* mate_dist_out_dev, int64_t* owned_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_mate_dist: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_mate_dist: negative probe count");
+  if (n == 0) return 0;
+  if (!probes_dev || !mate_idx_dev || !mate_dist_out_dev || !owned_out_dev) return set_error("dif_match_mate_dist: null pointer");
+  return mate_dist_run(&h->g, probes_dev, n, metric, mate_idx_dev, mate_dist_out_dev, owned_out_dev, (hipStream_t)stream);
+}
+
+int dif_match_rank_at(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev,
+                      const float* mate_dist_in_dev, int64_t* count_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_rank_at: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_rank_at: negative probe count");
+  if (n == 0) return 0;
+  if (!probes_dev || !mate_idx_dev || !mate_dist_in_dev || !count_out_dev) return set_error("dif_match_rank_at: null pointer");
+  return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, mate_dist_in_dev, count_out_dev, nullptr, (hipStream_t)stream);
 }
 
 int dif_match_topk(dif_gallery* h, const float* probes_dev, int n, int metric, int k, int64_t* idx_out_dev,
@@ -489,6 +509,51 @@ int dif_match_merge_packed(const void* packed_dev, int R, int n, int64_t* idx_ou
   const int64_t pitch = (int64_t)n * 16;     // per rank: key[n] f32 | dist[n] f32 | idx[n] i64
   return match_merge_run(base, pitch, base + (size_t)n * 8, pitch, base + (size_t)n * 4, pitch, R, n, idx_out_dev,
                          dist_out_dev, (hipStream_t)stream);
+}
+
+static int check_shards(const char* fn, int R, int n) {
+  if (R < 1 || R > DIF_SHARD_MAX) return set_error("%s: R %d outside [1, %d]", fn, R, DIF_SHARD_MAX);
+  if (n < 0) return set_error("%s: negative probe count", fn);
+  return 0;
+}
+
+int dif_shard_merge_topk(const int64_t* idx_dev, const float* dist_dev, int R, int n, int k, int64_t* idx_out_dev,
+                         float* dist_out_dev, void* stream) {
+  if (check_shards("dif_shard_merge_topk", R, n)) return -1;
+  if (k < 1 || k > DIF_TOPK_MAX) return set_error("dif_shard_merge_topk: k %d outside [1, %d]", k, DIF_TOPK_MAX);
+  if (n == 0) return 0;
+  if (!idx_dev || !dist_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_shard_merge_topk: null pointer");
+  return shard_merge_lists_run(true, nullptr, idx_dev, dist_dev, R, n, k, nullptr, idx_out_dev, dist_out_dev, (hipStream_t)stream);
+}
+
+int dif_shard_merge_topk_ids(const int64_t* idx_dev, const float* dist_dev, const int64_t* label_dev, int R, int n, int k,
+                             int64_t* idx_out_dev, float* dist_out_dev, int64_t* label_out_dev, void* stream) {
+  if (check_shards("dif_shard_merge_topk_ids", R, n)) return -1;
+  if (k < 1 || k > DIF_TOPK_MAX) return set_error("dif_shard_merge_topk_ids: k %d outside [1, %d]", k, DIF_TOPK_MAX);
+  if (n == 0) return 0;
+  if (!idx_dev || !dist_dev || !label_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_shard_merge_topk_ids: null pointer");
+  return shard_merge_ids_run(idx_dev, dist_dev, label_dev, R, n, k, idx_out_dev, dist_out_dev, label_out_dev, (hipStream_t)stream);
+}
+
+int dif_shard_merge_within(const int64_t* count_dev, const int64_t* idx_dev, const float* dist_dev, int R, int n, int max_hits,
+                           int64_t* count_out_dev, int64_t* idx_out_dev, float* dist_out_dev, void* stream) {
+  if (check_shards("dif_shard_merge_within", R, n)) return -1;
+  if (max_hits < 0 || max_hits > DIF_WITHIN_MAX_HITS)
+    return set_error("dif_shard_merge_within: max_hits %d outside [0, %d]", max_hits, DIF_WITHIN_MAX_HITS);
+  if (n == 0) return 0;
+  if (!count_dev || !count_out_dev) return set_error("dif_shard_merge_within: null pointer");
+  if (max_hits > 0 && (!idx_dev || !dist_dev || !idx_out_dev || !dist_out_dev))
+    return set_error("dif_shard_merge_within: null list pointer with max_hits > 0");
+  return shard_merge_lists_run(false, count_dev, idx_dev, dist_dev, R, n, max_hits, count_out_dev, idx_out_dev, dist_out_dev,
+                               (hipStream_t)stream);
+}
+
+int dif_shard_merge_rank(const int64_t* count_dev, const int64_t* owned_dev, const float* mate_dist_dev, int R, int n,
+                         int64_t* rank_out_dev, float* mate_dist_out_dev, void* stream) {
+  if (check_shards("dif_shard_merge_rank", R, n)) return -1;
+  if (n == 0) return 0;
+  if (!count_dev || !owned_dev || !mate_dist_dev || !rank_out_dev) return set_error("dif_shard_merge_rank: null pointer");
+  return shard_merge_rank_run(count_dev, owned_dev, mate_dist_dev, R, n, rank_out_dev, mate_dist_out_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

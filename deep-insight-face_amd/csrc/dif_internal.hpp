@@ -108,8 +108,10 @@ int match_run(Gallery* g, const float* probes, int B, int metric, int64_t* idx_o
               float* key_out, hipStream_t st);
 int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
                int64_t* idx_out, float* dist_out, hipStream_t st);
-int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
-             float* mate_dist_out, hipStream_t st);
+int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, const float* dm_in, int64_t* rank_out,
+             float* mate_dist_out, hipStream_t st);   // dm_in null: dif_match_rank; else dif_match_rank_at (rank_out: the shard's count)
+int mate_dist_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, float* mate_dist_out,
+                  int64_t* owned_out, hipStream_t st);
 int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
 int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, const int64_t* row_labels, const int64_t* exclude,
                  int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st);
@@ -123,5 +125,13 @@ int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D
                  hipStream_t st);
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,
                     int64_t dist_pitch, int R, int B, int64_t* idx_out, float* dist_out, hipStream_t st);   // pitches in bytes
+
+// csrc/match_shard.hip: merges of R per-shard results laid out [R][n][...]
+int shard_merge_lists_run(bool by_dist, const int64_t* count, const int64_t* idx, const float* dist, int R, int n, int L,
+                          int64_t* count_out, int64_t* idx_out, float* dist_out, hipStream_t st);
+int shard_merge_ids_run(const int64_t* idx, const float* dist, const int64_t* label, int R, int n, int k, int64_t* idx_out,
+                        float* dist_out, int64_t* label_out, hipStream_t st);
+int shard_merge_rank_run(const int64_t* count, const int64_t* owned, const float* mate_dist, int R, int n, int64_t* rank_out,
+                         float* mate_dist_out, hipStream_t st);
 
 }  // namespace dif

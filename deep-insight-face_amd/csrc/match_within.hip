@@ -1,5 +1,6 @@
 // Gallery range search: every enrolled row within a tolerance of each probe, exact (dif_match_within), the rank of
-// one given row among all of them (dif_match_rank; its section starts at rank_prep_kernel), and the k nearest rows in order
+// one given row among all of them (dif_match_rank, and its shard-local halves dif_match_mate_dist / dif_match_rank_at for a
+// mate the shard need not hold; the section starts at rank_prep_kernel), and the k nearest rows in order
 // (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), the k nearest distinct
 // identities over a label per row (dif_match_topk_ids; its section follows topk_run), and the connected components
 // of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find),
@@ -96,7 +97,8 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict_
                                                         const float* __restrict__ gallery, int64_t G, int64_t index_base,
                                                         const int64_t* __restrict__ mates, int clamp, const SumPlan plan,
                                                         f32x4* __restrict__ thr, RankMate* __restrict__ mate,
-                                                        float* __restrict__ mate_dist_out) {
+                                                        float* __restrict__ mate_dist_out,
+                                                        const float* __restrict__ dm_in) {
   __shared__ float scratch[4][NP_SCRATCH];
   const int wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
   if (p >= B) return;                                         // (wave-uniform, like everything below)
@@ -108,10 +110,13 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict_
   const bool mated = ml < (uint64_t)G;
   const float inf = __builtin_inff();
   float dm = __builtin_nanf("");
-  if (mated) (void)ref_distance(plan, scratch[wave], q, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
+  // dif_match_rank_at (dm_in): the mate's distance is handed in -- the shard need not hold the mate -- and RankMate.row is
+  // not used: rank_resolve_kernel<true> compares global rows with mates[p] itself
+  if (dm_in) dm = dm_in[p];
+  else if (mated) (void)ref_distance(plan, scratch[wave], q, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
   const float s = probe_sq(q, D, lane);
   if (lane != 0) return;
-  mate[p] = RankMate{dm, mated ? (int)ml : -1};
+  mate[p] = RankMate{dm, dm_in ? 0 : (mated ? (int)ml : -1)};
   if (mate_dist_out) mate_dist_out[p] = dm;
   // unmated, or a NaN distance: every row OUT, nothing to resolve (the third word, H, only ever vetoes SURE, and with
   // thr[0] = -inf nothing is: its value does not matter here)
@@ -122,6 +127,25 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict_
   const Band lo = within_band(metric, nextafterf(dm, -inf), s, D, cdot, sqmax_bits);
   const Band hi = within_band(metric, dm, s, D, cdot, sqmax_bits);
   thr[p] = hi.odd ? f32x4{-inf, inf, hi.H, 1.f} : f32x4{lo.T - lo.E, hi.T + hi.E, hi.H, 0.f};
+}
+
+// dif_match_mate_dist: the ref_distance part of rank_prep_kernel alone, a wave per probe -- the mate's distance where this
+// shard holds the mate (owned 1), NaN and owned 0 where it does not.  No census, no gallery pass.
+__global__ __launch_bounds__(256) void mate_dist_kernel(const float* __restrict__ probes, int B, int D, int metric,
+                                                        const float* __restrict__ gallery, int64_t G, int64_t index_base,
+                                                        const int64_t* __restrict__ mates, int clamp, const SumPlan plan,
+                                                        float* __restrict__ mate_dist_out, int64_t* __restrict__ owned_out) {
+  __shared__ float scratch[4][NP_SCRATCH];
+  const int wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
+  if (p >= B) return;                                         // (wave-uniform, like everything below)
+  const uint64_t ml = (uint64_t)mates[p] - (uint64_t)index_base;   // (unsigned: as in rank_prep_kernel)
+  const bool mated = ml < (uint64_t)G;
+  float dm = __builtin_nanf("");
+  if (mated)
+    (void)ref_distance(plan, scratch[wave], probes + (int64_t)p * D, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
+  if (lane != 0) return;
+  mate_dist_out[p] = dm;
+  owned_out[p] = mated ? 1 : 0;
 }
 
 template <class T>
@@ -284,12 +308,16 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const un
 // memory touched), any other tile -- every tile under the "resolve everything" flag -- is evaluated row by row, a wave per
 // row, and a row counts when it is closer than the mate or ties with it from a lower index.  Every wave keeps the count of
 // its own rows; they meet once, in LDS, at the end.  Which tiles are evaluated is block-uniform (the same LDS words).
+// EXT (dif_match_rank_at): the mate is named by its GLOBAL index mates[p] -- below, inside or above this shard -- and its
+// distance was handed in: there is no "unmated", and a tie counts when the row's global index is below the mate's.
+template <bool EXT>
 __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsigned short* __restrict__ census, int64_t G,
                                                                     int B, const f32x4* __restrict__ thr,
                                                                     const RankMate* __restrict__ mate,
                                                                     const float* __restrict__ probes,
                                                                     const float* __restrict__ gallery, int D, int metric,
                                                                     int clamp, const SumPlan plan,
+                                                                    const int64_t* __restrict__ mates, int64_t index_base,
                                                                     int64_t* __restrict__ rank_out) {
   constexpr int NT = 64 * WITHIN_NW;
   __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
@@ -297,10 +325,11 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
   __shared__ int s_part[WITHIN_NW];
   const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const RankMate mt = mate[p];
-  if (mt.row < 0 || !(mt.dm == mt.dm)) {                      // unmated: -1; the mate's distance is NaN: behind every row
-    if (tid == 0) rank_out[p] = mt.row < 0 ? -1 : G;
+  if ((!EXT && mt.row < 0) || !(mt.dm == mt.dm)) {            // unmated: -1; the mate's distance is NaN: behind every row
+    if (tid == 0) rank_out[p] = (!EXT && mt.row < 0) ? -1 : G;
     return;
   }
+  const int64_t m_ext = EXT ? mates[p] : 0;
   const float dm = mt.dm;
   const float* q = probes + (int64_t)p * D;
   const int64_t gtiles = (G + WITHIN_BM - 1) / WITHIN_BM;
@@ -323,7 +352,8 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
       for (int r = wave; r < rows; r += WITHIN_NW) {
         float d;
         (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
-        mine += (d < dm || (d == dm && g0 + r < mt.row)) ? 1 : 0;   // NaN: neither
+        const bool lower = EXT ? index_base + g0 + r < m_ext : g0 + r < mt.row;
+        mine += (d < dm || (d == dm && lower)) ? 1 : 0;       // NaN: neither
       }
     }
     __syncthreads();                                          // s_word is rewritten by the next round
@@ -401,9 +431,26 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
   return 0;
 }
 
-int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, int64_t* rank_out,
+int mate_dist_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, float* mate_dist_out,
+                  int64_t* owned_out, hipStream_t st) {
+  if (B <= 0) return 0;
+  SumPlan plan;
+  if (make_sum_plan(g->d, &plan)) return -1;
+  hipLaunchKernelGGL(mate_dist_kernel, dim3((B + 3) / 4), dim3(256), 0, st, probes, B, g->d, metric, g->rows, g->n,
+                     g->index_base, mates, g->clamp_nan ? 1 : 0, plan, mate_dist_out, owned_out);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+// `dm_in` null: dif_match_rank.  Not null: dif_match_rank_at -- the mates' distances are the caller's, rank_out receives the
+// shard's count and mate_dist_out is not written.
+int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, const float* dm_in, int64_t* rank_out,
              float* mate_dist_out, hipStream_t st) {
   if (B <= 0) return 0;
+  if (dm_in && g->n <= 0) {                                   // an empty shard counts nothing, whatever dm is (NaN: its size, 0);
+    DIF_HIP(hipMemsetAsync(rank_out, 0, (size_t)B * sizeof(int64_t), st));   // a handle never filled has no sqmax_bits for the band
+    return 0;
+  }
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
@@ -425,15 +472,20 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
     const float* pr = probes + b0 * g->d;
     hipLaunchKernelGGL(rank_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits,
                        g->rows, g->n, g->index_base, mates + b0, clamp, plan, reinterpret_cast<f32x4*>(g->within_thr),
-                       g->rank_mate, mate_dist_out ? mate_dist_out + b0 : nullptr);
+                       g->rank_mate, mate_dist_out ? mate_dist_out + b0 : nullptr, dm_in ? dm_in + b0 : nullptr);
     DIF_HIP(hipGetLastError());
     if (gtiles > 0) {
       const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st); });
       if (rc) return rc;
     }
-    hipLaunchKernelGGL(rank_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
-                       reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
-                       rank_out + b0);
+    if (dm_in)
+      hipLaunchKernelGGL(rank_resolve_kernel<true>, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
+                         reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
+                         mates + b0, g->index_base, rank_out + b0);
+    else
+      hipLaunchKernelGGL(rank_resolve_kernel<false>, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
+                         reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
+                         mates + b0, g->index_base, rank_out + b0);
     DIF_HIP(hipGetLastError());
   }
   return 0;

@@ -78,6 +78,14 @@ SIGNATURES = {
                               c_void_p]),
     'dif_match_merge': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'dif_match_merge_packed': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'dif_shard_merge_topk': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'dif_shard_merge_topk_ids': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    'dif_shard_merge_within': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    'dif_shard_merge_rank': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'dif_match_mate_dist': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dif_match_rank_at': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dif_net_create': (c_int, [P(c_void_p), c_char_p, c_char_p, c_int, c_int, c_int]),
     'dif_net_destroy': (c_int, [c_void_p]),
     'dif_net_param_count': (c_int, [c_void_p]),

@@ -325,6 +325,44 @@ class Gallery:
             rank, mate_dist = rank.cpu().numpy(), mate_dist.cpu().numpy()
         return rank, mate_dist
 
+    def _rank_args(self, fn, probes, arrays):
+        """The checks of the two shard-local rank forms: dense CUDA tensors of the library's own dtypes, [B] each."""
+        if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
+            raise ValueError('probes must be a [B, %d] tensor, got %s' % (
+                self.emd_size, tuple(probes.shape) if hasattr(probes, 'shape') else type(probes).__name__))
+        B = probes.shape[0]
+        for name, t, dt in (('probes', probes, torch.float32),) + tuple(arrays):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('%s: %s must be a contiguous %s tensor on %s' % (fn, name, dt, self._dev))
+            if name != 'probes' and (t.dim() != 1 or t.shape[0] != B):
+                raise ValueError('%s: %s must have shape [%d], got %s' % (fn, name, B, tuple(t.shape)))
+        return B
+
+    def mate_dist_into(self, probes, mates, distance_metric, mate_dist, owned):
+        """The first shard-local half of a sharded `rank` (parallel.ShardedGallery.rank): for `probes` [B, d] float32 and
+        `mates` [B] int64 (global indices) CUDA, writes mate_dist [B] float32 -- the distance to the mate where THIS gallery
+        holds it, NaN where it does not -- and owned [B] int64 (1 / 0).  O(B d): no pass over the gallery."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        B = self._rank_args('mate_dist_into', probes, (('mates', mates, torch.int64), ('mate_dist', mate_dist, torch.float32),
+                                                       ('owned', owned, torch.int64)))
+        if B:
+            N.check(N.lib.dif_match_mate_dist(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(mate_dist),
+                                              N.ptr(owned), N.stream_ptr()))
+
+    def rank_at_into(self, probes, mates, mate_dist, distance_metric, count):
+        """The second half: this gallery's share of the rank of a mate it need not hold.  `mate_dist` [B] float32 is the
+        mate's distance dm, from whichever shard owns it; count [B] int64 receives
+        ``count(d < dm) + count((d == dm) & (index_base + row < mates))`` over this gallery's rows (NaN is never closer;
+        dm NaN gives len(self)).  The counts of disjoint shards add up to `rank` over all their rows."""
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        B = self._rank_args('rank_at_into', probes, (('mates', mates, torch.int64), ('mate_dist', mate_dist, torch.float32),
+                                                     ('count', count, torch.int64)))
+        if B:
+            N.check(N.lib.dif_match_rank_at(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(mate_dist),
+                                            N.ptr(count), N.stream_ptr()))
+
     def topk_into(self, probes, k, distance_metric, idx, dist):
         """Allocation-free form of `topk`: `probes` [B, d] float32 CUDA, results written into the caller's CUDA tensors
         idx [B, k] int64 and dist [B, k] float32."""

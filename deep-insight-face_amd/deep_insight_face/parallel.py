@@ -12,9 +12,19 @@ for the exchange (backend "nccl" is RCCL over xGMI on ROCm; "gloo" on CPU for te
 
 There is no other collective on the data path.  The local compute (steps 1, 3, 5) is the
 HIP library; tests on CPU inject stand-ins for it to exercise steps 2 and 4.
+
+The other gallery queries follow the same pattern -- ShardedGallery.topk, topk_ids, within, rank and roc: all-gather the
+probes (and the per-probe arrays), run the local query on all R*b probes, ONE all-gather of the packed per-rank results,
+merge on the device (merge_topk, merge_topk_ids, merge_within, merge_rank; roc's int64 counts add).  `rank` takes two result
+exchanges: the mate's distance has to reach the shards that do not hold the mate before they can count.  Every answer equals,
+bit for bit, that of one oneshot.Gallery holding all the rows (DESIGN.md has the arguments).  `cluster` and `dbscan` do not
+merge (their edges cross shards); `update` / `remove` need a policy for which rank owns a row: neither is offered here.
 """
+import numpy as np
 import torch
 import torch.distributed as dist
+
+WITHIN_GATHER_MAX = 1 << 30   # bytes of gathered lists ShardedGallery.within accepts (see within_gather_bytes)
 
 
 def shard_bounds(n_rows, world_size, rank):
@@ -56,6 +66,114 @@ def _hip_merge(keys, idx, dists):
     return oi, od
 
 
+def _merge_args(fn, parts):
+    """The stacked per-shard results of a merge: CUDA tensors, dense, of the library's dtypes, and of one leading shape."""
+    first = parts[0][1]
+    for name, t, dt, shape in parts:
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError('%s: %s must be a contiguous %s CUDA tensor' % (fn, name, dt))
+        if t.device != first.device:
+            raise ValueError('%s: %s is on %s, %s on %s' % (fn, name, t.device, parts[0][0], first.device))
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError('%s: %s must have shape %s, got %s' % (fn, name, list(shape), tuple(t.shape)))
+
+
+def merge_topk(idx, dist_):
+    """R per-shard `topk` results stacked [R, n, k] (int64 global indices, float32 distances, -1 / NaN padding behind) -> the
+    whole gallery's (idx [n, k], dist [n, k]): the first k of the union by (distance, global index).  On the device
+    (dif_shard_merge_topk); an R outside [1, 64] or a k outside [1, 128] raises ValueError."""
+    from . import _native as N
+    if not torch.is_tensor(idx) or idx.dim() != 3:
+        raise ValueError('merge_topk: idx must be [R, n, k]')
+    _merge_args('merge_topk', (('idx', idx, torch.int64, None), ('dist', dist_, torch.float32, idx.shape)))
+    R, n, k = idx.shape
+    oi = torch.empty((n, k), dtype=torch.int64, device=idx.device)
+    od = torch.empty((n, k), dtype=torch.float32, device=idx.device)
+    N.check(N.lib.dif_shard_merge_topk(N.ptr(idx), N.ptr(dist_), R, n, k, N.ptr(oi), N.ptr(od), N.stream_ptr()), ValueError)
+    return oi, od
+
+
+def merge_topk_ids(idx, dist_, label):
+    """R per-shard `topk_ids` results stacked [R, n, k] -> (idx, dist, label), each [n, k]: the union by (distance, global
+    index), of every label its first entry, the first k of those; padding -1 / NaN / -1 (dif_shard_merge_topk_ids)."""
+    from . import _native as N
+    if not torch.is_tensor(idx) or idx.dim() != 3:
+        raise ValueError('merge_topk_ids: idx must be [R, n, k]')
+    _merge_args('merge_topk_ids', (('idx', idx, torch.int64, None), ('dist', dist_, torch.float32, idx.shape),
+                                   ('label', label, torch.int64, idx.shape)))
+    R, n, k = idx.shape
+    oi = torch.empty((n, k), dtype=torch.int64, device=idx.device)
+    od = torch.empty((n, k), dtype=torch.float32, device=idx.device)
+    ol = torch.empty((n, k), dtype=torch.int64, device=idx.device)
+    N.check(N.lib.dif_shard_merge_topk_ids(N.ptr(idx), N.ptr(dist_), N.ptr(label), R, n, k, N.ptr(oi), N.ptr(od), N.ptr(ol),
+                                           N.stream_ptr()), ValueError)
+    return oi, od, ol
+
+
+def merge_within(count, idx, dist_):
+    """R per-shard `within` results stacked -- count [R, n], idx and dist [R, n, K] -> (count [n], idx [n, K], dist [n, K]):
+    the counts summed, the K lowest global indices of the union in ascending order, padding -1 / NaN
+    (dif_shard_merge_within).  K may be 0."""
+    from . import _native as N
+    if not torch.is_tensor(idx) or idx.dim() != 3:
+        raise ValueError('merge_within: idx must be [R, n, K]')
+    _merge_args('merge_within', (('idx', idx, torch.int64, None), ('dist', dist_, torch.float32, idx.shape),
+                                 ('count', count, torch.int64, idx.shape[:2])))
+    R, n, K = idx.shape
+    oc = torch.empty((n,), dtype=torch.int64, device=idx.device)
+    oi = torch.empty((n, K), dtype=torch.int64, device=idx.device)
+    od = torch.empty((n, K), dtype=torch.float32, device=idx.device)
+    N.check(N.lib.dif_shard_merge_within(N.ptr(count), N.ptr(idx) if K else None, N.ptr(dist_) if K else None, R, n, K,
+                                         N.ptr(oc), N.ptr(oi) if K else None, N.ptr(od) if K else None, N.stream_ptr()),
+            ValueError)
+    return oc, oi, od
+
+
+def merge_rank(count, owned, mate_dist):
+    """R per-shard results of Gallery.mate_dist_into / rank_at_into stacked [R, n] (int64 counts, int64 0 / 1 owned, float32
+    mate_dist) -> (rank [n] int64, mate_dist [n] float32): the counts summed and the owner's distance, or -1 / NaN where no
+    shard owns the mate.  Were two shards to own it (overlapping shards: not allowed) the lowest rank wins
+    (dif_shard_merge_rank)."""
+    from . import _native as N
+    if not torch.is_tensor(count) or count.dim() != 2:
+        raise ValueError('merge_rank: count must be [R, n]')
+    _merge_args('merge_rank', (('count', count, torch.int64, None), ('owned', owned, torch.int64, count.shape),
+                               ('mate_dist', mate_dist, torch.float32, count.shape)))
+    R, n = count.shape
+    rk = torch.empty((n,), dtype=torch.int64, device=count.device)
+    md = torch.empty((n,), dtype=torch.float32, device=count.device)
+    N.check(N.lib.dif_shard_merge_rank(N.ptr(count), N.ptr(owned), N.ptr(mate_dist), R, n, N.ptr(rk), N.ptr(md),
+                                       N.stream_ptr()), ValueError)
+    return rk, md
+
+
+def within_gather_bytes(world, b, max_hits):
+    """Bytes of the lists ShardedGallery.within gathers on every rank: R records of R*b probes x max_hits slots x 12 bytes."""
+    return int(world) * int(world) * int(b) * int(max_hits) * 12
+
+
+def _pack(parts):
+    """One rank's record: the results of a local query as ONE dense float32 buffer (int64 parts first: they stay 8-byte aligned)."""
+    flat = [t.contiguous().view(-1).view(torch.float32) for t in parts if t.numel()]      # (an empty part has no bytes to view)
+    return torch.cat(flat) if flat else torch.empty((0,), dtype=torch.float32, device=parts[0].device)
+
+
+def _unpack(gathered, specs):
+    """[R, record] float32 -> one dense [R, *shape] tensor per (dtype, shape) of the record."""
+    out, at = [], 0
+    R = gathered.shape[0]
+    for dt, shape in specs:
+        n = int(np.prod(shape, dtype=np.int64)) * (2 if dt == torch.int64 else 1)
+        if n == 0:
+            out.append(torch.empty((R,) + tuple(shape), dtype=dt, device=gathered.device))
+            continue
+        part = torch.empty((R * n,), dtype=torch.float32, device=gathered.device)  # a fresh, aligned block: int64 is viewed on it
+        part.view(R, n).copy_(gathered[:, at:at + n])
+        out.append(part.view(dt).view((R,) + tuple(shape)))
+        at += n
+    return out
+
+
 class ShardedGallery:
     """Row shard of a gallery plus the two collectives around the local match."""
 
@@ -80,10 +198,12 @@ class ShardedGallery:
         if self.force and not dist.is_initialized():
             raise RuntimeError('force_collectives needs torch.distributed.init_process_group first')
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        # (this rank's number; `rank` itself is the query, as on oneshot.Gallery)
+        self.rank_index = dist.get_rank(group) if dist.is_initialized() else 0
         self._match = match_fn
         self._merge = merge_fn
         self._bufs = {}
+        self._seen = set()            # (query, b, d) shapes topk / topk_ids / within / rank / roc have met (check_batch 'first')
         if gallery is not None:
             self.gallery = gallery
         elif match_fn is None:
@@ -181,3 +301,139 @@ class ShardedGallery:
         keys, dists = allrec[:, 0:B].contiguous(), allrec[:, B:2 * B].contiguous()
         ix = allrec[:, 2 * B:4 * B].contiguous().view(torch.int64)
         return (self._merge or _hip_merge)(keys, ix, dists)
+
+    # ---- the other gallery queries: gather the probes, query the shard with all of them, gather the records, merge
+
+    def _local(self):
+        return self.world == 1 and not self.force
+
+    def _begin(self, what, local_probes):
+        """-> (probes [b, d] float32 on the shard's device, NumPy in?, b), the ranks' b compared as `match` does."""
+        if self._match is not None:
+            raise RuntimeError('ShardedGallery.%s needs the HIP gallery (match_fn stand-ins serve `match` only)' % what)
+        from . import _native as N
+        p, was_np = N.to_device_f32(local_probes, self.gallery._dev)
+        if p.dim() == 1:
+            p = p[None, :]
+        if p.dim() != 2 or p.shape[1] != self.gallery.emd_size:
+            raise ValueError('probes must be [b, %d], got %s' % (self.gallery.emd_size, tuple(p.shape)))
+        key = (what, p.shape[0], p.shape[1])
+        self._check_same_batch(p.shape[0], p.device, key not in self._seen)
+        self._seen.add(key)
+        return p, was_np, p.shape[0]
+
+    def _ints(self, x, name, n):
+        """A per-probe (or per-row) integer array, NumPy or torch -> int64 [n] on the shard's device."""
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+        if t.numel() == 0:
+            t = t.to(torch.int64)
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError('%s must be integers, got %s' % (name, t.dtype))
+        if tuple(t.shape) != (n,):
+            raise ValueError('%s must have shape [%d], got %s' % (name, n, tuple(t.shape)))
+        return t.to(device=self.gallery._dev, dtype=torch.int64).contiguous()
+
+    def _gather(self, local):
+        """all_gather_into_tensor of one dense tensor per rank -> [R, *local.shape]."""
+        out = torch.empty((self.world,) + tuple(local.shape), dtype=local.dtype, device=local.device)
+        if local.numel():
+            dist.all_gather_into_tensor(out.view(-1), local.contiguous().view(-1), group=self.group)
+        return out
+
+    @staticmethod
+    def _back(was_np, *ts):
+        return tuple(t.cpu().numpy() for t in ts) if was_np else ts
+
+    def topk(self, local_probes, k, distance_metric=1):
+        """oneshot.Gallery.topk over the whole sharded gallery: -> (idx [R*b, k] int64 global, dist [R*b, k] float32) for the
+        probes of ALL ranks in rank order, identical on every rank and equal, bit for bit, to one Gallery holding every row.
+        Every rank brings its own [b, d] probes (same b).  Exchange: the probes, then one gather of R records of
+        R*b*k*12 bytes; merged on the device (merge_topk)."""
+        if self._local():
+            return self.gallery.topk(local_probes, k, distance_metric)
+        p, was_np, b = self._begin('topk', local_probes)
+        probes = self.all_gather_embeddings(p)
+        B = probes.shape[0]
+        idx, d = self.gallery.topk(probes, k, distance_metric)
+        gi, gd = _unpack(self._gather(_pack([idx, d])), [(torch.int64, (B, k)), (torch.float32, (B, k))])
+        return self._back(was_np, *merge_topk(gi, gd))
+
+    def topk_ids(self, local_probes, k, row_labels, distance_metric=1, exclude=None):
+        """oneshot.Gallery.topk_ids over the whole sharded gallery: -> (idx, dist, label), each [R*b, k], identical on every
+        rank and equal to one Gallery holding every row.  `row_labels` [len(shard)] are THIS shard's labels in its local row
+        order; `exclude` [b] (or None -- on every rank alike) belongs to this rank's probes and is gathered with them.
+        Exchange: the probes, exclude, then one gather of R records of R*b*k*20 bytes (merge_topk_ids)."""
+        if self._local():
+            return self.gallery.topk_ids(local_probes, k, row_labels, distance_metric, exclude)
+        p, was_np, b = self._begin('topk_ids', local_probes)
+        ex = None if exclude is None else self._gather(self._ints(exclude, 'exclude', b)).view(-1)
+        probes = self.all_gather_embeddings(p)
+        B = probes.shape[0]
+        idx, d, lab = self.gallery.topk_ids(probes, k, self._ints(row_labels, 'row_labels', len(self.gallery)),
+                                            distance_metric, ex)
+        gi, gl, gd = _unpack(self._gather(_pack([idx, lab, d])),
+                             [(torch.int64, (B, k)), (torch.int64, (B, k)), (torch.float32, (B, k))])
+        return self._back(was_np, *merge_topk_ids(gi, gd, gl))
+
+    def within(self, local_probes, tolerance, distance_metric=1, max_hits=64):
+        """oneshot.Gallery.within over the whole sharded gallery: -> (count [R*b] int64, idx [R*b, K] int64, dist [R*b, K]
+        float32), K = max_hits, identical on every rank and equal to one Gallery holding every row: the counts are exact, the
+        lists hold the K lowest global rows.  Exchange: the probes, then one gather of R records of R*b*(8 + 12 K) bytes.
+        Every rank receives every shard's lists: R * R*b * max_hits * 12 bytes.  Above 2^30 bytes the call raises ValueError
+        before it allocates anything -- lower max_hits (0 gives the counts alone), or bring fewer probes per step."""
+        if self._local():
+            return self.gallery.within(local_probes, tolerance, distance_metric, max_hits)
+        p, was_np, b = self._begin('within', local_probes)
+        K = int(max_hits)
+        need = within_gather_bytes(self.world, b, K)
+        if need > WITHIN_GATHER_MAX:
+            raise ValueError('ShardedGallery.within: the gathered lists would take %d bytes (%d ranks x %d probes x %d hits x '
+                             '12) > 2^30: lower max_hits' % (need, self.world, self.world * b, K))
+        probes = self.all_gather_embeddings(p)
+        B = probes.shape[0]
+        cnt, idx, d = self.gallery.within(probes, tolerance, distance_metric, K)
+        gc, gi, gd = _unpack(self._gather(_pack([cnt, idx, d])),
+                             [(torch.int64, (B,)), (torch.int64, (B, K)), (torch.float32, (B, K))])
+        return self._back(was_np, *merge_within(gc, gi, gd))
+
+    def rank(self, local_probes, mates, distance_metric=1):
+        """oneshot.Gallery.rank over the whole sharded gallery: -> (rank [R*b] int64, mate_dist [R*b] float32), identical on
+        every rank and equal to one Gallery holding every row.  `mates` [b] are global indices (any shard's; -1 or an index
+        no shard holds: unmated, rank -1).  Two result exchanges, because a shard cannot count against a mate it does not
+        hold: the probes and mates; every shard's (owned, mate_dist) -- R records of R*b*12 bytes -- from which every rank
+        takes the owner's distance; then every shard's count against that distance -- R records of R*b*8 bytes -- summed
+        (merge_rank)."""
+        if self._local():
+            return self.gallery.rank(local_probes, mates, distance_metric)
+        p, was_np, b = self._begin('rank', local_probes)
+        m = self._gather(self._ints(mates, 'mates', b)).view(-1)
+        probes = self.all_gather_embeddings(p)
+        B = probes.shape[0]
+        dev = probes.device
+        md = torch.empty((B,), dtype=torch.float32, device=dev)
+        own = torch.empty((B,), dtype=torch.int64, device=dev)
+        self.gallery.mate_dist_into(probes, m, distance_metric, md, own)
+        g_own, g_md = _unpack(self._gather(_pack([own, md])), [(torch.int64, (B,)), (torch.float32, (B,))])
+        _, dm = merge_rank(torch.zeros_like(g_own), g_own, g_md)        # the owner's distance, on every rank
+        cnt = torch.empty((B,), dtype=torch.int64, device=dev)
+        self.gallery.rank_at_into(probes, m, dm, distance_metric, cnt)
+        return self._back(was_np, *merge_rank(self._gather(cnt), g_own, g_md))
+
+    def roc(self, local_probes, probe_labels, row_labels, thresholds, distance_metric=1, first_row=None):
+        """oneshot.Gallery.roc over the whole sharded gallery and the probes of ALL ranks: -> (accept [T, 2] int64, totals [4]
+        int64) on the device, identical on every rank and equal to one Gallery holding every row queried with all R*b probes.
+        `probe_labels` and `first_row` [b] (or None -- on every rank alike) belong to this rank's probes, `row_labels`
+        [len(shard)] to this shard's rows; `first_row` is a global row index.  `thresholds` must be EQUAL on all ranks: this is
+        not checked, and unequal thresholds add counts that do not belong together.  Exchange: the probes, their labels and
+        first rows, then one gather of R records of (2 T + 4) * 8 bytes; the counts of row shards add."""
+        if self._local():
+            return self.gallery.roc(local_probes, probe_labels, row_labels, thresholds, distance_metric, first_row)
+        p, _, b = self._begin('roc', local_probes)
+        pl = self._gather(self._ints(probe_labels, 'probe_labels', b)).view(-1)
+        fr = None if first_row is None else self._gather(self._ints(first_row, 'first_row', b)).view(-1)
+        probes = self.all_gather_embeddings(p)
+        acc, tot = self.gallery.roc(probes, pl, self._ints(row_labels, 'row_labels', len(self.gallery)), thresholds,
+                                    distance_metric, fr)
+        T = acc.shape[0]
+        s = self._gather(torch.cat([acc.reshape(-1), tot])).sum(0)
+        return s[:2 * T].view(T, 2), s[2 * T:]

@@ -516,6 +516,70 @@ int dif_match_merge(const float* keys_dev, const int64_t* idx_dev, const float* 
  * N>1 step needs one collective for the partial results */
 int dif_match_merge_packed(const void* packed_dev, int R, int n, int64_t* idx_out_dev, float* dist_out_dev,
                            void* stream);
+/* ------------------------------------------------------------------ sharded gallery: the other queries (csrc/match_shard.hip)
+ * A gallery row-sharded over R handles (dif_gallery_set's index_base; disjoint sets of global indices, in any order, not
+ * necessarily contiguous) answers dif_match_topk, dif_match_topk_ids, dif_match_within, dif_match_rank and dif_match_roc
+ * exactly as ONE handle holding all the rows would, bit for bit: every shard runs the local query on all n probes, the
+ * per-shard results are laid out [R][n][...] (each rank's record contiguous: one all-gather per exchange) and merged by the
+ * entries below.  All of them: 1 <= R <= DIF_SHARD_MAX; on the device, nothing read on the host, no atomics, deterministic;
+ * n = 0 is a no-op; an R outside the range, a negative n or a NULL pointer fails.  dif_match_roc needs no entry: its int64
+ * accept [T][2] and totals [4] of row shards add.  dif_gallery_cluster / dif_gallery_dbscan do not merge (their edges cross
+ * shards).
+ * dif_shard_merge_topk: R lists in dif_match_topk's order -- ascending (dist, idx), then -1 / NaN padding -- per probe
+ *     live  = [(dist[r][p][j], idx[r][p][j]) for r, j if idx[r][p][j] >= 0]        a slot with idx < 0 is padding whatever
+ *     keep  = sorted(live)[:k]                                                      its dist says
+ *     idx_out_dev[p][0 .. len(keep)), dist_out_dev[p][0 .. len(keep)) = keep; the other slots idx -1, dist NaN
+ *   Distances of live slots are >= +0 or +inf, never NaN (dif_match_topk lists none); their bit patterns are copied.  Equal to
+ *   dif_match_topk over the whole gallery: a row among the k nearest of all rows is among the k nearest of its shard.
+ *   k in [1, DIF_TOPK_MAX].  Costs R k binary searches of log k steps per list and probe: microseconds.
+ * dif_shard_merge_topk_ids: the same with one entry per label: of sorted(live), an entry stays only if no earlier entry carries
+ *   its label; the first k of those, then idx -1, dist NaN, label -1.  label_out_dev may be NULL.  Equal to dif_match_topk_ids
+ *   over the whole gallery (every shard queried with the same exclude): an identity of the whole-gallery list has its best row in
+ *   some shard, where fewer than k identities are ahead of it, so that shard lists it at its true distance; any other entry
+ *   stands at a distance no better than its identity's true one and displaces nothing.  The lists are folded one at a time
+ *   into a k-entry accumulator in LDS, which gives the same list (csrc/match_shard.hip has the argument).
+ * dif_shard_merge_within: count_out_dev[p] = sum over r of count_dev[r][p]; the list is the max_hits LOWEST global indices of
+ *   the union of the R lists (each ascending by index, padding behind), ascending, with their distances, then -1 / NaN -- for
+ *   contiguous shards in rank order the concatenation.  max_hits in [0, DIF_WITHIN_MAX_HITS]; with 0 only the counts are
+ *   produced and the four list pointers may be NULL.
+ * dif_shard_merge_rank: consumes the per-shard outputs of dif_match_mate_dist and dif_match_rank_at (below).  Per probe:
+ *     owner = the LOWEST r with owned_dev[r][p] != 0     (disjoint shards: at most one; overlapping shards are not allowed,
+ *                                                          the rule only makes the kernel total)
+ *     rank_out_dev[p]      = sum over r of count_dev[r][p], or -1 without an owner      (unmated, as dif_match_rank)
+ *     mate_dist_out_dev[p] = mate_dist_dev[owner][p], or NaN without an owner           (optional, may be NULL)
+ *   With count_dev all zeros it only selects the owner's distance: the step between the two local calls. */
+#define DIF_SHARD_MAX 64
+int dif_shard_merge_topk(const int64_t* idx_dev /* [R][n][k] */, const float* dist_dev /* [R][n][k] */, int R, int n, int k,
+                         int64_t* idx_out_dev /* [n][k] */, float* dist_out_dev /* [n][k] */, void* stream);
+int dif_shard_merge_topk_ids(const int64_t* idx_dev /* [R][n][k] */, const float* dist_dev /* [R][n][k] */,
+                             const int64_t* label_dev /* [R][n][k] */, int R, int n, int k, int64_t* idx_out_dev /* [n][k] */,
+                             float* dist_out_dev /* [n][k] */, int64_t* label_out_dev /* [n][k], or NULL */, void* stream);
+int dif_shard_merge_within(const int64_t* count_dev /* [R][n] */, const int64_t* idx_dev /* [R][n][max_hits] */,
+                           const float* dist_dev /* [R][n][max_hits] */, int R, int n, int max_hits,
+                           int64_t* count_out_dev /* [n] */, int64_t* idx_out_dev /* [n][max_hits] */,
+                           float* dist_out_dev /* [n][max_hits] */, void* stream);
+int dif_shard_merge_rank(const int64_t* count_dev /* [R][n] */, const int64_t* owned_dev /* [R][n] */,
+                         const float* mate_dist_dev /* [R][n] */, int R, int n, int64_t* rank_out_dev /* [n] */,
+                         float* mate_dist_out_dev /* [n], or NULL */, void* stream);
+/* rank against a mate the shard need not hold: dif_match_rank forms dm from its own row m; a shard without m is handed dm.
+ * dif_match_mate_dist: only the mate's distance.  Per probe q with m = mate_idx_dev[p] (int64 GLOBAL index):
+ *     owned_out_dev[p]     = 1 if index_base <= m < index_base + size else 0          (int64)
+ *     mate_dist_out_dev[p] = utility.distance(q, gallery[m - index_base], metric) where owned, NaN where not
+ *   bit-identical to dif_match_rank's mate_dist, under the handle's "clamp_nan"; it may be NaN where owned as well
+ *   (dif_match_rank's NaN-mate case).  Costs O(n d): no census, no pass over the gallery.
+ * dif_match_rank_at: the shard's share of the rank.  With d the shard's reference distances, dm = mate_dist_in_dev[p] and
+ *   row the LOCAL row number:
+ *     count_out_dev[p] = count(d < dm) + count((d == dm) & (index_base + row < m))    NaN compares False: never closer
+ *   m is compared as a full int64 and may lie below, inside or above the shard (a mate of -1 or beyond every shard is
+ *   legal here: "unmated" is decided by dif_shard_merge_rank, from owned).  dm NaN gives count = dif_gallery_size.  Summed over
+ *   disjoint shards that is dif_match_rank's count(d < dm) + count(d[:m] == dm) over the whole gallery, and with dm NaN its size.
+ *   The kernels, thresholds, arithmetic and cost are dif_match_rank's (the mate's distance is read, not computed; the tie
+ *   test is on the global row); it shares that call's workspace (calls on one stream are ordered).  An empty shard gives 0.
+ * n = 0 is a no-op; a metric other than 0 / 1 or a NULL handle or pointer fails. */
+int dif_match_mate_dist(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
+                        float* mate_dist_out_dev /* [n] */, int64_t* owned_out_dev /* [n]: 0 / 1 */, void* stream);
+int dif_match_rank_at(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
+                      const float* mate_dist_in_dev /* [n] */, int64_t* count_out_dev /* [n] */, void* stream);
 
 /* ------------------------------------------------------------------ embedding network
  * Stands behind the Keras model object of the reference:
