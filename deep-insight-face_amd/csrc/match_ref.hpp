@@ -8,7 +8,12 @@
 
 namespace dif {
 
-constexpr int NP_PLANE = 72;    // LDS floats a wave needs for one np_sum: 64 leaf sums + the combine stack
+// NumPy's tree over n <= 8192 elements has at most 65 leaves (441 sizes in [7689, 8191], e.g. 8191 = 4088 | 4103 -> ... ->
+// 128 | 64 | 71; a power of two has n / 128) and keeps at most 7 partial sums on the combine stack
+// (tests/test_oracle_golden.py walks every size); make_sum_plan fails on a tree that exceeds either.
+constexpr int NP_LEAVES = 72;   // leaf capacity of a SumPlan (np_sum runs eight leaves per pass)
+constexpr int NP_STACK = 8;     // combine-stack capacity
+constexpr int NP_PLANE = NP_LEAVES + NP_STACK;   // LDS floats a wave needs for one np_sum: the leaf sums + the combine stack
 constexpr int NP_SCRATCH = 3 * NP_PLANE;   // np_sum3 runs three sums side by side (the cosine distance's dot, |a|^2, |b|^2)
 constexpr float NORM_LO = 1e-30f, NORM_HI = 1e30f;   // |x|^2 range inside which the filter's error bounds hold
 
@@ -24,8 +29,8 @@ constexpr float NORM_LO = 1e-30f, NORM_HI = 1e30f;   // |x|^2 range inside which
 // np.sum bit for bit; tests/test_match_gpu.py checks the device against NumPy.
 struct SumPlan {
   int nleaf;
-  unsigned short start[64], len[64];
-  unsigned char pops[64];
+  unsigned short start[NP_LEAVES], len[NP_LEAVES];
+  unsigned char pops[NP_LEAVES];
 };
 
 int make_sum_plan(int d, SumPlan* out);   // match.hip
@@ -62,9 +67,9 @@ __device__ __forceinline__ float np_sum(const SumPlan& plan, float* scratch, int
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  // the stack machine, run by every lane on the same values (the stack lives in scratch[64..71]:
-  // depth <= log2(64) + 1; identical stores to one address are benign)
-  float* stack = scratch + 64;
+  // the stack machine, run by every lane on the same values (the stack lives behind the leaf sums, NP_STACK deep:
+  // make_sum_plan checks the depth; identical stores to one address are benign)
+  float* stack = scratch + NP_LEAVES;
   int sp = 0;
   float top = 0.f;
 #pragma unroll 1
@@ -135,7 +140,7 @@ __device__ __forceinline__ F3 np_sum3(const SumPlan& plan, float* scratch, int l
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  float* stack = scratch + 64;
+  float* stack = scratch + NP_LEAVES;
   int sp = 0;
   F3 top = {0.f, 0.f, 0.f};
 #pragma unroll 1

@@ -60,7 +60,14 @@ int dif_probe_mfma_clock(double* ghz_out, double* tflops_out, void* stream);
  * broadcast of a single row, which is how a probe is compared with a whole gallery
  * in the reference's terms).  Replaces evaluation/utility.py:52-66 `distance`
  * (and its twin :174-188).  metric other than 0/1 fails like the reference's
- * RuntimeError('Undefined distance metric %d').  NaN where the reference gives NaN. */
+ * RuntimeError('Undefined distance metric %d').  NaN where the reference gives NaN.
+ * d in [1, 8192] (anything else fails with "outside [1, 8192]"): metric 0 and DIF_METRIC_SIMILARITY are NumPy's float32
+ * result bit for bit at every such d -- the sums follow NumPy's pairwise-summation tree, which has at most 65 leaves of <= 128
+ * elements there (65 at 441 sizes of [7689, 8191], none a multiple of 32) -- and metric 1 within 4 ulp of it.  Tested at
+ * every d in 1..300, at sizes up to 8192 and at thirteen of the 65-leaf sizes; the gallery queries below at d = 96, 160, 288
+ * (two-term filter), 320, 640, 1024, 2048, 8192 (one-term row-major filter) besides the sizes up to 512; dif_arcmargin_logits
+ * at d = 32, 96, 1024, 2048 within s u ((d + 2) A + (d / 64 + 9) |c|) of the float64 value, u = 2^-24, c the cosine,
+ * A = sum |e_k w_k| / (|e| |w|) <= 1. */
 int dif_pairwise(const float* e1_dev, int64_t n1, const float* e2_dev, int64_t n2, int d, int metric,
                  float* out_dev, void* stream);
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import arcmargin_bounds as ab
 from oracle import distance as od
 from oracle import nets
 
@@ -206,6 +207,54 @@ def test_arcmargin_vs_oracle(cuda):
         np.testing.assert_allclose(gotm, wantm, atol=64 * 2e-5)
         assert np.array_equal(np.argmax(got, 1), np.argmax(want, 1))
         head.close()
+
+
+def _arcmargin_logits(e, w, labels, s, m):
+    from deep_insight_face.networks.arcmargin import ArcMarginHead
+    head = ArcMarginHead(w, s=s, m=m)
+    plain, labelled = head.logits(e), head.logits(e, labels)
+    head.close()
+    return plain, labelled
+
+
+@pytest.mark.parametrize('B,C,D,s,m', [shape + ab.HEADS[0] for shape in ab.SHAPES] + [ab.SHAPES[1] + ab.HEADS[1]])
+def test_arcmargin_embedding_sizes(cuda, B, C, D, s, m):
+    """Plain and labelled logits against the float64 oracle at D = 32, 96, 1024, 2048 (K loops of 1 to 64 steps) with tails in
+    both tile dimensions of Tile<2, 2>, and one head with s = 30, m = 0.3.  The gates are derived from the kernel's operations
+    in tests/arcmargin_bounds.py -- a D-term float32 multiply-add chain, two inverse norms, two products: s u ((D + 2) A +
+    (D / 64 + 9) |c|) per logit, and the existing 64 TOL / 64 * 2e-5 where that is smaller -- and the oracle's formula
+    evaluated in float32 by NumPy meets them as well (tests/test_arcmargin_bounds.py, without a GPU).  The arg-max must be the
+    oracle's wherever its best two logits lie further apart than twice the bound."""
+    e, w, labels = ab.general_case(B, C, D)
+    want = nets.arcmargin_logits(e.astype(np.float64), w.astype(np.float64), labels, s=s, m=m)
+    gate_w, _ = ab.plain_gate(e, w, s)                          # the module's float64 cosines are the oracle's
+    np.testing.assert_allclose(gate_w, nets.arcmargin_logits(e.astype(np.float64), w.astype(np.float64), s=s, m=m), rtol=0, atol=1e-9)
+    rows = np.arange(B)
+    np.testing.assert_allclose(ab.label_gate(e, w, labels, s, m)[0], want[rows, labels], rtol=0, atol=1e-9)
+    plain, labelled = _arcmargin_logits(e, w, labels, s, m)
+    ab.check_general(plain, labelled, e, w, labels, s, m)
+
+
+def test_arcmargin_planted_label_columns(cuda):
+    """D = 128, C = 70, one row or more per branch of the label column's epilogue: e = 3 w[label] and twelve more multiples (c
+    = 1: the sine's clamp), e = -2 w[label] and twelve more (c = -1: the fallback branch c - mm), c = th +- 1e-3 (a row on each
+    side of the threshold), a zero embedding, a zero class centre as the label (finite, the oracle's max(sum, 1e-12)), labels
+    -1 and C (no column moves).  s = 64 is a power of two, so plain / s is the device's cosine exactly: the label column
+    must be the float64 margin formula at that cosine within s (sm (sqrt(x + 4u) - sqrt(max(x - 4u, 0))) + |cm| u + 8u), x =
+    max(1 - c^2, 0), on the branch the cosine names -- the two branches lie more than 0.1 apart everywhere -- and every
+    other column the plain call's bit for bit."""
+    e, w, labels = ab.planted_case()
+    plain, labelled = _arcmargin_logits(e, w, labels, ab.PLANT_S, ab.PLANT_M)
+    ab.check_planted(plain, labelled, e, w, labels)
+    # against the oracle itself, where it takes the labels
+    ok = (labels >= 0) & (labels < ab.PLANT_C)
+    want = nets.arcmargin_logits(e[ok].astype(np.float64), w.astype(np.float64), labels[ok], s=ab.PLANT_S, m=ab.PLANT_M)
+    rows = np.flatnonzero(ok)
+    for name in ('zero_embedding', 'zero_centre', 'above_th', 'below_th'):
+        r = ab.PLANT_ROWS.index(name)
+        k = int(np.flatnonzero(rows == r)[0])
+        assert np.isfinite(want[k]).all()
+        assert abs(labelled[r, labels[r]] - want[k, labels[r]]) <= ab.label_gate(e[r:r + 1], w, labels[r:r + 1], ab.PLANT_S, ab.PLANT_M)[1][0], name
 
 
 def test_arcmargin_full_size_properties(cuda):

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import embed_dims as ed
 import golden_inputs as gi
 from oracle import distance as od
 from oracle import evalproto as oe
@@ -135,6 +136,13 @@ def test_numpy_summation_order_restated():
         want = np.sum(a, axis=1)
         got = np.array([od.np_pairwise_sum(r) for r in a])
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), d
+    # the large sizes dif_pairwise admits (tests/test_embed_dims_gpu.py runs the device at the same ones), on squares: the
+    # terms of the distances
+    for d in ed.PAIR_LARGE + ed.PAIR_65:
+        a = np.square(rng.standard_normal((3, d)).astype(np.float32))
+        want = np.sum(a, axis=1)
+        got = np.array([od.np_pairwise_sum(r) for r in a])
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), d
     # the three sums of the cosine distance, as the reference forms them (products rounded first)
     q = rng.standard_normal((1, 512)).astype(np.float32)
     gal = rng.standard_normal((20, 512)).astype(np.float32)
@@ -143,6 +151,35 @@ def test_numpy_summation_order_restated():
     for r in range(20):
         assert od.np_pairwise_sum(q[0] * gal[r]) == dot[r]
         assert np.sqrt(od.np_pairwise_sum(gal[r] * gal[r])) == nrm[r]
+
+
+def test_summation_tree_has_65_leaves_at_most():
+    """The tree of np_pairwise_sum, flattened as the device holds it (csrc/match_ref.hpp: SumPlan; NP_LEAVES and NP_STACK size
+    it): over every size dif_pairwise admits it has at most 65 leaves and keeps at most 7 partial sums, and 65 -- one more than
+    the 8192 / 128 of the largest size -- at 441 sizes, all in [7689, 8191] and none a multiple of 32 (no gallery has one).
+    The sizes of embed_dims.PAIR_65 are among them: that is why the device test runs them.  The flattened plan gives np.sum's
+    bits; cut off at 64 leaves (its last leaf takes the rest, 129 to 135 elements) it does not."""
+    leaves = {n: len(ed.pairwise_plan(n)) for n in range(1, 8193)}
+    assert max(leaves.values()) == 65 and leaves[8192] == 64 and leaves[128] == 1 and leaves[129] == 2
+    n65 = [n for n, c in leaves.items() if c == 65]
+    assert len(n65) == 441 and n65[0] == 7689 and n65[-1] == 8191 and all(n % 32 for n in n65)
+    assert max(ed.plan_stack_depth(ed.pairwise_plan(n)) for n in range(1, 8193)) == 7
+    assert len(ed.PAIR_65) >= 12 and {7689, 7690, 8185, 8191} <= set(ed.PAIR_65)
+    cut_differs = 0
+    for d in ed.PAIR_65:
+        plan = ed.pairwise_plan(d)
+        assert leaves[d] == 65 and all(1 <= ln <= 128 for _, ln, _ in plan), d
+        assert [s for s, _, _ in plan] == list(np.cumsum([0] + [ln for _, ln, _ in plan[:-1]])) and sum(ln for _, ln, _ in plan) == d
+        a, b = ed.pair_rows(d)                                 # the device test's rows
+        cut = [list(p) for p in plan[:64]]                     # what a 64-leaf plan held: 128 | 64 | 71 -> 128 | 135
+        cut[63][1] += plan[64][1]
+        cut[63][2] = plan[64][2] - 1
+        assert ed.plan_stack_depth(cut) <= 7
+        sq = np.square(a - b)
+        want = np.sum(sq, axis=1)
+        assert np.array_equal(ed.plan_sum(plan, sq).view(np.uint32), want.view(np.uint32)), d
+        cut_differs += int((ed.plan_sum(cut, sq).view(np.uint32) != want.view(np.uint32)).sum())
+    assert cut_differs >= 5                                    # about one row in twenty of these 13 x 64: the rows see the cut
 
 
 def test_degenerate_fixture(golden_dir):

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import embed_dims as ed
 import golden_inputs as gi
 import rank_ref
 import topk_ids_ref as ir
@@ -114,7 +115,7 @@ def _labellings(G):
             'one': np.zeros(G, dtype=np.int64)}
 
 
-@pytest.mark.parametrize('B,G,D', SHAPES + [(70, 4097, 128)])
+@pytest.mark.parametrize('B,G,D', SHAPES + [(70, 4097, 128)] + list(ed.QUERY_SHAPES))
 def test_clear_shares_of_the_shapes(B, G, D):
     """The cap test_topk_ids_gpu.py asserts per case, on the oracle alone (metric 1; metric 0 compares bit for bit): every
     labelling, with and without the probe's own identity excluded."""

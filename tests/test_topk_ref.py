@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import embed_dims as ed
 import golden_inputs as gi
 import rank_ref
 import topk_ref
@@ -95,7 +96,7 @@ def _inputs(B, G, D, seed=0):
     return probes, gal, pick
 
 
-@pytest.mark.parametrize('B,G,D', SHAPES + [(70, 4097, 128)])
+@pytest.mark.parametrize('B,G,D', SHAPES + [(70, 4097, 128)] + list(ed.QUERY_SHAPES))
 def test_clear_shares_of_the_shapes(B, G, D):
     """The cap test_topk_gpu.py asserts per case, on the oracle alone (metric 1; metric 0 compares bit for bit)."""
     probes, gal, _ = _inputs(B, G, D)
