@@ -39,6 +39,7 @@ SIGNATURES = {
     'dif_nms': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
                         c_void_p, c_void_p]),
     'dif_letterbox': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'dif_letterbox_extent': (c_int, [c_int, c_int, c_int, P(c_int), P(c_int)]),
     'dif_crop_resize': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p]),
     'dif_area_resize': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     'dif_crop_resize_multi': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p]),

@@ -101,10 +101,20 @@ def letterbox_image(image: Image.Image, size: typing.Tuple[int, int]) -> Image.I
     return canvas
 
 
+def letterbox_extent(h: int, w: int, size: int = 416) -> typing.Tuple[int, int]:
+    """(nw, nh): the resized extent ``letterbox_image`` and ``letterbox_batch`` give an h x w frame on a size x size
+    canvas (dif_letterbox_extent; no device needed).  The picture starts at column (size - nw) // 2, row (size - nh) // 2."""
+    nw, nh = ctypes.c_int(0), ctypes.c_int(0)
+    N.check(N.lib.dif_letterbox_extent(int(h), int(w), int(size), ctypes.byref(nw), ctypes.byref(nh)), ValueError)
+    return nw.value, nh.value
+
+
 def letterbox_batch(frames, size: int = 416) -> torch.Tensor:
     """``letterbox_image`` for a whole batch on the device: uint8 [N,H,W,3] (ndarray or tensor)
-    -> uint8 CUDA tensor [N,size,size,3] (dif_letterbox; PIL BICUBIC semantics, rounding may
-    differ from PIL's fixed-point passes by one grey level)."""
+    -> uint8 CUDA tensor [N,size,size,3] (dif_letterbox).  The resized extent is ``letterbox_image``'s at every
+    frame size -- computed in double, as Python computes it (``letterbox_extent``) -- so picture, offsets and grey bars
+    lie where PIL puts them; the resampling restates PIL's 8-bit BICUBIC passes (antialiasing, double weights rounded
+    to 22-bit fixed point, an 8-bit image between the passes) and gives PIL's bytes."""
     dev = N.require_device()
     t = torch.from_numpy(np.ascontiguousarray(frames)) if not torch.is_tensor(frames) else frames
     if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8:

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_match_topk_ids; + dif_gallery_cluster, gallery option "cluster_round"; + dif_gallery_dbscan; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap (additions: no entry point changed, the number stays) */
+#define DIF_VERSION 110 /* 1.1: + dif_gallery_update / _reserve / _capacity, dif_*_option_name, options "sk2", "mt"; gallery option "frag"; + dif_match_within, dif_match_rank; + dif_gallery_remove; + dif_match_topk, gallery option "topk_seed"; + dif_match_topk_ids; + dif_gallery_cluster, gallery option "cluster_round"; + dif_gallery_dbscan; + dif_match_roc, gallery option "roc_round"; + dif_net_op_describe, dif_net_embed_tap; + dif_letterbox_extent (additions: no entry point changed, the number stays) */
 
 /* distance metrics: evaluation/utility.py:52-66 */
 #define DIF_METRIC_SQL2 0   /* sum((a-b)^2, axis=1)                     utility.py:53-56 */
@@ -104,10 +104,20 @@ int dif_nms(const float* boxes_dev, const float* scores_dev, int n_images, int n
 /* Image resampling around the detector, uint8 NHWC in and out.
  * dif_letterbox: aspect-preserving BICUBIC resize (PIL semantics incl. antialiasing) onto a
  *   size x size canvas of (128,128,128)                       detector/yolov3.py:108-119
+ *   PIL's 8-bit arithmetic operation by operation: weights in double, normalised, rounded to 22-bit fixed point, int32
+ *   sums, an 8-bit image between the horizontal and the vertical pass -- PIL's bytes (tested against Pillow 12)
  * dif_crop_resize: per frame, box (left, top, right, bottom) + margin/2 per side, clamped
  *   (detector/run.py:63-87), resampled to size x size by area coverage (cv2 INTER_AREA, which is what
- *   predictions.py:93,154 selects); an empty / NaN box gives a black crop. */
+ *   predictions.py:93,154 selects); an empty / NaN box gives a black crop.
+ * dif_letterbox_extent: where the picture lies on dif_letterbox's canvas.  nw_out / nh_out (HOST pointers) = the resized
+ *   extent, exactly the reference's  scale = min(size / w, size / h); nw = int(w * scale); nh = int(h * scale)  in Python's
+ *   floats (IEEE double, one rounding per operation; float32 gives another pixel count at 8 % of the frame sizes up to
+ *   640 x 640 -- 1280 x 720 is 416 x 234 in the reference and 416 x 233 in float32).  The picture occupies columns
+ *   [(size - nw) / 2, (size - nw) / 2 + nw) and rows [(size - nh) / 2, (size - nh) / 2 + nh) (integer division), the rest is
+ *   grey; dif_letterbox resamples with the factors w / nw and h / nh.  No device call; fails as dif_letterbox does: "bad
+ *   sizes" for h, w or size < 1, "image too thin" where an axis comes to 0 pixels (PIL rejects that resize too). */
 int dif_letterbox(const uint8_t* frames_dev, int n, int h, int w, uint8_t* out_dev, int size, void* stream);
+int dif_letterbox_extent(int h, int w, int size, int* nw_out, int* nh_out);
 int dif_crop_resize(const uint8_t* frames_dev, int n, int h, int w, const float* boxes_ltrb_dev, float margin,
                     uint8_t* out_dev, int size, void* stream);
 /* dif_area_resize: whole images [n][h][w][3] -> [n][out_h][out_w][3] by the same area coverage: the

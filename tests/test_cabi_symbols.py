@@ -20,7 +20,7 @@ def declared():
 def test_header_declares_the_path():
     names = declared()
     for must in ('dif_pairwise', 'dif_gallery_set', 'dif_match', 'dif_match_merge', 'dif_net_create',
-                 'dif_net_embed', 'dif_arcmargin_logits', 'dif_last_error'):
+                 'dif_net_embed', 'dif_arcmargin_logits', 'dif_last_error', 'dif_letterbox', 'dif_letterbox_extent'):
         assert must in names
 
 
