@@ -1,0 +1,536 @@
+// hipcc-flags: -ffp-contract=off
+// (the reduction and the finish restate NumPy's float32 arithmetic operation by operation: a product is rounded before
+// it is added, and match_ref.hpp asks for this flag of every translation unit that includes it)
+// Template pooling: one exact mean embedding per identity (include/dif.h, "template pooling").
+//   group   pool_stats_kernel      OR of the non-negative labels and of their complements: a bit that is set in both
+//                                  varies, a byte without such a bit is constant and its sort pass is skipped
+//           pool_init_kernel       (key, position) pairs -- the t0 state labels in front of the n new ones, every negative
+//                                  label mapped to ONE key above all others -- and the plan of the eight passes
+//           pool_hist_kernel       } one stable LSD radix pass on an 8-bit digit: a histogram per block of kSortTile keys,
+//           pool_scan_kernel       } an exclusive scan over [digit][block] by one block, and a scatter that ranks every
+//           pool_scatter_kernel    } key among the equal digits in front of it in its block (ballots inside a wave, per-wave
+//                                  counters across the waves).  All eight passes are enqueued; a skipped one returns at
+//                                  once, and which of the two buffers a pass reads is part of the plan in device memory
+//           pool_heads_kernel      segment heads per block of kHeadBlock sorted keys (pool_scan_kernel scans them)
+//           pool_index_kernel      template number of every key -> index_out, the start of every segment, T
+//   reduce  pool_reduce_kernel     one thread per (segment, float4 column): the segment's rows in sorted -- that is, row --
+//                                  order into ONE accumulator, the loads of kLookAhead rows issued in front of their
+//                                  adds and their positions a chunk earlier
+//   finish  pool_finish_kernel     one wave per template: sums / divisor, and the row's norm in NumPy's order (np_sum)
+// The only atomics are the ORs of pool_stats_kernel and LDS counters whose totals do not depend on the order; every
+// output is a function of the input alone.
+#include "../../include/dif.h"
+#include "match_ref.hpp"
+#include <new>
+
+namespace dif {
+
+constexpr int kSortThreads = 256;
+constexpr int kSortWaves = kSortThreads / 64;
+constexpr int kSortItems = 8;                               // keys per thread and pass
+constexpr int kSortTile = kSortThreads * kSortItems;        // keys per block and pass
+constexpr int kScanThreads = 1024;
+constexpr int kHeadBlock = 256;                             // sorted keys per block of pool_heads_kernel / pool_index_kernel
+constexpr int kLookAhead = 16;                              // rows of a segment in flight in pool_reduce_kernel
+constexpr unsigned long long kNegBit = 1ull << 63;
+
+struct PoolMeta {
+  unsigned long long or_all, nor_all;   // OR of the non-negative labels, OR of their complements
+  int any_neg, any_nonneg;
+  int active[8], src[8];                // per pass: does it run, and which buffer holds its input
+  int final_buf, pad;                   // the buffer that holds the sorted pairs
+  long long T;                          // templates after the group
+};
+
+__device__ __forceinline__ int64_t pool_label(const int64_t* __restrict__ state, int t0, const int64_t* __restrict__ labels, int i) {
+  return i < t0 ? state[i] : labels[i - t0];
+}
+
+__global__ __launch_bounds__(256) void pool_stats_kernel(const int64_t* __restrict__ state, int t0, const int64_t* __restrict__ labels, int m,
+                                                         PoolMeta* __restrict__ meta) {
+  unsigned long long o = 0, no = 0;
+  int neg = 0, nonneg = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+    const int64_t l = pool_label(state, t0, labels, (int)i);
+    if (l < 0) {
+      neg = 1;
+    } else {
+      o |= (unsigned long long)l;
+      no |= ~(unsigned long long)l;
+      nonneg = 1;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    o |= __shfl_xor(o, off);
+    no |= __shfl_xor(no, off);
+    neg |= __shfl_xor(neg, off);
+    nonneg |= __shfl_xor(nonneg, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (o) atomicOr(&meta->or_all, o);
+    if (no) atomicOr(&meta->nor_all, no);
+    if (neg) atomicOr(&meta->any_neg, 1);
+    if (nonneg) atomicOr(&meta->any_nonneg, 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void pool_init_kernel(const int64_t* __restrict__ state, int t0, const int64_t* __restrict__ labels, int m,
+                                                        PoolMeta* __restrict__ meta, unsigned long long* __restrict__ keys,
+                                                        int* __restrict__ pos) {
+  const unsigned long long or_all = meta->or_all, nor_all = meta->nor_all;
+  // every negative label becomes one key: above every label by its top bit, equal to the labels in each byte that is
+  // constant over them, so that it adds no pass but the last
+  const unsigned long long negkey = kNegBit | ~nor_all;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+    const int64_t l = pool_label(state, t0, labels, (int)i);
+    keys[i] = l < 0 ? negkey : (unsigned long long)l;
+    pos[i] = (int)i;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    unsigned long long varies = or_all & nor_all;
+    if (meta->any_neg && meta->any_nonneg) varies |= 0xffull << 56;
+    int buf = 0;
+    for (int b = 0; b < 8; ++b) {
+      const int on = ((varies >> (8 * b)) & 0xff) != 0;
+      meta->active[b] = on;
+      meta->src[b] = buf;
+      buf ^= on;
+    }
+    meta->final_buf = buf;
+  }
+}
+
+__global__ __launch_bounds__(kSortThreads) void pool_hist_kernel(const PoolMeta* __restrict__ meta, int b,
+                                                                 const unsigned long long* __restrict__ k0,
+                                                                 const unsigned long long* __restrict__ k1, int m, int nb,
+                                                                 unsigned* __restrict__ hist) {
+  if (!meta->active[b]) return;
+  const unsigned long long* __restrict__ keys = meta->src[b] ? k1 : k0;
+  __shared__ unsigned h[256];
+  const int tid = threadIdx.x;
+  h[tid] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * kSortTile;
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const int64_t i = base + r * kSortThreads + tid;
+    if (i < m) atomicAdd(&h[(unsigned)(keys[i] >> (8 * b)) & 255u], 1u);
+  }
+  __syncthreads();
+  hist[(int64_t)tid * nb + blockIdx.x] = h[tid];
+}
+
+// exclusive scan of data[0 .. E) in place, by ONE block: a thread sums a contiguous share, the shares are scanned across
+// the block, and the thread rewrites its share.  `active` (or null): a skipped pass has nothing to scan.
+__global__ __launch_bounds__(kScanThreads) void pool_scan_kernel(const int* __restrict__ active, unsigned* __restrict__ data, int E) {
+  if (active && !*active) return;
+  __shared__ unsigned wave_total[kScanThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t per = ((int64_t)E + kScanThreads - 1) / kScanThreads;
+  const int64_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
+  unsigned s = 0;
+  for (int64_t i = lo; i < hi; ++i) s += data[i];
+  unsigned inc = s;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned v = __shfl_up(inc, off);
+    if (lane >= off) inc += v;
+  }
+  if (lane == 63) wave_total[wave] = inc;
+  __syncthreads();
+  unsigned run = inc - s;
+  for (int w = 0; w < wave; ++w) run += wave_total[w];
+  for (int64_t i = lo; i < hi; ++i) {
+    const unsigned v = data[i];
+    data[i] = run;
+    run += v;
+  }
+}
+
+// Key i of the block's tile goes to hist[digit][block] (keys with a smaller digit, and keys with this digit in the blocks
+// in front) + the keys with this digit in front of it in the tile.  Tile order: wave w holds keys [w * 512, (w + 1) * 512)
+// of the tile, round r of the wave keys [r * 64, (r + 1) * 64) of those, lane by lane.
+__global__ __launch_bounds__(kSortThreads) void pool_scatter_kernel(const PoolMeta* __restrict__ meta, int b, unsigned long long* __restrict__ k0,
+                                                                    unsigned long long* __restrict__ k1, int* __restrict__ p0,
+                                                                    int* __restrict__ p1, int m, int nb,
+                                                                    const unsigned* __restrict__ hist) {
+  if (!meta->active[b]) return;
+  const int src = meta->src[b];
+  const unsigned long long* kin = src ? k1 : k0;
+  unsigned long long* kout = src ? k0 : k1;
+  const int* pin = src ? p1 : p0;
+  int* pout = src ? p0 : p1;
+  __shared__ unsigned cnt[kSortWaves][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int w = 0; w < kSortWaves; ++w) cnt[w][tid] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * kSortTile + wave * (kSortItems * 64);
+  unsigned long long key[kSortItems];
+  int p[kSortItems];
+  unsigned off[kSortItems];
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const int64_t i = base + r * 64 + lane;
+    const bool valid = i < m;
+    key[r] = valid ? kin[i] : 0ull;
+    p[r] = valid ? pin[i] : 0;
+    const unsigned dg = (unsigned)(key[r] >> (8 * b)) & 255u;
+    unsigned long long same = __ballot(valid);       // the valid lanes of the wave that hold this lane's digit
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+      const bool one = (dg >> bit) & 1u;
+      const unsigned long long bal = __ballot(one);
+      same &= one ? bal : ~bal;
+    }
+    const unsigned long long below = same & ((1ull << lane) - 1ull);
+    off[r] = valid ? cnt[wave][dg] + (unsigned)__popcll(below) : 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    if (valid && below == 0ull) cnt[wave][dg] += (unsigned)__popcll(same);   // one lane per digit: distinct addresses
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  __syncthreads();
+  {
+    unsigned run = hist[(int64_t)tid * nb + blockIdx.x];
+#pragma unroll
+    for (int w = 0; w < kSortWaves; ++w) {
+      const unsigned c = cnt[w][tid];
+      cnt[w][tid] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const int64_t i = base + r * 64 + lane;
+    if (i < m) {
+      const unsigned dst = cnt[wave][(unsigned)(key[r] >> (8 * b)) & 255u] + off[r];
+      kout[dst] = key[r];
+      pout[dst] = p[r];
+    }
+  }
+}
+
+// sorted key i opens a segment: a label (not the key of the negatives) that differs from the key in front of it
+__device__ __forceinline__ bool pool_is_head(const unsigned long long* __restrict__ keys, int64_t i, int m) {
+  if (i >= m) return false;
+  const unsigned long long k = keys[i];
+  return !(k & kNegBit) && (i == 0 || keys[i - 1] != k);
+}
+
+__global__ __launch_bounds__(kHeadBlock) void pool_heads_kernel(const PoolMeta* __restrict__ meta, const unsigned long long* __restrict__ k0,
+                                                                const unsigned long long* __restrict__ k1, int m,
+                                                                unsigned* __restrict__ block_heads) {
+  const unsigned long long* __restrict__ keys = meta->final_buf ? k1 : k0;
+  __shared__ int wave_total[kHeadBlock / 64];
+  const int tid = threadIdx.x;
+  const unsigned long long mask = __ballot(pool_is_head(keys, (int64_t)blockIdx.x * kHeadBlock + tid, m));
+  if ((tid & 63) == 0) wave_total[tid >> 6] = __popcll(mask);
+  __syncthreads();
+  if (tid == 0) {
+    int all = 0;
+#pragma unroll
+    for (int w = 0; w < kHeadBlock / 64; ++w) all += wave_total[w];
+    block_heads[blockIdx.x] = (unsigned)all;
+  }
+}
+
+// i runs over [0, m]: the sorted keys and one slot behind them.  The labels end at the first key of the negatives, or at
+// m: that slot closes the last segment and knows T.
+__global__ __launch_bounds__(kHeadBlock) void pool_index_kernel(PoolMeta* __restrict__ meta, const unsigned long long* __restrict__ k0,
+                                                                const unsigned long long* __restrict__ k1, const int* __restrict__ p0,
+                                                                const int* __restrict__ p1, int m, int t0,
+                                                                const unsigned* __restrict__ block_heads, int* __restrict__ seg_start,
+                                                                int64_t* __restrict__ index_out, int64_t* __restrict__ t_out) {
+  const int fin = meta->final_buf;
+  const unsigned long long* __restrict__ keys = fin ? k1 : k0;
+  const int* __restrict__ pos = fin ? p1 : p0;
+  __shared__ int wave_total[kHeadBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t i = (int64_t)blockIdx.x * kHeadBlock + tid;
+  const bool head = pool_is_head(keys, i, m);
+  const unsigned long long mask = __ballot(head);
+  if (lane == 0) wave_total[wave] = __popcll(mask);
+  __syncthreads();
+  int before = (int)block_heads[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));   // heads in front of i
+  for (int w = 0; w < wave; ++w) before += wave_total[w];
+  if (i > m) return;
+  const bool neg = i < m && (keys[i] & kNegBit);
+  if (head) seg_start[before] = (int)i;
+  if ((i == m || neg) && (i == 0 || !(keys[i - 1] & kNegBit))) {
+    seg_start[before] = (int)i;
+    meta->T = before;
+    t_out[0] = before;
+  }
+  if (i < m) {
+    const int p = pos[i];
+    if (p >= t0) index_out[p - t0] = neg ? -1 : (int64_t)(before + (head ? 1 : 0) - 1);
+  }
+}
+
+template <bool W>
+__global__ __launch_bounds__(256) void pool_reduce_kernel(const PoolMeta* __restrict__ meta, const unsigned long long* __restrict__ k0,
+                                                          const unsigned long long* __restrict__ k1, const int* __restrict__ p0,
+                                                          const int* __restrict__ p1, const int* __restrict__ seg_start, int t0,
+                                                          const float4* __restrict__ state_sums, const float* __restrict__ state_wsum,
+                                                          const int64_t* __restrict__ state_counts, const float4* __restrict__ rows,
+                                                          const float* __restrict__ weights, int64_t t, int q,
+                                                          int64_t* __restrict__ labels_out, float4* __restrict__ sums_out,
+                                                          float* __restrict__ wsum_out, int64_t* __restrict__ counts_out) {
+#pragma clang fp contract(off)
+  if (meta->T != t) return;                     // the caller's buffers hold t templates: write nothing into a wrong size
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t seg = gid / q;
+  const int c = (int)(gid - seg * q);
+  if (seg >= t) return;
+  const int fin = meta->final_buf;
+  const int* __restrict__ order = fin ? p1 : p0;
+  const int b = seg_start[seg], e = seg_start[seg + 1];
+  const int first = order[b];
+  float4 acc;
+  float ws = 0.f;
+  int64_t cnt;
+  if (first < t0) {                             // a stored template: its sum goes on
+    acc = state_sums[(int64_t)first * q + c];
+    if (W) ws = state_wsum[first];
+    cnt = state_counts[first] + (e - b - 1);
+  } else {                                      // the sum starts AT the first row, not at zero: -0 stays -0
+    const float4 x = rows[(int64_t)(first - t0) * q + c];
+    if (W) {
+      const float w = weights[first - t0];
+      acc = make_float4(w * x.x, w * x.y, w * x.z, w * x.w);
+      ws = w;
+    } else {
+      acc = x;
+    }
+    cnt = e - b;
+  }
+  // The rest of the segment in chunks of kLookAhead rows: the loads of a chunk are issued together, in front of its adds,
+  // and its positions were loaded a chunk earlier, so that a row's load never waits on the load of its position.
+  int next[kLookAhead];
+  int64_t i = b + 1;
+#pragma unroll
+  for (int k = 0; k < kLookAhead; ++k) next[k] = k < e - i ? order[i + k] : -1;
+  for (; i < e; i += kLookAhead) {
+    float4 x[kLookAhead];
+    float w[kLookAhead];
+#pragma unroll
+    for (int k = 0; k < kLookAhead; ++k) {
+      const int p = next[k];
+      next[k] = k + kLookAhead < e - i ? order[i + kLookAhead + k] : -1;
+      x[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+      w[k] = 0.f;
+      if (p >= 0) {
+        x[k] = rows[(int64_t)(p - t0) * q + c];
+        if (W) w[k] = weights[p - t0];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kLookAhead; ++k)
+      if (k < e - i) {                          // in row order, one add after the other
+        if (W) {
+          acc.x = acc.x + w[k] * x[k].x;
+          acc.y = acc.y + w[k] * x[k].y;
+          acc.z = acc.z + w[k] * x[k].z;
+          acc.w = acc.w + w[k] * x[k].w;
+          ws = ws + w[k];
+        } else {
+          acc.x = acc.x + x[k].x;
+          acc.y = acc.y + x[k].y;
+          acc.z = acc.z + x[k].z;
+          acc.w = acc.w + x[k].w;
+        }
+      }
+  }
+  sums_out[seg * q + c] = acc;
+  if (c == 0) {
+    labels_out[seg] = (int64_t)(fin ? k1 : k0)[b];
+    counts_out[seg] = cnt;
+    if (W) wsum_out[seg] = ws;
+  }
+}
+
+__global__ __launch_bounds__(256) void pool_finish_kernel(const float* __restrict__ sums, const float* __restrict__ wsum,
+                                                          const int64_t* __restrict__ counts, int64_t t, int d, int normalize,
+                                                          const SumPlan plan, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ float scratch[4][NP_PLANE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  if (row >= t) return;                         // (np_sum synchronises the wave alone)
+  const float div = wsum ? wsum[row] : (float)counts[row];
+  const float* __restrict__ s = sums + row * d;
+  float* __restrict__ o = out + row * d;
+  float norm = 1.f;
+  if (normalize) {
+    const float ss = np_sum(plan, scratch[wave], lane, [&](int k) {
+      const float mean = s[k] / div;
+      return mean * mean;
+    });
+    norm = __builtin_sqrtf(ss);
+  }
+  for (int k = lane; k < d; k += 64) {
+    const float mean = s[k] / div;
+    o[k] = normalize ? mean / norm : mean;
+  }
+}
+
+}  // namespace dif
+
+using namespace dif;
+
+struct dif_pool {
+  int d = 0;
+  char* ws = nullptr;            // one allocation, carved by pool_carve for the sizes of the last group
+  size_t ws_cap = 0;
+  PoolMeta* meta = nullptr;
+  unsigned long long* keys[2] = {nullptr, nullptr};
+  int* pos[2] = {nullptr, nullptr};
+  unsigned* hist = nullptr;      // [256][blocks of kSortTile]
+  unsigned* block_heads = nullptr;
+  int* seg_start = nullptr;      // [T + 1]
+  bool grouped = false;          // the workspace holds the order of a group ...
+  int64_t t0 = 0, n = 0;         // ... of these sizes
+  int64_t* t_host = nullptr;     // pinned: T of the last group, copied asynchronously behind it; valid once t_event has passed
+  hipEvent_t t_event = nullptr;
+};
+
+static size_t pool_carve(dif_pool* p, int64_t m, int64_t nb, int64_t nhb) {
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p->ws ? p->ws + at : nullptr;
+    at += (bytes + 255) & ~(size_t)255;
+    return q;
+  };
+  p->meta = (PoolMeta*)take(sizeof(PoolMeta));
+  for (int i = 0; i < 2; ++i) p->keys[i] = (unsigned long long*)take((size_t)m * 8);
+  for (int i = 0; i < 2; ++i) p->pos[i] = (int*)take((size_t)m * 4);
+  p->hist = (unsigned*)take((size_t)nb * 256 * 4);
+  p->block_heads = (unsigned*)take((size_t)nhb * 4);
+  p->seg_start = (int*)take((size_t)(m + 1) * 4);
+  return at;
+}
+
+static bool misaligned16(const void* q) { return ((uintptr_t)q & 15) != 0; }
+
+extern "C" {
+
+int dif_pool_create(dif_pool** out, int d) {
+  if (!out) return set_error("dif_pool_create: null out");
+  if (d <= 0 || d % 32 != 0) return set_error("dif_pool_create: embedding size must be a positive multiple of 32 (got %d)", d);
+  dif_pool* p = new (std::nothrow) dif_pool();
+  if (!p) return set_error("dif_pool_create: out of host memory");
+  p->d = d;
+  hipError_t e = hipHostMalloc((void**)&p->t_host, sizeof(int64_t), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->t_event, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    if (p->t_host) (void)hipHostFree(p->t_host);
+    delete p;
+    return set_error("dif_pool_create: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return 0;
+}
+
+int dif_pool_destroy(dif_pool* p) {
+  if (!p) return 0;
+  if (p->ws) (void)hipFree(p->ws);
+  if (p->t_event) (void)hipEventDestroy(p->t_event);
+  if (p->t_host) (void)hipHostFree(p->t_host);
+  delete p;
+  return 0;
+}
+
+int dif_pool_group(dif_pool* p, const int64_t* state_labels_dev, int64_t t0, const int64_t* labels_dev, int64_t n, int64_t* index_out_dev,
+                   int64_t* t_out_dev, void* stream) {
+  if (!p) return set_error("dif_pool_group: null handle");
+  if (t0 < 0 || n < 0 || t0 > 0x7fffffff || n > 0x7fffffff || t0 + n > 0x7fffffffll)
+    return set_error("dif_pool_group: sizes out of range (t0 %lld, n %lld; t0 + n must stay below 2^31)", (long long)t0, (long long)n);
+  if (!t_out_dev || (t0 > 0 && !state_labels_dev) || (n > 0 && (!labels_dev || !index_out_dev)))
+    return set_error("dif_pool_group: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  p->grouped = false;
+  const int64_t m = t0 + n;
+  const int64_t nb = m > 0 ? (m + kSortTile - 1) / kSortTile : 1;
+  const int64_t nhb = (m + 1 + kHeadBlock - 1) / kHeadBlock;
+  if (nb * 256 > 0x7fffffff) return set_error("dif_pool_group: sizes out of range");
+  dif_pool probe;
+  const size_t need = pool_carve(&probe, m, nb, nhb);
+  if (grow(&p->ws, &p->ws_cap, need, 1)) return -1;
+  pool_carve(p, m, nb, nhb);
+  DIF_HIP(hipMemsetAsync(p->meta, 0, sizeof(PoolMeta), st));
+  const unsigned flat = (unsigned)(m > 0 ? (nb < 2048 ? nb : 2048) : 1);
+  hipLaunchKernelGGL(pool_stats_kernel, dim3(flat), dim3(256), 0, st, state_labels_dev, (int)t0, labels_dev, (int)m, p->meta);
+  hipLaunchKernelGGL(pool_init_kernel, dim3(flat), dim3(256), 0, st, state_labels_dev, (int)t0, labels_dev, (int)m, p->meta, p->keys[0],
+                     p->pos[0]);
+  for (int b = 0; b < 8 && m > 1; ++b) {
+    hipLaunchKernelGGL(pool_hist_kernel, dim3((unsigned)nb), dim3(kSortThreads), 0, st, p->meta, b, p->keys[0], p->keys[1], (int)m, (int)nb,
+                       p->hist);
+    hipLaunchKernelGGL(pool_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, &p->meta->active[b], p->hist, (int)(nb * 256));
+    hipLaunchKernelGGL(pool_scatter_kernel, dim3((unsigned)nb), dim3(kSortThreads), 0, st, p->meta, b, p->keys[0], p->keys[1], p->pos[0],
+                       p->pos[1], (int)m, (int)nb, p->hist);
+  }
+  hipLaunchKernelGGL(pool_heads_kernel, dim3((unsigned)nhb), dim3(kHeadBlock), 0, st, p->meta, p->keys[0], p->keys[1], (int)m, p->block_heads);
+  hipLaunchKernelGGL(pool_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const int*)nullptr, p->block_heads, (int)nhb);
+  hipLaunchKernelGGL(pool_index_kernel, dim3((unsigned)nhb), dim3(kHeadBlock), 0, st, p->meta, p->keys[0], p->keys[1], p->pos[0], p->pos[1],
+                     (int)m, (int)t0, p->block_heads, p->seg_start, index_out_dev, t_out_dev);
+  DIF_HIP(hipGetLastError());
+  // T follows the kernels into pinned memory without a wait: dif_pool_reduce compares it once the event has passed
+  DIF_HIP(hipMemcpyAsync(p->t_host, &p->meta->T, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DIF_HIP(hipEventRecord(p->t_event, st));
+  p->grouped = true;
+  p->t0 = t0;
+  p->n = n;
+  return 0;
+}
+
+int dif_pool_reduce(dif_pool* p, const float* state_sums_dev, const float* state_wsum_dev, const int64_t* state_counts_dev,
+                    const float* rows_dev, const float* weights_dev, int64_t t, int64_t* labels_out_dev, float* sums_out_dev,
+                    float* wsum_out_dev, int64_t* counts_out_dev, void* stream) {
+  if (!p) return set_error("dif_pool_reduce: null handle");
+  if (!p->grouped) return set_error("dif_pool_reduce: no dif_pool_group on this handle left an order behind");
+  if (t < p->t0 || t > p->t0 + p->n)
+    return set_error("dif_pool_reduce: t %lld disagrees with the group (%lld stored templates, %lld rows)", (long long)t, (long long)p->t0,
+                     (long long)p->n);
+  const hipError_t seen = hipEventQuery(p->t_event);
+  (void)hipGetLastError();                      // (not ready is no error)
+  if (seen == hipSuccess && *p->t_host != t)
+    return set_error("dif_pool_reduce: t %lld disagrees with the %lld templates the group found", (long long)t, (long long)*p->t_host);
+  const bool weighted = weights_dev != nullptr;
+  if ((p->t0 > 0 && (!state_sums_dev || !state_counts_dev || (weighted && !state_wsum_dev))) || (p->n > 0 && !rows_dev) ||
+      (t > 0 && (!labels_out_dev || !sums_out_dev || !counts_out_dev || (weighted && !wsum_out_dev))))
+    return set_error("dif_pool_reduce: null pointer");
+  if (misaligned16(state_sums_dev) || misaligned16(rows_dev) || misaligned16(sums_out_dev))
+    return set_error("dif_pool_reduce: rows and sums must be aligned to 16 bytes");
+  if (t == 0) return 0;
+  const int q = p->d / 4;
+  const int64_t blocks = (t * q + 255) / 256;
+  if (blocks > 0x7fffffff) return set_error("dif_pool_reduce: sizes out of range");
+  hipStream_t st = (hipStream_t)stream;
+  auto kernel = weighted ? pool_reduce_kernel<true> : pool_reduce_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, p->meta, p->keys[0], p->keys[1], p->pos[0], p->pos[1], p->seg_start,
+                     (int)p->t0, (const float4*)state_sums_dev, state_wsum_dev, state_counts_dev, (const float4*)rows_dev, weights_dev, t, q,
+                     labels_out_dev, (float4*)sums_out_dev, wsum_out_dev, counts_out_dev);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+int dif_pool_finish(const float* sums_dev, const float* wsum_dev, const int64_t* counts_dev, int64_t t, int d, int normalize, float* out_dev,
+                    void* stream) {
+  if (d <= 0 || d % 32 != 0) return set_error("dif_pool_finish: embedding size must be a positive multiple of 32 (got %d)", d);
+  if (t < 0 || t > 0x7fffffff) return set_error("dif_pool_finish: t %lld out of range", (long long)t);
+  if (t == 0) return 0;
+  if (!sums_dev || !out_dev || (!wsum_dev && !counts_dev)) return set_error("dif_pool_finish: null pointer");
+  SumPlan plan;
+  if (make_sum_plan(d, &plan)) return -1;
+  hipLaunchKernelGGL(pool_finish_kernel, dim3((unsigned)((t + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sums_dev, wsum_dev, counts_dev, t, d,
+                     normalize != 0, plan, out_dev);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

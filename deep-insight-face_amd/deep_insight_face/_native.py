@@ -57,6 +57,12 @@ SIGNATURES = {
     'dif_align_crop_list': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, P(c_float), c_void_p, c_int,
                                     c_void_p, c_void_p]),
     'dif_faces_gather': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'dif_pool_create': (c_int, [P(c_void_p), c_int]),
+    'dif_pool_destroy': (c_int, [c_void_p]),
+    'dif_pool_group': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'dif_pool_reduce': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    'dif_pool_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     'dif_gallery_create': (c_int, [P(c_void_p), c_int]),
     'dif_gallery_destroy': (c_int, [c_void_p]),
     'dif_gallery_set': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),

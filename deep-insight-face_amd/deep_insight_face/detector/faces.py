@@ -52,6 +52,21 @@ class FrameFaces(typing.NamedTuple):
         from .. import oneshot
         return oneshot.dbscan(self.emb, tolerance, min_samples, distance_metric)[0]
 
+    def templates(self, labels, weighted: bool = False, normalize: bool = True):
+        """One template per person of the batch: the embeddings pooled by ``labels`` [M] (what ``cluster`` or ``dbscan``
+        returned; a negative label -- noise -- leaves the face out) -> (templates [T, d] float32, template_labels [T] int64
+        ascending, counts [T] int64) on the device.  A template is the mean of its faces in row order, exact
+        (``templates.pool_templates``), divided by its norm with ``normalize``; ``weighted`` weighs every face by its detection
+        score.  ``M == 0`` gives empty tensors."""
+        if self.emb is None:
+            raise ValueError('FrameFaces.templates needs the embeddings (embed_and_match, or a pipeline\'s faces())')
+        if self.emb.shape[0] == 0:
+            dev = self.emb.device
+            return (torch.empty((0, self.emb.shape[1]), dtype=torch.float32, device=dev),
+                    torch.empty((0,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int64, device=dev))
+        from .. import templates
+        return templates.pool_templates(self.emb, labels, self.scores if weighted else None, normalize)[:3]
+
 
 def _tensor(x):
     return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))

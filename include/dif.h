@@ -731,6 +731,54 @@ const char* dif_net_op_describe(const dif_net* net, int i);
 int dif_net_embed_tap(dif_net* net, const void* x_dev, int n, int layout, int dtype, float* out_dev, int i, float* x_tap,
                       float* res_tap, float* y_tap, float* y2_tap, void* stream);
 
+/* ------------------------------------------------------------------ template pooling (csrc/templates.hip)
+ * One mean embedding per identity, exact: the rows that carry one label (the images of a person, the frames of a track;
+ * the labels of dif_gallery_cluster / dif_gallery_dbscan) are pooled into one template row, which is what a 1:N system
+ * enrols (deep_insight_face.templates: TemplatePool, pool_templates; detector.faces.FrameFaces.templates).  The
+ * arithmetic is NumPy's float32, bit for bit (tests/templates_ref.py restates it):
+ *   sums[t] = ((x_r0 + x_r1) + x_r2) + ... over the label's rows in ascending row number, every add rounded to float32
+ *             (np.add.reduce(x[labels == l], axis=0)); with weights (... + fl(w_r * x_r)), the product rounded before
+ *             the add (no FMA), and wsum[t] = ((w_r0 + w_r1) + ...);
+ *   mean    = sums / float32(count), or sums / wsum; weights are used as given, NaN and Inf propagate;
+ *   normalised: mean / sqrt(add.reduce(mean * mean)) in NumPy's pairwise order (np.linalg.norm(mean, axis=1,
+ *             keepdims=True)); a zero-norm template is a NaN row.
+ * A row with a NEGATIVE label is left out (the convention of dif_match_roc and dif_match_topk_ids; dbscan's noise);
+ * the templates are the distinct non-negative labels in ascending order; T may be 0.  Labels are full int64.
+ * The sums are sequential, so pooling is INCREMENTAL: a caller keeps labels [T] ascending, sums [T][d], wsum [T]
+ * (weighted pools) and counts [T] int64, hands them back as the state of the next call, and the result is bit-identical
+ * to one call over all rows ever added, in order.  The handle owns only workspace (the sort's buffers and the order
+ * they leave behind), grown on demand; all state is the caller's.  One add = dif_pool_group, ONE host read of
+ * t_out_dev (8 bytes, the only synchronisation, as dif_faces_compact has one) to size the outputs, dif_pool_reduce;
+ * dif_pool_finish turns sums into templates whenever they are wanted.  No call reads anything back or waits.
+ * dif_pool_group: a stable LSD radix sort (8-bit digits; a digit that is constant over all keys costs nothing) of
+ *   (label, position), the t0 state labels -- ascending, distinct, >= 0; NULL when t0 = 0 -- in front of the n new
+ *   ones, so that a stored template is first in its segment.  Writes index_out_dev int64 [n]: the position of each
+ *   row's template among the templates AFTER this add (-1 for a negative label), and t_out_dev int64 [1]: T, their
+ *   number (t0 <= T <= t0 + n).  t0 + n < 2^31.  The output does not depend on thread or block order.
+ * dif_pool_reduce: uses the order the preceding dif_pool_group on the same handle left behind (its t0 and n), and
+ *   fails if there was none, or if t is outside [t0, t0 + n], or -- once the group has run, which it has for a caller
+ *   that read t_out_dev -- if t is not the T it wrote; kernels enqueued behind a group that is still running check t on
+ *   the device and write nothing into buffers of a wrong size.  state_sums_dev [t0][d], state_wsum_dev [t0],
+ *   state_counts_dev [t0]: the state (NULL when t0 = 0); rows_dev float [n][d]; weights_dev float [n], or NULL for an
+ *   unweighted pool (state_wsum_dev and wsum_out_dev are then not used and may be NULL).  Writes labels_out_dev [t],
+ *   sums_out_dev [t][d], wsum_out_dev [t], counts_out_dev [t], none of which may overlap the state.  A segment's rows
+ *   are never split across accumulators: one thread owns four columns of one template and adds its rows in order, with
+ *   the loads of sixteen rows in flight; parallelism comes from the columns and the templates.  Rows and sums must be
+ *   aligned to 16 bytes.
+ * dif_pool_finish: out_dev float [t][d] = the means (normalize = 0) or the normalised templates; wsum_dev NULL divides
+ *   by float32(counts_dev).  t = 0 is a no-op.
+ * d not a positive multiple of 32, a NULL pointer where one is needed and sizes out of range fail. */
+typedef struct dif_pool dif_pool;
+int dif_pool_create(dif_pool** out, int d);
+int dif_pool_destroy(dif_pool* p);
+int dif_pool_group(dif_pool* p, const int64_t* state_labels_dev, int64_t t0, const int64_t* labels_dev, int64_t n,
+                   int64_t* index_out_dev, int64_t* t_out_dev, void* stream);
+int dif_pool_reduce(dif_pool* p, const float* state_sums_dev, const float* state_wsum_dev, const int64_t* state_counts_dev,
+                    const float* rows_dev, const float* weights_dev, int64_t t, int64_t* labels_out_dev, float* sums_out_dev,
+                    float* wsum_out_dev, int64_t* counts_out_dev, void* stream);
+int dif_pool_finish(const float* sums_dev, const float* wsum_dev, const int64_t* counts_dev, int64_t t, int d, int normalize,
+                    float* out_dev, void* stream);
+
 /* ------------------------------------------------------------------ ArcMargin logits
  * Not in the reference (north_star only; ArcFace, Deng et al. 2019):
  * logits = s * cos(theta + m * onehot(label)); labels_dev NULL -> s * cos(theta). */
