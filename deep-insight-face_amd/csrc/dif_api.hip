@@ -101,7 +101,7 @@ int dif_gallery_destroy(dif_gallery* h) {
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
                   (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min, (void*)g.cluster_parent,
                   (void*)g.cluster_bad, (void*)g.dbscan_degree, (void*)g.dbscan_anchor, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins,
-                  (void*)g.topk_ids_stat})
+                  (void*)g.topk_ids_stat, (void*)g.topk_tagged_stat})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -353,6 +353,15 @@ int dif_gallery_get_stat(dif_gallery* h, const char* key, int64_t* out, void* st
     *out = (int64_t)v;
     return 0;
   }
+  if (k == "topk_tagged_tiles") {              // (probe, tile) pairs the last tagged top-k call evaluated row by row
+    unsigned long long v = 0;
+    if (g.topk_tagged_stat) {
+      DIF_HIP(hipMemcpyAsync(&v, g.topk_tagged_stat, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      DIF_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
+    *out = (int64_t)v;
+    return 0;
+  }
   return set_error("dif_gallery_get_stat: unknown key '%s'", key);
 }
 
@@ -434,6 +443,44 @@ int dif_match_topk_ids(dif_gallery* h, const float* probes_dev, int n, int metri
   if (h->g.n > 0 && !row_labels_dev) return set_error("dif_match_topk_ids: null row labels");
   return topk_ids_run(&h->g, probes_dev, n, metric, k, row_labels_dev, exclude_dev, idx_out_dev, dist_out_dev, label_out_dev,
                       (hipStream_t)stream);
+}
+
+int dif_match_topk_tagged(dif_gallery* h, const float* probes_dev, int n, int metric, int k, const int64_t* row_tags_dev,
+                          const int64_t* probe_masks_dev, int64_t* idx_out_dev, float* dist_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_topk_tagged: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_topk_tagged: negative probe count");
+  if (k < 1 || k > DIF_TOPK_MAX) return set_error("dif_match_topk_tagged: k %d outside [1, %d]", k, DIF_TOPK_MAX);
+  if (n == 0) return 0;
+  if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match_topk_tagged: null pointer");
+  if (h->g.n > 0 && (!row_tags_dev || !probe_masks_dev)) return set_error("dif_match_topk_tagged: null row tags or probe masks");
+  if (h->g.n == 0) {                            // nothing enrolled: all padding, no tag is read, no tile evaluated
+    if (h->g.topk_tagged_stat) DIF_HIP(hipMemsetAsync(h->g.topk_tagged_stat, 0, sizeof(unsigned long long), (hipStream_t)stream));
+    return topk_run(&h->g, probes_dev, n, metric, k, idx_out_dev, dist_out_dev, (hipStream_t)stream);
+  }
+  return topk_run(&h->g, probes_dev, n, metric, k, idx_out_dev, dist_out_dev, (hipStream_t)stream, row_tags_dev,
+                  probe_masks_dev);
+}
+
+int dif_match_topk_ids_tagged(dif_gallery* h, const float* probes_dev, int n, int metric, int k, const int64_t* row_labels_dev,
+                              const int64_t* exclude_dev, const int64_t* row_tags_dev, const int64_t* probe_masks_dev,
+                              int64_t* idx_out_dev, float* dist_out_dev, int64_t* label_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_topk_ids_tagged: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_topk_ids_tagged: negative probe count");
+  if (k < 1 || k > DIF_TOPK_MAX) return set_error("dif_match_topk_ids_tagged: k %d outside [1, %d]", k, DIF_TOPK_MAX);
+  if (n == 0) return 0;
+  if (!probes_dev || !idx_out_dev || !dist_out_dev) return set_error("dif_match_topk_ids_tagged: null pointer");
+  if (h->g.n > 0 && !row_labels_dev) return set_error("dif_match_topk_ids_tagged: null row labels");
+  if (h->g.n > 0 && (!row_tags_dev || !probe_masks_dev))
+    return set_error("dif_match_topk_ids_tagged: null row tags or probe masks");
+  if (h->g.n == 0) {                            // nothing enrolled: all padding, no label or tag is read, no tile evaluated
+    if (h->g.topk_tagged_stat) DIF_HIP(hipMemsetAsync(h->g.topk_tagged_stat, 0, sizeof(unsigned long long), (hipStream_t)stream));
+    return topk_ids_run(&h->g, probes_dev, n, metric, k, row_labels_dev, exclude_dev, idx_out_dev, dist_out_dev, label_out_dev,
+                        (hipStream_t)stream);
+  }
+  return topk_ids_run(&h->g, probes_dev, n, metric, k, row_labels_dev, exclude_dev, idx_out_dev, dist_out_dev, label_out_dev,
+                      (hipStream_t)stream, row_tags_dev, probe_masks_dev);
 }
 
 int dif_gallery_cluster(dif_gallery* h, int metric, float tolerance, int64_t first_row, const int64_t* labels_in_dev,

@@ -73,6 +73,8 @@ struct Gallery {
   int topk_seed = 0;                         // "topk_seed": tiles the seed of dif_match_topk evaluates per probe (0: k of them)
   // dif_match_topk_ids shares topk_min (stream-ordered calls) and adds one counter: the (probe, tile) evaluations of the last call
   unsigned long long* topk_ids_stat = nullptr;
+  // dif_match_topk_tagged / dif_match_topk_ids_tagged share topk_min too and add the counter of "topk_tagged_tiles"
+  unsigned long long* topk_tagged_stat = nullptr;
   // dif_gallery_cluster (csrc/match_within.hip) shares the census and its thresholds (stream-ordered calls) and adds the
   // union-find's parent array, one int per row, and one int that tells cluster_flatten_kernel of a bad labels_in entry
   int* cluster_parent = nullptr;
@@ -112,9 +114,11 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
              float* mate_dist_out, hipStream_t st);   // dm_in null: dif_match_rank; else dif_match_rank_at (rank_out: the shard's count)
 int mate_dist_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, float* mate_dist_out,
                   int64_t* owned_out, hipStream_t st);
-int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st);
+int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st,
+             const int64_t* row_tags = nullptr, const int64_t* probe_masks = nullptr);   // tags given: dif_match_topk_tagged
 int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, const int64_t* row_labels, const int64_t* exclude,
-                 int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st);
+                 int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st, const int64_t* row_tags = nullptr,
+                 const int64_t* probe_masks = nullptr);                                   // tags given: dif_match_topk_ids_tagged
 int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
                 int64_t* n_clusters, hipStream_t st);
 int dbscan_run(Gallery* g, int metric, float tolerance, int min_samples, int64_t* labels_out, int* degree_out, int64_t* counts,

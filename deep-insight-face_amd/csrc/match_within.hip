@@ -2,7 +2,8 @@
 // one given row among all of them (dif_match_rank, and its shard-local halves dif_match_mate_dist / dif_match_rank_at for a
 // mate the shard need not hold; the section starts at rank_prep_kernel), and the k nearest rows in order
 // (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), the k nearest distinct
-// identities over a label per row (dif_match_topk_ids; its section follows topk_run), and the connected components
+// identities over a label per row (dif_match_topk_ids; its section follows topk_run) -- both also over the rows each probe is
+// eligible for (dif_match_topk_tagged, dif_match_topk_ids_tagged: the `Tagged` form of their three kernels) --, and the connected components
 // of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find),
 // and density clustering with noise on the same edges (dif_gallery_dbscan; its section starts at dbscan_init_kernel).
 // hipcc-flags: -ffp-contract=off
@@ -533,11 +534,23 @@ __device__ __forceinline__ float unord_f32(unsigned o) {
   return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-template <class T>
+// Tagged (dif_match_topk_tagged, dif_match_topk_ids_tagged): row r is eligible for probe p iff (row_tags[r] & probe_masks[p])
+// != 0, on the raw 64 bits.  The word becomes the minimum key over the ELIGIBLE rows of the tile (-inf when an eligible row's
+// key is NaN), and a tile with no eligible row for the probe stores a positive quiet NaN: "nothing here".  No eligible row can
+// produce that word -- a NaN key is turned into -inf before it reaches the minimum, and every other key is a number or an
+// infinity -- so the select stages skip a NaN word in every phase, also where t = +inf or the probe is outside the bound's
+// validity and every other tile is evaluated.  (+inf would not do: an enrolled row with an overflowed |g|^2 has the key +inf
+// under metric 0.)  The minimum starts as NaN, fminf drops a NaN operand, so the reductions over lanes and waves keep NaN
+// exactly when every part is NaN.  The tags of the thread's rows and the masks of its probe columns are read once per tile
+// through buffer descriptors bounded like `arsrc`: a row past G reads tag 0, a probe past B mask 0 -- never eligible.
+// Tagged = false is the kernel as it was; the two pointers are unused there.
+template <class T, bool Tagged>
 __global__ __launch_bounds__(T::NT, 2) void topk_tilemin_kernel(const float* __restrict__ gallery, int64_t G,
                                                               const float* __restrict__ probes, int B, int D,
                                                               const float* __restrict__ aux, int metric,
-                                                              float* __restrict__ words, int nparts) {
+                                                              float* __restrict__ words, int nparts,
+                                                              const int64_t* __restrict__ row_tags,
+                                                              const int64_t* __restrict__ probe_masks) {
   constexpr int WM = T::WM, WN = T::WN;
   static_assert(T::BM == WITHIN_BM, "one word per 128 gallery rows");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -574,23 +587,59 @@ __global__ __launch_bounds__(T::NT, 2) void topk_tilemin_kernel(const float* __r
     const int64_t rows_left = G - g0;
     const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(aux + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 4));
     float mn[WN];
+    if constexpr (!Tagged) {
 #pragma unroll
-    for (int n = 0; n < WN; ++n) mn[n] = inf;
+      for (int n = 0; n < WN; ++n) mn[n] = inf;
 #pragma unroll
-    for (int m = 0; m < WM; ++m) {
-      const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
+      for (int m = 0; m < WM; ++m) {
+        const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {                          // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
-        const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
+        for (int q = 0; q < 4; ++q) {                        // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
+          const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bool ok = rbase + 8 * q + j < rows_left;
+          for (int j = 0; j < 4; ++j) {
+            const bool ok = rbase + 8 * q + j < rows_left;
 #pragma unroll
-          for (int n = 0; n < WN; ++n) {
-            const float dot = acc[m][n][4 * q + j];
-            float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
-            key = ok ? key : inf;                             // a row past G
-            mn[n] = (key != key) ? -inf : fminf(mn[n], key);  // (once -inf it stays -inf)
+            for (int n = 0; n < WN; ++n) {
+              const float dot = acc[m][n][4 * q + j];
+              float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
+              key = ok ? key : inf;                           // a row past G
+              mn[n] = (key != key) ? -inf : fminf(mn[n], key);  // (once -inf it stays -inf)
+            }
+          }
+        }
+      }
+    } else {
+      const int64_t cols_left = (int64_t)B - p0;
+      const __amdgpu_buffer_rsrc_t trsrc = make_rsrc(row_tags + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 8));
+      const __amdgpu_buffer_rsrc_t mrsrc = make_rsrc(probe_masks + p0, (uint32_t)((cols_left < T::BN ? cols_left : T::BN) * 8));
+      u32x2 msk[WN];                                          // the masks of this thread's probe columns, once per tile
+#pragma unroll
+      for (int n = 0; n < WN; ++n) {
+        msk[n] = __builtin_amdgcn_raw_buffer_load_b64(mrsrc, (uint32_t)col[n] * 8u, 0, 0);
+        mn[n] = __builtin_nanf("");                           // no eligible row yet
+      }
+#pragma unroll
+      for (int m = 0; m < WM; ++m) {
+        const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                        // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
+          const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
+          u32x4 tg[2];                                        // their four tags, {lo, hi} each
+          tg[0] = __builtin_amdgcn_raw_buffer_load_b128(trsrc, (uint32_t)(rbase + 8 * q) * 8u, 0, 0);
+          tg[1] = __builtin_amdgcn_raw_buffer_load_b128(trsrc, (uint32_t)(rbase + 8 * q) * 8u + 16u, 0, 0);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool ok = rbase + 8 * q + j < rows_left;    // (a row past G reads tag 0 through the descriptor as well)
+            const unsigned tlo = ok ? tg[j >> 1][2 * (j & 1)] : 0u, thi = ok ? tg[j >> 1][2 * (j & 1) + 1] : 0u;
+#pragma unroll
+            for (int n = 0; n < WN; ++n) {
+              const float dot = acc[m][n][4 * q + j];
+              const float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
+              const bool elig = ((tlo & msk[n][0]) | (thi & msk[n][1])) != 0u;   // false for a row past G (tag 0)
+              const float with = (key != key) ? -inf : fminf(mn[n], key);     // fminf(NaN, key) = key
+              mn[n] = elig ? with : mn[n];
+            }
           }
         }
       }
@@ -606,6 +655,7 @@ __global__ __launch_bounds__(T::NT, 2) void topk_tilemin_kernel(const float* __r
       float v = s_min[c];
 #pragma unroll
       for (int w = 1; w < T::WGM; ++w) v = fminf(v, s_min[w * T::BN + c]);
+      if constexpr (Tagged) v = (v != v) ? __builtin_nanf("") : v;   // one bit pattern for "nothing here"
       if (p0 + c < B) words[gt * B + p0 + c] = v;
     }
     // (s_min is written again only after the next tile's main loop, i.e. behind several barriers)
@@ -615,13 +665,29 @@ __global__ __launch_bounds__(T::NT, 2) void topk_tilemin_kernel(const float* __r
 // One block per probe; `words` rows are B floats apart.  All control flow is block-uniform: every thread derives kappa, t and
 // thr_out from the same LDS words, and which tiles are evaluated follows from those alone.
 // (four waves per SIMD asked for: two blocks per CU overlap the latency of the row-by-row stage -- DESIGN 4i has the A/B)
+// Tagged (the words are topk_tilemin_kernel<T, true>'s): a NaN word -- no eligible row in the tile -- is selected in neither
+// phase, whatever kappa, `all` and thr_out are; an ineligible row is skipped before ref_distance (one wave per row: the test
+// is wave-uniform).  The argument above holds with "row" read as "eligible row": a word is the minimum key over the tile's
+// eligible rows (or -inf), every true top-k row is eligible, so its tile's word is a number <= thr_out or -inf and the tile is
+// evaluated; t is the distance of an eligible row.  `tiles_stat` counts the (probe, tile) evaluations ("topk_tagged_tiles").
+// Tagged = false is the kernel as it was, with the arguments it had: `tagargs` is one TopkTags when Tagged, nothing otherwise.
+struct TopkTags {
+  const int64_t* row_tags;                                    // [G]
+  const int64_t* probe_masks;                                 // [B], this launch's probes
+  unsigned long long* tiles_stat;                             // "topk_tagged_tiles"
+};
+__device__ __forceinline__ const TopkTags& topk_tags(const TopkTags& t) { return t; }
+
+template <bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const float* __restrict__ words, int64_t G, int B,
                                                                    const float* __restrict__ probes,
                                                                    const float* __restrict__ gallery, int D, int metric,
                                                                    float cdot, const unsigned* __restrict__ sqmax_bits,
                                                                    int clamp, const SumPlan plan, int k, int seed,
                                                                    int64_t index_base, int64_t* __restrict__ idx_out,
-                                                                   float* __restrict__ dist_out) {
+                                                                   float* __restrict__ dist_out,
+                                                                   const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one TopkTags exactly when Tagged");
   constexpr int NT = 64 * WITHIN_NW;
   static_assert(2 * TOPK_MAX <= NT && TOPK_MAX == WITHIN_BM, "the list holds k kept words and one tile's");
   __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
@@ -683,8 +749,11 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const fl
     kappa = prefix;
   }
 
+  unsigned ntiles = 0;                                        // Tagged: tiles this block evaluated row by row
   if (gtiles > 0) {
     const float s = probe_sq(q, D, lane);                     // the same in every thread
+    unsigned long long pm = 0;                                // Tagged: the probe's mask
+    if constexpr (Tagged) pm = (unsigned long long)topk_tags(tagargs...).probe_masks[p];
     bool all = false;
     float thr_out = 0.f;
 #pragma unroll 1
@@ -699,17 +768,25 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const fl
       for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
         const float w = t0 + tid < gtiles ? words[(t0 + tid) * B + p] : inf;
         s_word[tid] = w;
-        const bool mine = phase == 0 ? ord_f32(w) <= kappa : (ord_f32(w) > kappa && (all || !(w > thr_out)));
+        bool mine = phase == 0 ? ord_f32(w) <= kappa : (ord_f32(w) > kappa && (all || !(w > thr_out)));
+        if constexpr (Tagged) mine = mine && w == w;          // a NaN word: no eligible row
         if (!__syncthreads_or(t0 + tid < gtiles && mine)) continue;   // (also the barrier between two rounds of words)
         const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
         for (int j = 0; j < nw; ++j) {
           const float wj = s_word[j];
           if (!(phase == 0 ? ord_f32(wj) <= kappa : (ord_f32(wj) > kappa && (all || !(wj > thr_out))))) continue;
+          if constexpr (Tagged) {
+            if (wj != wj) continue;
+            ++ntiles;
+          }
           const int64_t g0 = (t0 + j) * WITHIN_BM;
           const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
           const unsigned long long kth = s_list[k - 1];       // a word that is not below it cannot enter the list
           bool any = false;
           for (int r = wave; r < rows; r += WITHIN_NW) {
+            if constexpr (Tagged) {
+              if (((unsigned long long)topk_tags(tagargs...).row_tags[g0 + r] & pm) == 0) continue;   // not eligible: never a candidate
+            }
             float d;
             (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
             if (d == d) {                                     // a NaN distance is never listed
@@ -748,11 +825,15 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const fl
     idx_out[(int64_t)p * k + tid] = w == TOPK_NONE ? -1 : (int64_t)(unsigned)w + index_base;
     dist_out[(int64_t)p * k + tid] = w == TOPK_NONE ? __builtin_nanf("") : unord_f32((unsigned)(w >> 32));
   }
+  if constexpr (Tagged) {
+    if (tid == 0 && ntiles) atomicAdd(topk_tags(tagargs...).tiles_stat, (unsigned long long)ntiles);
+  }
 }
 
-template <class T>
-static int launch_tilemin(const Gallery* g, const float* probes, int B, int metric, hipStream_t st) {
-  auto kern = topk_tilemin_kernel<T>;
+template <class T, bool Tagged = false>
+static int launch_tilemin(const Gallery* g, const float* probes, int B, int metric, hipStream_t st,
+                          const int64_t* row_tags = nullptr, const int64_t* probe_masks = nullptr) {
+  auto kern = topk_tilemin_kernel<T, Tagged>;
   constexpr int lds = T::LDS_BYTES + T::WGM * T::BN * 4;
   static bool done[64];
   int dev = 0;
@@ -765,13 +846,24 @@ static int launch_tilemin(const Gallery* g, const float* probes, int B, int metr
   const int cblocks = (B + T::BN - 1) / T::BN;
   dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
   hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, g->n, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
-                     g->topk_min, nparts);
+                     g->topk_min, nparts, row_tags, probe_masks);
   DIF_HIP(hipGetLastError());
   return 0;
 }
 
-int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st) {
+// the counter of "topk_tagged_tiles", zeroed on the stream by every tagged call
+static int tagged_stat_reset(Gallery* g, hipStream_t st) {
+  if (!g->topk_tagged_stat) DIF_HIP(hipMalloc(&g->topk_tagged_stat, sizeof(unsigned long long)));
+  DIF_HIP(hipMemsetAsync(g->topk_tagged_stat, 0, sizeof(unsigned long long), st));
+  return 0;
+}
+
+// row_tags null: dif_match_topk; else dif_match_topk_tagged (probe_masks [B])
+int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st,
+             const int64_t* row_tags, const int64_t* probe_masks) {
   if (B <= 0) return 0;
+  const bool tagged = row_tags != nullptr;
+  if (tagged && tagged_stat_reset(g, st)) return -1;
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
@@ -791,11 +883,19 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
     const int nb = (int)(B - b0 < per ? B - b0 : per);
     const float* pr = probes + b0 * g->d;
     if (gtiles > 0) {
-      const int rc = with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
+      const int rc = tagged ? with_census_tile(nb, [&](auto tile) {
+        return launch_tilemin<decltype(tile), true>(g, pr, nb, metric, st, row_tags, probe_masks + b0);
+      }) : with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
       if (rc) return rc;
     }
-    hipLaunchKernelGGL(topk_select_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows, g->d,
-                       metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k, dist_out + b0 * k);
+    if (tagged)
+      hipLaunchKernelGGL((topk_select_kernel<true, TopkTags>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows,
+                         g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k,
+                         dist_out + b0 * k, TopkTags{row_tags, probe_masks + b0, g->topk_tagged_stat});
+    else
+      hipLaunchKernelGGL((topk_select_kernel<false>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows,
+                         g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k,
+                         dist_out + b0 * k);
     DIF_HIP(hipGetLastError());
   }
   return 0;
@@ -881,12 +981,16 @@ __device__ __forceinline__ unsigned topk_ids_kappa(const float* __restrict__ wor
 }
 
 // One block per probe, block-uniform control flow, as topk_select_kernel.  `tiles_stat` counts the (probe, tile) evaluations.
+// Tagged as topk_select_kernel<true>: a NaN word is never selected nor counted among the tiles left, an ineligible row is
+// not usable, and the evaluations are also added to `tagged_stat`.  Tagged = false is the kernel as it was.
+template <bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
     const float* __restrict__ words, int64_t G, int B, const float* __restrict__ probes, const float* __restrict__ gallery, int D,
     int metric, float cdot, const unsigned* __restrict__ sqmax_bits, int clamp, const SumPlan plan, int k, int seed,
     int64_t index_base, const int64_t* __restrict__ row_labels, const int64_t* __restrict__ exclude,
     int64_t* __restrict__ idx_out, float* __restrict__ dist_out, int64_t* __restrict__ label_out,
-    unsigned long long* __restrict__ tiles_stat) {
+    unsigned long long* __restrict__ tiles_stat, const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one TopkTags exactly when Tagged");
   constexpr int NT = 64 * WITHIN_NW;
   __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
   __shared__ unsigned long long s_list[2 * TOPK_MAX];         // [0, k): kept, ascending; [TOPK_MAX, ..): the tile being merged
@@ -919,6 +1023,9 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
     auto pass = [&](const bool sweep) {
       auto sel = [&](const float w) {
         const unsigned o = ord_f32(w);
+        if constexpr (Tagged) {
+          if (w != w) return false;                           // a NaN word: no eligible row
+        }
         return sweep ? (o > kappa && (all || !(w > thr_out))) : ((long long)o > lo && o <= kappa);
       };
       for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
@@ -936,6 +1043,10 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
           for (int r = wave; r < rows; r += WITHIN_NW) {
             const long long lab = row_labels[g0 + r];
             if (lab < 0 || lab == ex) continue;               // not usable: never a candidate
+            if constexpr (Tagged) {
+              const TopkTags& tg = topk_tags(tagargs...);   // (the probe's mask: a uniform load)
+              if ((tg.row_tags[g0 + r] & tg.probe_masks[p]) == 0) continue;   // not eligible: not usable
+            }
             float d;
             (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
             if (d == d) {                                     // a NaN distance is never listed
@@ -1014,6 +1125,7 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
         if (t0 + tid < gtiles) {
           const float w = words[(t0 + tid) * B + p];
           mine = ord_f32(w) > kappa && (all || !(w > thr_out));
+          if constexpr (Tagged) mine = mine && w == w;
         }
         left += __syncthreads_count(mine);
       }
@@ -1033,11 +1145,18 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
     if (label_out) label_out[(int64_t)p * k + tid] = w == TOPK_NONE ? -1 : (int64_t)s_lab[tid];
   }
   if (tid == 0 && ntiles) atomicAdd(tiles_stat, (unsigned long long)ntiles);
+  if constexpr (Tagged) {
+    if (tid == 0 && ntiles) atomicAdd(topk_tags(tagargs...).tiles_stat, (unsigned long long)ntiles);
+  }
 }
 
+// row_tags null: dif_match_topk_ids; else dif_match_topk_ids_tagged (probe_masks [B])
 int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, const int64_t* row_labels, const int64_t* exclude,
-                 int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st) {
+                 int64_t* idx_out, float* dist_out, int64_t* label_out, hipStream_t st, const int64_t* row_tags,
+                 const int64_t* probe_masks) {
   if (B <= 0) return 0;
+  const bool tagged = row_tags != nullptr;
+  if (tagged && tagged_stat_reset(g, st)) return -1;
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
@@ -1059,13 +1178,22 @@ int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, cons
     const int nb = (int)(B - b0 < per ? B - b0 : per);
     const float* pr = probes + b0 * g->d;
     if (gtiles > 0) {
-      const int rc = with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
+      const int rc = tagged ? with_census_tile(nb, [&](auto tile) {
+        return launch_tilemin<decltype(tile), true>(g, pr, nb, metric, st, row_tags, probe_masks + b0);
+      }) : with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
       if (rc) return rc;
     }
-    hipLaunchKernelGGL(topk_ids_select_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows, g->d,
-                       metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, row_labels,
-                       exclude ? exclude + b0 : nullptr, idx_out + b0 * k, dist_out + b0 * k,
-                       label_out ? label_out + b0 * k : nullptr, g->topk_ids_stat);
+    if (tagged)
+      hipLaunchKernelGGL((topk_ids_select_kernel<true, TopkTags>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr,
+                         g->rows, g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, row_labels,
+                         exclude ? exclude + b0 : nullptr, idx_out + b0 * k, dist_out + b0 * k,
+                         label_out ? label_out + b0 * k : nullptr, g->topk_ids_stat,
+                         TopkTags{row_tags, probe_masks + b0, g->topk_tagged_stat});
+    else
+      hipLaunchKernelGGL((topk_ids_select_kernel<false>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr,
+                         g->rows, g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, row_labels,
+                         exclude ? exclude + b0 : nullptr, idx_out + b0 * k, dist_out + b0 * k,
+                         label_out ? label_out + b0 * k : nullptr, g->topk_ids_stat);
     DIF_HIP(hipGetLastError());
   }
   return 0;

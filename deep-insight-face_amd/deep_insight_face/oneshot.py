@@ -31,6 +31,41 @@ def up32(thresholds):
     return np.where(low, np.nextafter(t32, np.float32(np.inf)), t32).astype(np.float32)
 
 
+def _bit_sets(x, name, n, dev, scalar=False):
+    """`row_tags` / `probe_masks` of the tagged searches -> int64 [n] on `dev`, one 64-bit set per entry.  NumPy or torch
+    integers of any width (a negative value has bit 63 set; NumPy uint64 is taken bit for bit); floats and bools are rejected,
+    the shape must be [n].  With `scalar` a Python int stands for every entry: -2^63 .. 2^64 - 1, the same 64 bits."""
+    if scalar and isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)):
+        v = int(x)
+        if not -(1 << 63) <= v < (1 << 64):
+            raise ValueError('%s %d does not fit 64 bits' % (name, v))
+        return torch.full((n,), v - (1 << 64) if v >= (1 << 63) else v, dtype=torch.int64, device=dev)
+    if torch.is_tensor(x):
+        t = x
+    else:
+        a = np.asarray(x)
+        if a.size == 0 and a.dtype.kind == 'f':                 # np.asarray([]) is float64: an empty list holds no set
+            a = a.astype(np.int64)
+        if a.dtype.kind not in 'iu':
+            raise ValueError('%s must be integers, got %s' % (name, a.dtype))
+        a = np.ascontiguousarray(a)
+        t = torch.from_numpy(a.view(np.int64).copy() if a.dtype == np.uint64 else a.astype(np.int64))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError('%s must be integers, got %s' % (name, t.dtype))
+    if tuple(t.shape) != (n,):
+        raise ValueError('%s must have shape [%d], got %s' % (name, n, tuple(t.shape)))
+    return t.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def _tag_pair(row_tags, probe_masks, G, B, dev):
+    """Both None -> (None, None); exactly one given -> ValueError; else the two int64 device tensors."""
+    if row_tags is None and probe_masks is None:
+        return None, None
+    if row_tags is None or probe_masks is None:
+        raise ValueError('row_tags and probe_masks go together: give both or neither')
+    return _bit_sets(row_tags, 'row_tags', G, dev), _bit_sets(probe_masks, 'probe_masks', B, dev, scalar=True)
+
+
 class Gallery:
     """Device-resident gallery of enrolled embeddings, [G, d] float32.
 
@@ -155,7 +190,9 @@ class Gallery:
         'row_bytes': device bytes per row;
         'exact_probes': probes the last match sent to the exact whole-gallery search (synchronises);
         'roc_resolved': pairs the last `roc` evaluated one by one, too close to a threshold to call (synchronises);
-        'topk_ids_tiles': (probe, 128-row tile) pairs the last `topk_ids` evaluated row by row (synchronises)."""
+        'topk_ids_tiles': (probe, 128-row tile) pairs the last `topk_ids` evaluated row by row (synchronises);
+        'topk_tagged_tiles': the same for the last `topk` or `topk_ids` given `row_tags` and `probe_masks` -- a tile without
+        a row eligible for the probe is never among them (synchronises)."""
         v = ctypes.c_int64(0)
         N.check(N.lib.dif_gallery_get_stat(self._h, key.encode(), ctypes.byref(v), N.stream_ptr()), ValueError)
         return int(v.value)
@@ -363,9 +400,12 @@ class Gallery:
             N.check(N.lib.dif_match_rank_at(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(mate_dist),
                                             N.ptr(count), N.stream_ptr()))
 
-    def topk_into(self, probes, k, distance_metric, idx, dist):
+    def topk_into(self, probes, k, distance_metric, idx, dist, row_tags=None, probe_masks=None):
         """Allocation-free form of `topk`: `probes` [B, d] float32 CUDA, results written into the caller's CUDA tensors
-        idx [B, k] int64 and dist [B, k] float32."""
+        idx [B, k] int64 and dist [B, k] float32.  `row_tags` [len(self)] and `probe_masks` [B], both int64 CUDA or both
+        None, restrict every probe to its eligible rows (`topk`)."""
+        if (row_tags is None) != (probe_masks is None):
+            raise ValueError('row_tags and probe_masks go together: give both or neither')
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         k = int(k)
@@ -380,11 +420,22 @@ class Gallery:
                 raise ValueError('topk_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
             if name != 'probes' and tuple(t.shape) != (B, k):
                 raise ValueError('topk_into: %s must have shape [%d, %d], got %s' % (name, B, k, tuple(t.shape)))
+        if row_tags is not None:
+            G = len(self)
+            for name, t, shape in (('row_tags', row_tags, (G,)), ('probe_masks', probe_masks, (B,))):
+                if not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != self._dev or not t.is_contiguous():
+                    raise ValueError('topk_into: %s must be a contiguous %s tensor on %s' % (name, torch.int64, self._dev))
+                if tuple(t.shape) != shape:
+                    raise ValueError('topk_into: %s must have shape %s, got %s' % (name, list(shape), tuple(t.shape)))
+            if B:
+                N.check(N.lib.dif_match_topk_tagged(self._h, N.ptr(probes), B, distance_metric, k, N.ptr(row_tags) if G else None,
+                                                    N.ptr(probe_masks), N.ptr(idx), N.ptr(dist), N.stream_ptr()))
+            return
         if B:
             N.check(N.lib.dif_match_topk(self._h, N.ptr(probes), B, distance_metric, k, N.ptr(idx), N.ptr(dist),
                                          N.stream_ptr()))
 
-    def topk(self, probes, k, distance_metric=1):
+    def topk(self, probes, k, distance_metric=1, row_tags=None, probe_masks=None):
         """The k nearest enrolled rows of each probe, in order, exact.  -> (idx[B, k] int64, dist[B, k] float32); NumPy in ->
         NumPy out.  1 <= k <= 128.
 
@@ -393,7 +444,15 @@ class Gallery:
         dist = d[keep].  A NaN distance is never listed (set_option('clamp_nan', 1) orders and reports the clamped 0 / 1
         instead); k above len(self), or fewer than k rows with a distance that is not NaN, pads with idx -1 and dist NaN, and
         an empty gallery gives all padding.  `rank(q, idx[:, j])` returns `(j, dist[:, j])`; where no distance is NaN idx[:, 0]
-        is `match`'s row."""
+        is `match`'s row.
+
+        Watch-lists: `row_tags` [len(self)] holds one 64-bit set per enrolled row in the gallery's row order (any integer
+        dtype, NumPy uint64 taken bit for bit; the gallery stores none -- keep it as `row_labels` is kept, permuted by the moves
+        `remove` reports) and `probe_masks` [B] one per probe (a Python int stands for every probe).  Row r is eligible for
+        probe b iff ``(row_tags[r] & probe_masks[b]) != 0`` on the raw 64 bits, and the list is the one above with
+        ``d[~eligible[b]] = NaN``: an ineligible row is never listed, however near; a tag of 0 is never eligible, a mask of 0
+        gives all padding.  Give both or neither (ValueError otherwise).  `stat('topk_tagged_tiles')` tells how many tiles
+        the call evaluated row by row; a tile without an eligible row is never one."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         k = int(k)
@@ -405,17 +464,21 @@ class Gallery:
         if p.dim() != 2 or p.shape[1] != self.emd_size:
             raise ValueError('probes must be [B, %d], got %s' % (self.emd_size, tuple(p.shape)))
         B = p.shape[0]
+        rt, pm = _tag_pair(row_tags, probe_masks, len(self), B, self._dev)
         idx = torch.empty((B, k), dtype=torch.int64, device=self._dev)
         dist = torch.empty((B, k), dtype=torch.float32, device=self._dev)
-        self.topk_into(p, k, distance_metric, idx, dist)
+        self.topk_into(p, k, distance_metric, idx, dist, rt, pm)
         if was_np:
             idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
         return idx, dist
 
-    def topk_ids_into(self, probes, k, distance_metric, row_labels, exclude, idx, dist, label=None):
+    def topk_ids_into(self, probes, k, distance_metric, row_labels, exclude, idx, dist, label=None, row_tags=None,
+                      probe_masks=None):
         """Allocation-free form of `topk_ids`: `probes` [B, d] float32, `row_labels` [len(self)] int64 and `exclude` [B] int64
         (or None) CUDA, results written into the caller's CUDA tensors idx [B, k] int64, dist [B, k] float32 and (optional)
-        label [B, k] int64."""
+        label [B, k] int64.  `row_tags` [len(self)] and `probe_masks` [B], both int64 CUDA or both None, as in `topk_into`."""
+        if (row_tags is None) != (probe_masks is None):
+            raise ValueError('row_tags and probe_masks go together: give both or neither')
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         k = int(k)
@@ -427,19 +490,25 @@ class Gallery:
         B, G = probes.shape[0], len(self)
         for name, t, dt, shape in (('probes', probes, torch.float32, None), ('row_labels', row_labels, torch.int64, (G,)),
                                    ('exclude', exclude, torch.int64, (B,)), ('idx', idx, torch.int64, (B, k)),
-                                   ('dist', dist, torch.float32, (B, k)), ('label', label, torch.int64, (B, k))):
-            if t is None and name in ('exclude', 'label'):
+                                   ('dist', dist, torch.float32, (B, k)), ('label', label, torch.int64, (B, k)),
+                                   ('row_tags', row_tags, torch.int64, (G,)), ('probe_masks', probe_masks, torch.int64, (B,))):
+            if t is None and name in ('exclude', 'label', 'row_tags', 'probe_masks'):
                 continue
             if not torch.is_tensor(t) or t.dtype != dt or t.device != self._dev or not t.is_contiguous():
                 raise ValueError('topk_ids_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
             if shape is not None and tuple(t.shape) != shape:
                 raise ValueError('topk_ids_into: %s must have shape %s, got %s' % (name, list(shape), tuple(t.shape)))
-        if B:
+        if B and row_tags is not None:
+            N.check(N.lib.dif_match_topk_ids_tagged(
+                self._h, N.ptr(probes), B, distance_metric, k, N.ptr(row_labels) if G else None,
+                N.ptr(exclude) if exclude is not None else None, N.ptr(row_tags) if G else None, N.ptr(probe_masks),
+                N.ptr(idx), N.ptr(dist), N.ptr(label) if label is not None else None, N.stream_ptr()))
+        elif B:
             N.check(N.lib.dif_match_topk_ids(self._h, N.ptr(probes), B, distance_metric, k, N.ptr(row_labels) if G else None,
                                              N.ptr(exclude) if exclude is not None else None, N.ptr(idx), N.ptr(dist),
                                              N.ptr(label) if label is not None else None, N.stream_ptr()))
 
-    def topk_ids(self, probes, k, row_labels, distance_metric=1, exclude=None):
+    def topk_ids(self, probes, k, row_labels, distance_metric=1, exclude=None, row_tags=None, probe_masks=None):
         """The k nearest distinct IDENTITIES of each probe, each with its best row, in order, exact.
         -> (idx[B, k] int64, dist[B, k] float32, label[B, k] int64); NumPy in -> NumPy out.  1 <= k <= 128.
 
@@ -453,7 +522,10 @@ class Gallery:
 
         With ``exclude`` the probe's own identity the list holds the k nearest OTHER identities (k = 1: the hardest negative).
         With all-distinct labels idx and dist are `topk`'s bit for bit; with one label the list has one entry, `match`'s row
-        where no distance is NaN.  `stat('topk_ids_tiles')` tells how many tiles the call evaluated row by row."""
+        where no distance is NaN.  `stat('topk_ids_tiles')` tells how many tiles the call evaluated row by row.
+
+        `row_tags` and `probe_masks` are `topk`'s: a row that is not eligible for the probe is dropped like one with a
+        negative label, so an identity is listed with its best ELIGIBLE row."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         k = int(k)
@@ -478,10 +550,11 @@ class Gallery:
 
         rl = ints(row_labels, 'row_labels', G)
         ex = None if exclude is None else ints(exclude, 'exclude', B)
+        rt, pm = _tag_pair(row_tags, probe_masks, G, B, self._dev)
         idx = torch.empty((B, k), dtype=torch.int64, device=self._dev)
         dist = torch.empty((B, k), dtype=torch.float32, device=self._dev)
         label = torch.empty((B, k), dtype=torch.int64, device=self._dev)
-        self.topk_ids_into(p, k, distance_metric, rl, ex, idx, dist, label)
+        self.topk_ids_into(p, k, distance_metric, rl, ex, idx, dist, label, rt, pm)
         if was_np:
             idx, dist, label = idx.cpu().numpy(), dist.cpu().numpy(), label.cpu().numpy()
         return idx, dist, label
@@ -727,22 +800,23 @@ def rank(probes, gallery, mates, distance_metric=1):
             g.close()
 
 
-def topk(probes, gallery, k, distance_metric=1):
-    """One-call form of Gallery.topk: per probe, the k nearest gallery rows in order -> (idx[B, k], dist[B, k])."""
+def topk(probes, gallery, k, distance_metric=1, row_tags=None, probe_masks=None):
+    """One-call form of Gallery.topk: per probe, the k nearest gallery rows in order -> (idx[B, k], dist[B, k]); with
+    `row_tags` and `probe_masks`, the k nearest rows the probe is eligible for."""
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
-        return g.topk(probes, k, distance_metric)
+        return g.topk(probes, k, distance_metric, row_tags, probe_masks)
     finally:
         if g is not gallery:
             g.close()
 
 
-def topk_ids(probes, gallery, k, row_labels, distance_metric=1, exclude=None):
+def topk_ids(probes, gallery, k, row_labels, distance_metric=1, exclude=None, row_tags=None, probe_masks=None):
     """One-call form of Gallery.topk_ids: per probe, the k nearest distinct identities, each with its best row
-    -> (idx[B, k], dist[B, k], label[B, k])."""
+    -> (idx[B, k], dist[B, k], label[B, k]); `row_tags` and `probe_masks` as in Gallery.topk."""
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
-        return g.topk_ids(probes, k, row_labels, distance_metric, exclude)
+        return g.topk_ids(probes, k, row_labels, distance_metric, exclude, row_tags, probe_masks)
     finally:
         if g is not gallery:
             g.close()

@@ -344,33 +344,51 @@ class ShardedGallery:
     def _back(was_np, *ts):
         return tuple(t.cpu().numpy() for t in ts) if was_np else ts
 
-    def topk(self, local_probes, k, distance_metric=1):
+    def _tags(self, row_tags, probe_masks, b):
+        """The watch-list pair of `topk` / `topk_ids`: -> (this shard's row tags [len(shard)], the masks of ALL ranks' probes
+        [R*b]) as int64 on the shard's device, or (None, None); exactly one given raises ValueError."""
+        if row_tags is None and probe_masks is None:
+            return None, None
+        if row_tags is None or probe_masks is None:
+            raise ValueError('row_tags and probe_masks go together: give both or neither')
+        from .oneshot import _bit_sets
+        dev = self.gallery._dev
+        rt = _bit_sets(row_tags, 'row_tags', len(self.gallery), dev)
+        return rt, self._gather(_bit_sets(probe_masks, 'probe_masks', b, dev, scalar=True)).view(-1)
+
+    def topk(self, local_probes, k, distance_metric=1, row_tags=None, probe_masks=None):
         """oneshot.Gallery.topk over the whole sharded gallery: -> (idx [R*b, k] int64 global, dist [R*b, k] float32) for the
         probes of ALL ranks in rank order, identical on every rank and equal, bit for bit, to one Gallery holding every row.
         Every rank brings its own [b, d] probes (same b).  Exchange: the probes, then one gather of R records of
-        R*b*k*12 bytes; merged on the device (merge_topk)."""
+        R*b*k*12 bytes; merged on the device (merge_topk).
+        `row_tags` [len(shard)] are THIS shard's tags in its local row order, as `row_labels` are; `probe_masks` [b] (or a
+        Python int; None on every rank alike) belong to this rank's probes and are gathered with them (oneshot.Gallery.topk).
+        The merge is unchanged: a row among the k nearest eligible rows of all shards is among those of its own shard."""
         if self._local():
-            return self.gallery.topk(local_probes, k, distance_metric)
+            return self.gallery.topk(local_probes, k, distance_metric, row_tags, probe_masks)
         p, was_np, b = self._begin('topk', local_probes)
+        rt, pm = self._tags(row_tags, probe_masks, b)
         probes = self.all_gather_embeddings(p)
         B = probes.shape[0]
-        idx, d = self.gallery.topk(probes, k, distance_metric)
+        idx, d = self.gallery.topk(probes, k, distance_metric, rt, pm)
         gi, gd = _unpack(self._gather(_pack([idx, d])), [(torch.int64, (B, k)), (torch.float32, (B, k))])
         return self._back(was_np, *merge_topk(gi, gd))
 
-    def topk_ids(self, local_probes, k, row_labels, distance_metric=1, exclude=None):
+    def topk_ids(self, local_probes, k, row_labels, distance_metric=1, exclude=None, row_tags=None, probe_masks=None):
         """oneshot.Gallery.topk_ids over the whole sharded gallery: -> (idx, dist, label), each [R*b, k], identical on every
         rank and equal to one Gallery holding every row.  `row_labels` [len(shard)] are THIS shard's labels in its local row
         order; `exclude` [b] (or None -- on every rank alike) belongs to this rank's probes and is gathered with them.
-        Exchange: the probes, exclude, then one gather of R records of R*b*k*20 bytes (merge_topk_ids)."""
+        Exchange: the probes, exclude, then one gather of R records of R*b*k*20 bytes (merge_topk_ids).
+        `row_tags` (this shard's) and `probe_masks` (this rank's probes', gathered with them) as in `topk`."""
         if self._local():
-            return self.gallery.topk_ids(local_probes, k, row_labels, distance_metric, exclude)
+            return self.gallery.topk_ids(local_probes, k, row_labels, distance_metric, exclude, row_tags, probe_masks)
         p, was_np, b = self._begin('topk_ids', local_probes)
         ex = None if exclude is None else self._gather(self._ints(exclude, 'exclude', b)).view(-1)
+        rt, pm = self._tags(row_tags, probe_masks, b)
         probes = self.all_gather_embeddings(p)
         B = probes.shape[0]
         idx, d, lab = self.gallery.topk_ids(probes, k, self._ints(row_labels, 'row_labels', len(self.gallery)),
-                                            distance_metric, ex)
+                                            distance_metric, ex, rt, pm)
         gi, gl, gd = _unpack(self._gather(_pack([idx, lab, d])),
                              [(torch.int64, (B, k)), (torch.int64, (B, k)), (torch.float32, (B, k))])
         return self._back(was_np, *merge_topk_ids(gi, gd, gl))

@@ -307,7 +307,9 @@ int dif_gallery_set_option(dif_gallery* g, const char* key, int value);
  * last dif_match on `stream` sent to the exact whole-gallery search (synchronises the stream); "roc_resolved": how many pairs the
  * last dif_match_roc on `stream` evaluated one by one, being too close to a threshold to call (synchronises the stream);
  * "topk_ids_tiles": how many (probe, 128-row tile) pairs the last dif_match_topk_ids on `stream` evaluated row by row, over
- * all its probes (synchronises the stream). */
+ * all its probes (synchronises the stream); "topk_tagged_tiles": the same count for the last dif_match_topk_tagged or
+ * dif_match_topk_ids_tagged on `stream` -- a tile without a row eligible for the probe is never among them, so with few rows
+ * eligible it is about the number of tiles that hold one (synchronises the stream; 0 before the first tagged call). */
 int dif_gallery_get_stat(dif_gallery* g, const char* key, int64_t* out, void* stream);
 /* top-1 search of n probes [n][d]: idx_out_dev[n] = np.argmin over the reference's float32 distances
  * (int64 global index; first minimum; a row whose reference distance is NaN ranks first, as in
@@ -423,6 +425,34 @@ int dif_match_topk_ids(dif_gallery* g, const float* probes_dev, int n, int metri
                        const int64_t* row_labels_dev /* [size] */, const int64_t* exclude_dev /* [n], or NULL */,
                        int64_t* idx_out_dev /* [n][k] */, float* dist_out_dev /* [n][k] */,
                        int64_t* label_out_dev /* [n][k], or NULL */, void* stream);
+/* watch-lists: dif_match_topk and dif_match_topk_ids over the rows each probe is allowed to see.  The gallery stores no tags:
+ * row_tags_dev [size] int64 holds one 64-bit set per enrolled row in local row order (as row_labels_dev is kept by the caller:
+ * permute it by dif_gallery_remove's moves), probe_masks_dev [n] int64 one set per probe.
+ *     eligible[p][r] = (row_tags[r] & probe_masks[p]) != 0         on the raw 64 bits: a negative value has bit 63 set
+ *   A tag of 0 is never eligible; a mask of 0 gives all padding.  Per probe q
+ *     d = utility.distance(q[None, :], gallery, metric);  d[~eligible[p]] = NaN
+ *   and the result is dif_match_topk's for that d (dif_match_topk_tagged), or dif_match_topk_ids' with
+ *   ok &= eligible[p] (dif_match_topk_ids_tagged): the same order (ties to the lower row), NaN rule, "clamp_nan", padding
+ *   (-1 / NaN / label -1), index_base, k in [1, DIF_TOPK_MAX], units and arithmetic -- metric 0 bit-identical to the reference,
+ *   metric 1 up to the arccos.  An ineligible row is never listed, however many of them are nearer than the first eligible one.
+ *   n = 0 is a no-op; an empty gallery gives all padding (not an error) and reads neither array; with rows enrolled a NULL
+ *   row_tags_dev or probe_masks_dev fails, as do dif_match_topk's / dif_match_topk_ids' own argument errors.
+ * Relations: with every (row, probe) pair eligible -- all tags and masks -1, say -- the results are the untagged calls', bit for
+ *   bit; the tagged list of a probe equals the untagged list over a gallery of its eligible rows alone, indices mapped back.
+ * Costs the untagged call's MFMA pass with 8 more bytes read per row: the tile word is the minimum key over the tile's
+ *   ELIGIBLE rows, and a tile with no eligible row for the probe is marked and never evaluated row by row, whatever the
+ *   tolerance -- so a selective mask makes the call cheaper, not dearer.  Within an evaluated tile an ineligible row is skipped
+ *   before any arithmetic.  dif_gallery_get_stat "topk_tagged_tiles" counts the tiles evaluated.  No host synchronisation in
+ *   steady state; shares dif_match_topk's workspace (calls on one stream are ordered) plus one 8-byte counter.  The untagged
+ *   entries run the kernels they ran before. */
+int dif_match_topk_tagged(dif_gallery* g, const float* probes_dev, int n, int metric, int k,
+                          const int64_t* row_tags_dev /* [size] */, const int64_t* probe_masks_dev /* [n] */,
+                          int64_t* idx_out_dev /* [n][k] */, float* dist_out_dev /* [n][k] */, void* stream);
+int dif_match_topk_ids_tagged(dif_gallery* g, const float* probes_dev, int n, int metric, int k,
+                              const int64_t* row_labels_dev /* [size] */, const int64_t* exclude_dev /* [n], or NULL */,
+                              const int64_t* row_tags_dev /* [size] */, const int64_t* probe_masks_dev /* [n] */,
+                              int64_t* idx_out_dev /* [n][k] */, float* dist_out_dev /* [n][k] */,
+                              int64_t* label_out_dev /* [n][k], or NULL */, void* stream);
 /* which enrolled rows are the same person: exact single-linkage clustering of the gallery's own rows at a tolerance, i.e. the
  * connected components of the graph whose edges are the pairs of rows within `tolerance`.  With n = dif_gallery_size:
  *     for i in range(n):                                            every enrolled row is a probe
