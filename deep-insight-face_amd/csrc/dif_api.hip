@@ -221,7 +221,7 @@ int dif_gallery_remove(dif_gallery* h, const int64_t* rows_dev, int64_t k, int64
 int64_t dif_gallery_size(const dif_gallery* h) { return h ? h->g.n : 0; }
 int64_t dif_gallery_capacity(const dif_gallery* h) { return h ? h->g.cap : 0; }
 
-static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", "cluster_round", "roc_round", "roc_blocks", nullptr};
+static const char* const kGalleryOptions[] = {"filter", "frag", "clamp_nan", "bd", "bd_fill", "topk_seed", "cluster_round", "roc_round", "roc_blocks", "within_round", "topk_round", nullptr};
 
 const char* dif_gallery_option_name(int i) {
   int n = 0;
@@ -256,6 +256,18 @@ int dif_gallery_set_option(dif_gallery* h, const char* key, int value) {
     // probes per round of dif_match_roc (0: what the mask workspace's cap allows).  Same answers: tests force several rounds
     if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'roc_round' takes 0 or a multiple of 128");
     h->g.roc_round = value;
+    return 0;
+  }
+  if (std::string(key) == "within_round") {
+    // probes per round of dif_match_within, dif_match_rank and dif_match_rank_at (0: what the census' cap allows).  Same answers: tests force several rounds
+    if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'within_round' takes 0 or a multiple of 128");
+    h->g.within_round = value;
+    return 0;
+  }
+  if (std::string(key) == "topk_round") {
+    // probes per round of dif_match_topk, dif_match_topk_ids and their tagged forms (0: what the tile words' cap allows).  Same answers: tests force several rounds
+    if (value < 0 || value % 128 != 0) return set_error("dif_gallery_set_option: 'topk_round' takes 0 or a multiple of 128");
+    h->g.topk_round = value;
     return 0;
   }
   if (std::string(key) == "roc_blocks") {

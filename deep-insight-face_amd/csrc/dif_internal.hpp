@@ -64,6 +64,7 @@ struct Gallery {
   size_t within_census_cap = 0;              // ... in 16-bit words
   float* within_thr = nullptr;               // per probe: {key <= [0]: sure, key > [1]: out, |key| >= [2]: borderline, [3] != 0: resolve all}
   size_t within_thr_cap = 0;                 // ... in probes
+  int within_round = 0;                      // "within_round": probes per round of dif_match_within / _rank / _rank_at (0: what the census' cap allows)
   // dif_match_rank shares the two above (stream-ordered calls) and adds, per probe, the mate's distance and local row
   struct RankMate* rank_mate = nullptr;
   size_t rank_mate_cap = 0;                  // ... in probes
@@ -71,6 +72,7 @@ struct Gallery {
   float* topk_min = nullptr;
   size_t topk_min_cap = 0;                   // ... in floats
   int topk_seed = 0;                         // "topk_seed": tiles the seed of dif_match_topk evaluates per probe (0: k of them)
+  int topk_round = 0;                        // "topk_round": probes per round of the four top-k entries (0: what the tile words' cap allows)
   // dif_match_topk_ids shares topk_min (stream-ordered calls) and adds one counter: the (probe, tile) evaluations of the last call
   unsigned long long* topk_ids_stat = nullptr;
   // dif_match_topk_tagged / dif_match_topk_ids_tagged share topk_min too and add the counter of "topk_tagged_tiles"

@@ -406,6 +406,7 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
   // probes per round: whole 128-probe blocks whose census stays below WITHIN_CENSUS_MAX words
   int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
+  if (g->within_round > 0 && g->within_round < per) per = g->within_round;
   if (per < 128) per = 128;
   if (per > B) per = B;
   const size_t need_c = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
@@ -458,6 +459,7 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
   // probes per round as in within_run (an empty gallery has no census: one round, every probe unmated)
   int64_t per = gtiles > 0 ? (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128 : B;
+  if (g->within_round > 0 && g->within_round < per) per = g->within_round;
   if (per < 128) per = 128;
   if (per > B) per = B;
   const size_t need_c = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
@@ -871,6 +873,7 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
   // probes per round: whole 128-probe blocks whose tile words stay below TOPK_MIN_MAX (an empty gallery has none: one round)
   int64_t per = gtiles > 0 ? (int64_t)(TOPK_MIN_MAX / (size_t)gtiles) / 128 * 128 : B;
+  if (g->topk_round > 0 && g->topk_round < per) per = g->topk_round;
   if (per < 128) per = 128;
   if (per > B) per = B;
   const size_t need = (size_t)gtiles * (size_t)per;
@@ -1164,6 +1167,7 @@ int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, cons
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
   // the rounds and the words are topk_run's
   int64_t per = gtiles > 0 ? (int64_t)(TOPK_MIN_MAX / (size_t)gtiles) / 128 * 128 : B;
+  if (g->topk_round > 0 && g->topk_round < per) per = g->topk_round;
   if (per < 128) per = 128;
   if (per > B) per = B;
   const size_t need = (size_t)gtiles * (size_t)per;

@@ -179,6 +179,10 @@ class Gallery:
         results for every value (include/dif.h).
         'roc_round': probes per round of `roc`, a multiple of 128 -- 0 (default): what its workspace allows; same results for
         every value (include/dif.h).
+        'within_round': probes per round of `within`, `rank` and `rank_at`, a multiple of 128 -- 0 (default): what the census
+        workspace allows; same results for every value (include/dif.h).
+        'topk_round': probes per round of `topk` and `topk_ids`, plain and tagged, a multiple of 128 -- 0 (default): what the
+        tile-word workspace allows; same results for every value (include/dif.h).
         'roc_blocks': most blocks of `roc`'s resolve stage -- 0 (default): 2048; same results for every value (include/dif.h)."""
         N.check(N.lib.dif_gallery_set_option(self._h, key.encode(), int(value)), ValueError)
 

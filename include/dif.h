@@ -296,6 +296,12 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * "roc_round": 0 (default) dif_match_roc takes as many probes per round as its mask workspace allows (2^24 masks of 16 bytes /
  * the number of 128-row tiles, in whole blocks of 128, at least 128); n > 0, a multiple of 128, makes it n probes when that is
  * fewer.  Same answers for every value (tests: several rounds at a small shape).
+ * "within_round": 0 (default) dif_match_within, dif_match_rank and dif_match_rank_at take as many probes per round as the census
+ * workspace allows (2^27 words / the number of 128-row tiles, in whole blocks of 128, at least 128); n > 0, a multiple of 128,
+ * makes it n probes when that is fewer.  Same answers for every value (tests: several rounds at a small shape).
+ * "topk_round": 0 (default) dif_match_topk, dif_match_topk_ids and their tagged forms take as many probes per round as the
+ * tile-word workspace allows (2^26 floats / the number of 128-row tiles, in whole blocks of 128, at least 128); n > 0, a multiple
+ * of 128, makes it n probes when that is fewer.  Same answers for every value (tests: several rounds at a small shape).
  * "roc_blocks": 0 (default) the resolve stage of dif_match_roc launches at most 2048 blocks, each taking 512 masks per trip;
  * n in 1 .. 65536 makes it at most n.  Same answers for every value (tests: one block that takes many trips at a small shape).
  * Every key the library accepts is listed here (dif_gallery_option_name; tests/test_cabi_symbols.py). */

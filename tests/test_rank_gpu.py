@@ -419,3 +419,62 @@ def test_evaluate_identification(cuda, kind):
     out = ident.evaluate_identification(gal, conv(probes), conv(mates), 1)
     assert sorted(out) == ['cmc', 'mate_dist', 'rank'] and back(out['cmc']).shape == (10,)
     gal.close()
+
+
+# ------------------------------------------------------------------------------------------- 9
+# Rounds of probes (test_within_gpu.py's section 8): rank_run has within_run's loop and adds `mates + b0` at three launch
+# sites, `mate_dist_out + b0` and `rank_out + b0`.  Gallery option "within_round" makes it take several rounds here.
+ROUND_SHAPES = [(129, 257, 512), (300, 1000, 128), (384, 1000, 128)]
+
+
+def _round_options(B):
+    return (0, 128, 256, 0) if B == 300 else (0, 128, 0)
+
+
+def _without_offset(arg, per):
+    """What a launch that dropped its `+ b0` would read in rounds of `per`: probe b0 + j gets entry j."""
+    return arg[np.arange(arg.shape[0]) % per]
+
+
+def _round_mates(B, G, D):
+    """A row of the probe's own identity; every 7th probe unmated (-1), every 11th with a mate beyond the gallery."""
+    mates = _identity_mates(B, G, D).copy()
+    mates[::7] = -1
+    mates[::11] = G + 5
+    return mates
+
+
+@pytest.mark.parametrize('metric', [0, 1])
+@pytest.mark.parametrize('B,G,D', ROUND_SHAPES)
+def test_rank_rounds(cuda, B, G, D, metric):
+    """"within_round" 0, 128 (and 256 at B = 300), 0 on one handle: every answer passes the oracle check, and the forced-round
+    answers and the one after the option is taken back equal the first one-round answer bit for bit.  Before the device is
+    asked: the oracle on the mates a dropped `+ b0` would read differs from the true one in every round after the first."""
+    from deep_insight_face import oneshot
+    probes, gal_np, _ = _inputs(B, G, D)
+    full = _oracle(B, G, D, metric)
+    assert not np.isnan(full).any()
+    mates = _round_mates(B, G, D)
+    want_r, want_d = rank_ref.rank_full(full, mates)
+    assert (want_r[mates == -1] == -1).all() and (want_r[mates == G + 5] == -1).all() and (want_r >= 0).sum() > B // 2
+    for per in _round_options(B)[1:-1]:
+        r, d = rank_ref.rank_full(full, _without_offset(mates, per))
+        differs = (r != want_r) | (np.isnan(d) != np.isnan(want_d)) | (~np.isnan(d) & ~np.isnan(want_d) & (d != want_d))
+        for b0 in range(per, B, per):
+            assert differs[b0:b0 + per].any(), (per, b0)
+    if metric == 1:
+        assert (_near(full, mates) == 0).mean() >= 0.5                          # the cap, on the oracle
+    gal = oneshot.Gallery(gal_np)
+    first = None
+    for per in _round_options(B):
+        gal.set_option('within_round', per)
+        got = gal.rank(probes, mates, metric)
+        _check(got, full, mates, metric)
+        first = first or got
+        assert np.array_equal(got[0], first[0]), (per, np.flatnonzero(got[0] != first[0])[:8])
+        assert np.array_equal(np.isnan(got[1]), np.isnan(first[1]))
+        ok = ~np.isnan(first[1])
+        assert np.array_equal(got[1][ok].view(np.uint32), first[1][ok].view(np.uint32)), per
+    with pytest.raises(ValueError, match='within_round'):
+        gal.set_option('within_round', 100)                                     # not a multiple of 128
+    gal.close()

@@ -395,6 +395,72 @@ def test_rank_at_direct(cuda, G, R, B):
     h.close()
 
 
+# ------------------------------------------------------------------------------------------- rounds of probes in every shard
+def test_forced_rounds_in_every_shard(cuda):
+    """Every shard is queried with the gathered probes of all ranks, so the shards are where the round loops of within_run,
+    rank_run, topk_run and topk_ids_run are met first.  300 probes over three shards of 1001 rows with "within_round" and
+    "topk_round" at 128 on every shard (128 + 128 + 44 probes): the merged rank -- dif_match_rank_at in rounds, its mates
+    global, owned by other shards or by none, its `dm` handed in per probe --, top-k, identities and range search equal the
+    whole handle's one-round answers and the shards' own one-round answers bit for bit, and NumPy on metric 0.  Before the
+    device is asked: the oracle on the mates a dropped `+ b0` would read differs in both later rounds."""
+    B, G, R, D = 300, 1001, 3, 128
+    c = si.case(B, G, D)
+    h = Handles(c.gal, R)
+    assert all(lo > 0 for lo, _ in h.bounds[1:])                                 # index_base != 0
+    p = _t(c.probes)
+    mates = si.mates(h.bounds, G, B)
+    owner = np.array([next((r for r, (lo, hi) in enumerate(h.bounds) if lo <= m < hi), -1) for m in mates])
+    assert all((owner == r).sum() >= 32 for r in range(R)) and (owner == -1).sum() >= 3
+    m = _t(mates)
+    labels, exclude = c.labels, c.labels[c.pick]
+    ex = _t(exclude)
+    want_r, want_d = rank_ref.rank_full(_full(B, G, D, 0), mates)
+    wrong_r, wrong_d = rank_ref.rank_full(_full(B, G, D, 0), mates[np.arange(B) % 128])
+    for b0 in (128, 256):
+        assert ((wrong_r != want_r) | (wrong_d.view(np.uint32) != want_d.view(np.uint32)))[b0:b0 + 128].any()
+
+    def queries(metric):
+        full = _full(B, G, D, metric)
+        tols = _tolerances(full)
+        out = {'rank': h.rank(p, m, metric)}
+        for k in (5, 128):
+            out['topk %d' % k] = h.topk(p, k, metric)
+            out['ids %d' % k] = h.topk_ids(p, k, labels, metric, ex)
+        for K in (4, 0):
+            out['within %d' % K] = h.within(p, tols[2], metric, K)
+        return out, tols
+
+    for metric in (0, 1):
+        base, tols = queries(metric)
+        for g in h.shards:
+            g.set_option('within_round', 128)
+            g.set_option('topk_round', 128)
+        forced, _ = queries(metric)
+        for g in h.shards:
+            g.set_option('within_round', 0)
+            g.set_option('topk_round', 0)
+        again, _ = queries(metric)
+        whole = {'rank': h.whole.rank(p, m, metric)}
+        for k in (5, 128):
+            whole['topk %d' % k] = h.whole.topk(p, k, metric)
+            whole['ids %d' % k] = h.whole.topk_ids(p, k, _t(labels), metric, ex)
+        for K in (4, 0):
+            whole['within %d' % K] = h.whole.within(p, tols[2], metric, K)
+        for name in whole:
+            _raw(forced[name], whole[name])
+            _raw(forced[name], base[name])
+            _raw(again[name], base[name])
+        if metric == 0:
+            full = _full(B, G, D, 0)
+            _ref(forced['rank'], (want_r, want_d))
+            for k in (5, 128):
+                _ref(forced['topk %d' % k], topk_ref.topk_full(full, k))
+                _ref(forced['ids %d' % k], topk_ids_ref.topk_ids_full(full, labels, k, exclude))
+            for K in (4, 0):
+                _ref(forced['within %d' % K], sm.within_full(full, tols[2], K))
+    h.close()
+
+
 # ------------------------------------------------------------------------------------------- argument errors
 def test_argument_errors(cuda):
     """Every one returns an error (ValueError from the wrappers, a non-zero code from the library) and launches nothing."""

@@ -400,3 +400,56 @@ def test_topk_arguments(cuda):
             i0, d0 = empty.topk(probes, k, metric)
             assert i0.shape == (B, k) and i0.dtype == np.int64 and (i0 == -1).all() and np.isnan(d0).all()
     empty.close()
+
+
+# ------------------------------------------------------------------------------------------- 9
+# Rounds of probes.  topk_run (and topk_ids_run) split a call into rounds of `per` probes when the tile words would pass their
+# cap -- at a million rows from 8 577 probes up.  Gallery option "topk_round" lowers `per`, so the loop and its per-round
+# offsets run here: 128 + 1 probes (the last round on the 32-probe tile), 128 + 128 + 44 (the 64-probe tile; 256 + 44 with the
+# option at 256) and three full rounds.  With the option at 0 the same arrays are one launch of three probe blocks.
+ROUND_SHAPES = [(129, 257, 512), (300, 1000, 128), (384, 1000, 128)]
+
+
+def _round_options(B):
+    """One round, forced rounds, one round again."""
+    return (0, 128, 256, 0) if B == 300 else (0, 128, 0)
+
+
+def _without_offset(arg, per):
+    """What a launch that dropped its `+ b0` would read in rounds of `per`: probe b0 + j gets entry j."""
+    return arg[np.arange(arg.shape[0]) % per]
+
+
+def _later_rounds(B, per):
+    return [slice(b0, min(b0 + per, B)) for b0 in range(per, B, per)]
+
+
+@pytest.mark.parametrize('metric', [0, 1])
+@pytest.mark.parametrize('k', [5, 128])
+@pytest.mark.parametrize('B,G,D', ROUND_SHAPES)
+def test_topk_rounds(cuda, B, G, D, k, metric):
+    """"topk_round" 0, 128 (and 256 at B = 300), 0 on one handle, under the default seed and under "topk_seed" 1 (the seed and
+    the sweep then both work in every round): every answer passes the oracle check, and the forced-round answers and the one
+    after the option is taken back equal the first one-round answer bit for bit."""
+    from deep_insight_face import oneshot
+    probes, gal_np, _ = _inputs(B, G, D)
+    full = _oracle(B, G, D, metric)
+    assert not np.isnan(full).any()
+    _cap(full, k, metric)
+    gal = oneshot.Gallery(gal_np)
+    p = torch.from_numpy(probes).cuda()
+    first = None
+    for seed in (0, 1):
+        gal.set_option('topk_seed', seed)
+        for per in _round_options(B):
+            gal.set_option('topk_round', per)
+            got = _np(gal.topk(p, k, metric))
+            _check(got, full, k, metric)
+            first = first or got
+            assert np.array_equal(got[0], first[0]), (seed, per, np.argwhere(got[0] != first[0])[:8])
+            assert _bits_equal(got[1], first[1]), (seed, per)
+    with pytest.raises(ValueError, match='topk_round'):
+        gal.set_option('topk_round', 100)                                       # not a multiple of 128
+    with pytest.raises(ValueError, match='topk_round'):
+        gal.set_option('topk_round', -128)
+    gal.close()

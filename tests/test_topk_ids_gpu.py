@@ -24,7 +24,8 @@ import rank_ref
 import remove_ref
 import topk_ids_ref as ir
 from oracle import distance as od
-from test_topk_gpu import ATOL, MIN_CLEAR, NEAR, SHAPES, _bits_equal, _cos_ok, _inputs, _np, _oracle
+from test_topk_gpu import ATOL, MIN_CLEAR, NEAR, ROUND_SHAPES, SHAPES, _bits_equal, _cos_ok, _inputs, _later_rounds, _np, \
+    _oracle, _round_options, _without_offset
 
 pytestmark = pytest.mark.gpu
 
@@ -524,4 +525,50 @@ def test_evaluate_identification_ids(cuda, metric):
     assert _same(_np((t['idx'], t['dist'], t['label'])), want)
     rows = ident.evaluate_identification_ids(gal_np, probes, probe_labels, labels, metric, max_rank=10)   # rows to enrol
     assert np.array_equal(rows['rank'], out['rank'])
+    gal.close()
+
+
+# ------------------------------------------------------------------------------------------- 12
+@pytest.mark.parametrize('metric', [0, 1])
+@pytest.mark.parametrize('k', [5, 128])
+@pytest.mark.parametrize('B,G,D', ROUND_SHAPES)
+def test_topk_ids_rounds(cuda, B, G, D, k, metric):
+    """Rounds of probes (test_topk_gpu.py's section 9): "topk_round" 0, 128 (and 256 at B = 300), 0 on one handle, four rows per
+    identity, with every probe's own identity excluded -- another label from probe to probe -- and with no exclusion: every
+    answer (idx, dist and label) passes the oracle check, and the forced-round answers and the one after the option is taken
+    back equal the first one-round answer bit for bit.  "topk_ids_tiles" counts (probe, tile) evaluations, which do not depend
+    on the split: the forced-round call reports the one-round call's number (a counter zeroed in every round reports the last
+    round's alone).  Before the device is asked: the oracle under the excluded labels a dropped `+ b0` would read differs from
+    the true one in every round after the first."""
+    from deep_insight_face import oneshot
+    probes, gal_np, pick = _inputs(B, G, D)
+    full = _oracle(B, G, D, metric)
+    assert not np.isnan(full).any()
+    labels = (np.arange(G) % (G // 4)).astype(np.int64)
+    ex = pick.astype(np.int64)
+    want = ir.topk_ids_full(full, labels, k, ex)
+    for per in _round_options(B)[1:-1]:
+        wrong = ir.topk_ids_full(full, labels, k, _without_offset(ex, per))
+        for sl in _later_rounds(B, per):
+            assert (wrong[2][sl] != want[2][sl]).any(), (per, sl)
+    _cap(full, labels, k, metric)
+    _cap(full, labels, k, metric, ex)
+    gal = oneshot.Gallery(gal_np)
+    p, lab, e = torch.from_numpy(probes).cuda(), torch.from_numpy(labels).cuda(), torch.from_numpy(ex).cuda()
+    tiles = {}
+    for name, excl, excl_dev in (('excluded', ex, e), ('all', None, None)):
+        first = None
+        for per in _round_options(B):
+            gal.set_option('topk_round', per)
+            got = _np(gal.topk_ids(p, k, lab, metric, exclude=excl_dev))
+            tiles.setdefault(name, []).append(gal.stat('topk_ids_tiles'))
+            _check(got, full, labels, k, metric, excl)
+            first = first or got
+            assert _same(got, first), (name, per)
+    print('topk_ids_tiles', (B, G, D), k, metric, tiles)
+    gtiles = (G + 127) // 128
+    for name, counts in tiles.items():
+        assert 0 < counts[0] <= B * gtiles and counts == [counts[0]] * len(counts), (name, counts)
+    with pytest.raises(ValueError, match='topk_round'):
+        gal.set_option('topk_round', 100)                                       # not a multiple of 128
     gal.close()

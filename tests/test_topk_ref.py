@@ -142,7 +142,7 @@ def test_the_c_abi_carries_topk():
     while fn(len(keys)) is not None:
         keys.append(fn(len(keys)).decode())
         assert len(keys) < 100
-    assert 'topk_seed' in keys
+    assert 'topk_seed' in keys and 'topk_round' in keys and 'within_round' in keys
     from deep_insight_face import _native, oneshot
     assert 'dif_match_topk' in _native.SIGNATURES
     assert oneshot.TOPK_MAX == 128 and callable(oneshot.topk) and callable(oneshot.Gallery.topk_into)

@@ -18,6 +18,7 @@ import rank_ref
 import remove_ref
 import tagged_ref
 import test_topk_gpu as tg
+import test_topk_ids_gpu as ti
 import topk_ref
 
 pytestmark = pytest.mark.gpu
@@ -462,4 +463,68 @@ def test_tagged_cuda_in_cuda_out_and_no_host_read(cuda):
     tg._check(tg._np((ti, td)), _masked(B, G, D, 1), k, 1)
     six = tagged_ref.masked(tg._oracle(B, G, D, 1), tagged_ref.case_tags(G), np.full(B, 6, dtype=np.int64))
     tg._check(tg._np((bi, bd)), six, k, 1)
+    gal.close()
+
+
+# ------------------------------------------------------------------------------------------- 10
+def _round_masks(B):
+    """tagged_ref.case_masks with every block of 128 probes one step further along the cycle.  The cycle's period, 8, divides
+    128, so under case_masks(B) itself -- and under any rotation of the whole array -- probe 128 + j carries probe j's mask
+    and a launch that dropped its `probe_masks + b0` would answer correctly."""
+    i = np.arange(B)
+    m = tagged_ref.case_masks(B + B // 128 + 1)[i + i // 128].copy()
+    m.setflags(write=False)
+    return m
+
+
+@pytest.mark.parametrize('metric', [0, 1])
+@pytest.mark.parametrize('k', [5, 128])
+@pytest.mark.parametrize('B,G,D', tg.ROUND_SHAPES)
+def test_tagged_rounds(cuda, B, G, D, k, metric):
+    """Rounds of probes (test_topk_gpu.py's section 9), both tagged entries: "topk_round" 0, 128 (and 256 at B = 300), 0 on one
+    handle; every answer passes the oracle check, and the forced-round answers and the one after the option is taken back equal
+    the first one-round answer bit for bit; the identities with every probe's own identity excluded.  Rounds two and three
+    hold probes whose mask admits no row: all padding.  "topk_tagged_tiles" and "topk_ids_tiles" count (probe, tile)
+    evaluations, which do not depend on the split: a forced-round call reports the one-round call's number (a counter zeroed
+    in every round reports the last round's alone).  Before the device is asked: the oracle under the masks a dropped `+ b0`
+    would read differs from the true one in every round after the first."""
+    from deep_insight_face import oneshot
+    probes, gal_np, pick = tg._inputs(B, G, D)
+    full = tg._oracle(B, G, D, metric)
+    tags, masks, labels, ex = tagged_ref.case_tags(G), _round_masks(B), _labels(G), pick.astype(np.int64)
+    fm = tagged_ref.masked(full, tags, masks)
+    want = topk_ref.topk_full(fm, k)
+    for per in tg._round_options(B)[1:-1]:
+        wrong = topk_ref.topk_full(tagged_ref.masked(full, tags, tg._without_offset(masks, per)), k)
+        for sl in tg._later_rounds(B, per):
+            assert (wrong[0][sl] != want[0][sl]).any(), (per, sl)
+    blind = ~tagged_ref.eligible(tags, masks).any(1)                            # probes whose mask admits no row
+    assert blind[:128].any() and all(blind[sl].any() for sl in tg._later_rounds(B, 128) if sl.stop - sl.start >= 8)
+    tg._cap(fm, k, metric)
+    ti._cap(fm, labels, k, metric, ex)
+    gal = oneshot.Gallery(gal_np)
+    p = torch.from_numpy(probes).cuda()
+    t_dev, m_dev, l_dev, e_dev = (torch.from_numpy(np.array(a)).cuda() for a in (tags, masks, labels, ex))
+    first, first_ids, tiles = None, None, {'rows': [], 'ids': [], 'ids, topk_ids_tiles': []}
+    for per in tg._round_options(B):
+        gal.set_option('topk_round', per)
+        got = tg._np(gal.topk(p, k, metric, t_dev, m_dev))
+        tiles['rows'].append(gal.stat('topk_tagged_tiles'))
+        tg._check(got, fm, k, metric)
+        assert (got[0][blind] == -1).all() and np.isnan(got[1][blind]).all()
+        first = first or got
+        _same(got, first)
+        ids = tg._np(gal.topk_ids(p, k, l_dev, metric, e_dev, t_dev, m_dev))
+        tiles['ids'].append(gal.stat('topk_tagged_tiles'))
+        tiles['ids, topk_ids_tiles'].append(gal.stat('topk_ids_tiles'))
+        ti._check(ids, fm, labels, k, metric, ex)
+        assert (ids[0][blind] == -1).all() and np.isnan(ids[1][blind]).all() and (ids[2][blind] == -1).all()
+        first_ids = first_ids or ids
+        _same(ids, first_ids)
+    print('topk_tagged_tiles', (B, G, D), k, metric, tiles)
+    gtiles = (G + 127) // 128
+    for name, counts in tiles.items():
+        assert 0 < counts[0] <= int((~blind).sum()) * gtiles and counts == [counts[0]] * len(counts), (name, counts)
+    with pytest.raises(ValueError, match='topk_round'):
+        gal.set_option('topk_round', 100)                                       # not a multiple of 128
     gal.close()

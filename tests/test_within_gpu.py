@@ -14,7 +14,12 @@ import numpy as np
 import pytest
 import torch
 
+import cluster_ref
+import dbscan_ref
 import golden_inputs as gi
+import rank_ref
+import topk_ids_ref
+import topk_ref
 from oracle import distance as od
 
 pytestmark = pytest.mark.gpu
@@ -352,3 +357,142 @@ def test_within_arguments(cuda):
     c, i, d = empty.within(probes, 0.5, 1, max_hits=4)                         # np.flatnonzero of an empty array
     assert c.dtype == np.int64 and not c.any() and (i == -1).all() and np.isnan(d).all()
     empty.close()
+
+
+# ------------------------------------------------------------------------------------------- 8
+# Rounds of probes.  within_run splits a call into rounds of `per` probes when the census would pass its cap -- at a million
+# rows from 17 153 probes up.  Gallery option "within_round" lowers `per`, so the loop and its per-round offsets run here:
+# 128 + 1 probes (the last round on the 32-probe census tile), 128 + 128 + 44 (the 64-probe tile; 256 + 44 with the option at
+# 256) and three full rounds.  With the option at 0 the same arrays are one launch of three probe blocks.
+ROUND_SHAPES = [(129, 257, 512), (300, 1000, 128), (384, 1000, 128)]
+
+
+def _round_options(B):
+    """One round, forced rounds, one round again."""
+    return (0, 128, 256, 0) if B == 300 else (0, 128, 0)
+
+
+def _bits(a):
+    """An array as integers that compare bit for bit, every NaN taken as one value."""
+    if a.dtype != np.float32:
+        return a
+    return np.where(np.isnan(a), np.uint32(0x7fc00000), a.view(np.uint32))
+
+
+def _identical(got, first):
+    assert len(got) == len(first)
+    for i, (g, f) in enumerate(zip(got, first)):
+        assert g.dtype == f.dtype and g.shape == f.shape, i
+        bad = np.argwhere(_bits(g) != _bits(f))
+        assert bad.shape[0] == 0, (i, bad[:8])
+
+
+@pytest.mark.parametrize('metric', [0, 1])
+@pytest.mark.parametrize('B,G,D', ROUND_SHAPES)
+def test_within_rounds(cuda, B, G, D, metric):
+    """"within_round" 0, 128 (and 256 at B = 300), 0 on one handle: every answer passes the oracle check, and the forced-round
+    answers and the one after the option is taken back equal the first one-round answer bit for bit.  The sparse tolerance with
+    lists of 8 on both metrics; the dense one on metric 0 with lists of 64 and count-only (max_hits = 0: the list pointers stay
+    null through the offset arithmetic), on metric 1 through the whole hit mask."""
+    from deep_insight_face import oneshot
+    probes, gal_np = _inputs(B, G, D)
+    full = _oracle(B, G, D, metric)
+    assert not np.isnan(full).any()
+    t, gap = _sparse_t(full)
+    assert gap >= 1e-3, gap
+    sparse = _expect(full, t, 8)
+    assert 1 <= sparse[0].min() and sparse[0].max() <= 8
+    tm = _median_t(full)
+    if metric == 1:
+        assert (np.abs(full.astype(np.float64) - float(tm)) <= NEAR).mean() <= 2e-4
+    gal = oneshot.Gallery(gal_np)
+    first = {}
+    for per in _round_options(B):
+        gal.set_option('within_round', per)
+        got = gal.within(probes, t, metric, max_hits=8)
+        _check(got, sparse, metric)
+        _identical(got, first.setdefault('sparse', got))
+        if metric == 0:
+            for K in (64, 0):
+                got = gal.within(probes, tm, 0, max_hits=K)
+                assert got[1].shape == (B, K) and got[2].shape == (B, K)
+                _check(got, _expect(full, tm, K), 0)
+                _identical(got, first.setdefault(K, got))
+        else:
+            cnt, mask = _device_mask(gal, probes, tm, 1, G)
+            _check_near(cnt, mask, full, tm)
+            _identical((cnt, mask), first.setdefault('mask', (cnt, mask)))
+    with pytest.raises(ValueError, match='within_round'):
+        gal.set_option('within_round', 100)                                    # not a multiple of 128
+    with pytest.raises(ValueError, match='within_round'):
+        gal.set_option('within_round', -128)
+    gal.close()
+
+
+# ------------------------------------------------------------------------------------------- 9
+def test_shared_workspaces_survive_a_non_monotone_sequence_of_queries(cuda):
+    """within, rank, cluster and dbscan share within_census / within_thr, the four top-k entries share topk_min, and each
+    compares its need with a capacity another may have set.  One handle of 1000 x 128 rows through top-k at 3 probes, within at
+    300, rank at 37, cluster, within in forced rounds, an append of 300 rows (8 gallery tiles become 11: the census need grows
+    at the same number of probes), within in one round and in forced rounds, topk_ids at 300, dbscan, top-k at 130 -- every
+    step against its oracle on metric 0, bit for bit."""
+    from deep_insight_face import oneshot
+    B, G, D = 300, 1000, 128
+    probes, gal_np = _inputs(B, G, D)
+    pick = rank_ref.distances(probes, gal_np[:G // 4], 0).argmin(1)             # each probe's identity: its nearest first copy
+    extra = (gal_np[:300] + 0.05 * np.random.default_rng(5).standard_normal((300, D))).astype(np.float32)
+    rows = {G: gal_np, G + 300: np.concatenate([gal_np, extra])}
+    full = {n: rank_ref.distances(probes, r, 0) for n, r in rows.items()}
+    assert not any(np.isnan(f).any() for f in full.values())
+    lower = {n: cluster_ref.lower_distances(r, 0) for n, r in rows.items()}
+    gal = oneshot.Gallery(gal_np)
+
+    def topk(n, k):
+        idx, dist = gal.topk(probes[:n], k, 0)
+        want = topk_ref.topk_full(full[len(gal)][:n], k)
+        assert np.array_equal(idx, want[0])
+        _check_dist(dist, want[1], 0)
+
+    def within(n):
+        f = full[len(gal)][:n]
+        for t, K in ((_sparse_t(f)[0], 8), (_median_t(f), 64), (_median_t(f), 0)):
+            _check(gal.within(probes[:n], t, 0, max_hits=K), _expect(f, t, K), 0)
+
+    def gap_t(inside=False):
+        """The midpoint of the widest gap between the pairwise distances (identities apart); `inside`: the median distance
+        within an identity, a tolerance ON a distance (metric 0 is bit-identical) that leaves core, border and noise rows."""
+        v = np.sort(cluster_ref.pair_values(lower[len(gal)]))
+        k = int(np.argmax(np.diff(v)))
+        return np.float32(v[k // 2]) if inside else np.float32((v[k] + v[k + 1]) / 2)
+
+    topk(3, 5)                                                                  # 1
+    within(300)                                                                 # 2
+    mates = (pick[:37] + (G // 4) * (np.arange(37) % 4)).astype(np.int64)       # 3
+    rank, md = gal.rank(probes[:37], mates, 0)
+    want = rank_ref.rank_full(full[G][:37], mates)
+    assert np.array_equal(rank, want[0]) and (want[0] <= 4).all()
+    _check_dist(md, want[1], 0)
+    labels, n = gal.cluster(gap_t(), 0)                                         # 4
+    want = cluster_ref.cluster_from(lower[G], G, gap_t())
+    assert want[1] == G // 4 and int(n) == want[1] and np.array_equal(labels.cpu().numpy(), want[0])
+    gal.set_option('within_round', 128)                                         # 5
+    within(300)
+    gal.update(extra)                                                           # 6
+    assert len(gal) == G + 300
+    gal.set_option('within_round', 0)                                           # 7
+    within(300)
+    gal.set_option('within_round', 128)
+    within(300)
+    gal.set_option('within_round', 0)
+    row_labels = (np.arange(G + 300) % (G // 4)).astype(np.int64)               # 8
+    got = gal.topk_ids(probes, 5, row_labels, 0)
+    want = topk_ids_ref.topk_ids_full(full[G + 300], row_labels, 5)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[2], want[2])
+    _check_dist(got[1], want[1], 0)
+    labels, degree, counts = gal.dbscan(gap_t(True), 3, 0)                      # 9
+    want = dbscan_ref.dbscan_from(lower[G + 300], G + 300, gap_t(True), 3)
+    assert all(kind.sum() >= 10 for kind in dbscan_ref.kinds(want[0], want[1], 3))     # core, border and noise rows
+    assert tuple(counts.cpu().tolist()) == tuple(want[2])
+    assert np.array_equal(degree.cpu().numpy(), want[1]) and np.array_equal(labels.cpu().numpy(), want[0])
+    topk(130, 128)                                                              # 10
+    gal.close()
