@@ -226,6 +226,20 @@ static int grow(P** p, size_t* cap, size_t need, size_t elem) {
   return 0;
 }
 
+// Lifts a kernel's dynamic-LDS limit to `bytes`, once per (device, kernel): the kernel is the template argument, so every
+// instantiation has flags of its own
+template <auto Kern>
+static int allow_lds_once(int bytes) {
+  static bool done[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!done[dev]) {
+    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done[dev] = true;
+  }
+  return 0;
+}
+
 int match_tile_kind(int B);                                  // match.hip: the f32 tile shape for B probes
 // match.hip: gallery parts (blocks along the rows) of a tile launch over the first `rows` rows (-1: all of them)
 int match_plan_parts(const Gallery* g, int B, bool bd, int64_t rows = -1);

@@ -17,7 +17,7 @@
 //     A[j] = c(t_j)  and  B[j] = c(t_j'),  t_j' = nextafterf(t_j, -inf):  dist < t_j  iff  dist <= t_j'  (rank_prep_kernel's
 //     device for a strict comparison).  A is padded with +inf to P - 1 entries, P the power of two above T; B[T] = +inf.
 //  2. roc_prep_kernel   -- per probe the scale (1 / |q|, or |q|^2), the half width e of the band in that space, and H.
-//  3. roc_census_kernel -- a sibling of within_census_kernel: the same tiles, the same f32 MFMA main loop on the rows
+//  3. roc_census_kernel -- a sibling of key_tiles (key_tiles.hpp): the same tiles, the same f32 MFMA main loop on the rows
 //     themselves, the same XCD-aware block order, the same key.  One pass whatever T is.  The epilogue normalises each key,
 //        kn = key / |q|  (metric 1)     kn = key + |q|^2  (metric 0)
 //     finds  b = number of j with A[j] < kn - e  by a branch-free binary search of log2 P LDS reads, and calls the pair
@@ -48,10 +48,7 @@
 //     same flush.  Exactly the flagged pairs are evaluated, not their 128-row tiles.  A block takes ROC_CHUNK masks per trip
 //     ("roc_blocks" caps the grid; tests force many trips); the queue's two counters are used in turn.
 //  5. roc_finish_kernel -- prefix sums of the bins -> accept, totals.
-#include "gemm_core.hpp"
-#include "dif_internal.hpp"
-#include "match_ref.hpp"
-#include "match_band.hpp"
+#include "key_tiles.hpp"
 
 namespace dif {
 
@@ -111,22 +108,20 @@ __global__ __launch_bounds__(256) void roc_prep_kernel(const float* __restrict__
 template <class T>
 __global__ __launch_bounds__(T::NT, 2) void roc_census_kernel(const float* __restrict__ gallery, int64_t G,
                                                             const float* __restrict__ probes, int B, int D,
-                                                            const float* __restrict__ aux, int metric,
+                                                            const float* __restrict__ aux, int metric, int nparts,
                                                             const f32x4* __restrict__ thr, const float* __restrict__ tab,
                                                             int nT, int P, const int64_t* __restrict__ probe_labels,
                                                             const int64_t* __restrict__ row_labels,
                                                             const int64_t* __restrict__ first_row, int64_t index_base,
                                                             unsigned* __restrict__ mask,
-                                                            unsigned long long* __restrict__ bins, int nparts) {
+                                                            unsigned long long* __restrict__ bins) {
   constexpr int WM = T::WM, WN = T::WN;
   static_assert(T::BM == WITHIN_BM && T::WGM * WM == 4, "four 32-bit mask words per 128 gallery rows, one per wave row and m");
   static_assert(T::NT == ROC_NT, "the register copy of the histogram is laid out for 256 threads");
   static_assert(T::LDS_FLOATS >= ROC_TAB + (ROC_MAX_T + 1) + 2 * (ROC_MAX_T + 1), "the tables and the histogram alias the main loop's LDS");
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  // block -> (gallery part, probe block) as within_census_kernel: the probe blocks of one part share an XCD
-  const int cblocks = (B + T::BN - 1) / T::BN;
-  const int grp = (int)blockIdx.x / (8 * cblocks), rem = (int)blockIdx.x % (8 * cblocks);
-  const int part = grp * 8 + (rem & 7), cblk = rem >> 3;
+  const TileBlock tb = tile_block((B + T::BN - 1) / T::BN);
+  const int part = tb.part;
   if (part >= nparts) return;
   // valid between the main loop's last barrier and the next tile's first store only
   float* sA = smem;                                            // [P - 1] (+inf from T on)
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(T::NT, 2) void roc_census_kernel(const float* __res
   unsigned* sH = reinterpret_cast<unsigned*>(smem + ROC_TAB + ROC_MAX_T + 1);   // [T + 1][2]
   const int tid = threadIdx.x;
   const int wc = T::wave_col();
-  const int p0 = cblk * T::BN;
+  const int p0 = tb.cblk * T::BN;
   const int ksteps = D / BK;
   const int64_t gtiles = (G + T::BM - 1) / T::BM;
   const int nhist = 2 * (nT + 1);
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(T::NT, 2) void roc_census_kernel(const float* __res
     // dots -> keys -> a bin or a mask bit per pair.  aux[g] = -1/|g| (metric 1) or |g|^2 (metric 0), NaN for the rows kept
     // out of the filter: a NaN key fails every comparison and is BORDERLINE.  Rows past G carry label -1: in no pair.
     int lane = tid & 63;
-    asm volatile("" : "+v"(lane));                           // opaque per tile, as in within_census_kernel
+    asm volatile("" : "+v"(lane));                           // opaque per tile, as in key_tiles
     const int wr = T::wave_row();
     const int64_t rows_left = G - g0;
     const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(aux + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 4));
@@ -337,31 +332,6 @@ __global__ __launch_bounds__(256) void roc_finish_kernel(const unsigned long lon
   }
 }
 
-template <class T>
-static int launch_roc_census(const Gallery* g, const float* probes, int B, int metric, int nT, int P,
-                             const int64_t* probe_labels, const int64_t* row_labels, const int64_t* first_row, hipStream_t st) {
-  auto kern = roc_census_kernel<T>;
-  constexpr int lds = T::LDS_BYTES;
-  static bool done[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!done[dev]) {
-    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    done[dev] = true;
-  }
-  const int nparts = match_plan_parts(g, B, false);
-  const int64_t gtiles = (g->n + T::BM - 1) / T::BM;
-  if ((gtiles + nparts - 1) / nparts > ROC_BLOCK_TILES)      // (16 M rows per block: no device holds such a gallery)
-    return set_error("dif_match_roc: %lld gallery tiles over %d blocks would overflow a block's 32-bit counters", (long long)gtiles, nparts);
-  const int cblocks = (B + T::BN - 1) / T::BN;
-  dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
-  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, g->n, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
-                     reinterpret_cast<const f32x4*>(g->roc_thr), g->roc_tab, nT, P, probe_labels, row_labels, first_row,
-                     g->index_base, g->roc_mask, g->roc_bins, nparts);
-  DIF_HIP(hipGetLastError());
-  return 0;
-}
-
 int roc_run(Gallery* g, const float* probes, int B, int metric, const int64_t* probe_labels, const int64_t* row_labels,
             const int64_t* first_row, const float* thresholds, int nT, int64_t* accept_out, int64_t* totals_out,
             hipStream_t st) {
@@ -374,19 +344,12 @@ int roc_run(Gallery* g, const float* probes, int B, int metric, const int64_t* p
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
-  // probes per round: whole 128-probe blocks whose masks stay below ROC_MASK_MAX, or the "roc_round" option if that is fewer
-  int64_t per = (int64_t)(ROC_MASK_MAX / (size_t)gtiles) / 128 * 128;
-  if (g->roc_round > 0 && g->roc_round < per) per = g->roc_round;
-  if (per < 128) per = 128;
-  if (per > B) per = B;
-  const size_t need_m = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
-  if (need_m > g->roc_mask_cap || need_t > g->roc_thr_cap || !g->roc_tab || !g->roc_bins) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
-    if (grow(&g->roc_mask, &g->roc_mask_cap, need_m, 4 * sizeof(unsigned))) return -1;
-    if (grow(&g->roc_thr, &g->roc_thr_cap, need_t, 4 * sizeof(float))) return -1;
-    if (!g->roc_tab) DIF_HIP(hipMalloc(&g->roc_tab, 2 * ROC_TAB * sizeof(float)));
-    if (!g->roc_bins) DIF_HIP(hipMalloc(&g->roc_bins, (ROC_BINS + 1) * sizeof(unsigned long long)));
-  }
+  const Rounds rounds = plan_rounds(gtiles, B, ROC_MASK_MAX, g->roc_round, 128);   // ("roc_round"; a word here is a mask)
+  if (ensure(st, workspace(&g->roc_mask, &g->roc_mask_cap, (size_t)gtiles * (size_t)rounds.per, 4 * sizeof(unsigned)),
+             workspace(&g->roc_thr, &g->roc_thr_cap, (size_t)rounds.per, 4 * sizeof(float))))
+    return -1;
+  if (!g->roc_tab) DIF_HIP(hipMalloc(&g->roc_tab, 2 * ROC_TAB * sizeof(float)));
+  if (!g->roc_bins) DIF_HIP(hipMalloc(&g->roc_bins, (ROC_BINS + 1) * sizeof(unsigned long long)));
   int P = 2;
   while (P <= nT) P <<= 1;                                   // the power of two above T: P - 1 searchable entries
   hipLaunchKernelGGL(roc_table_kernel, dim3((ROC_BINS + 255) / 256), dim3(256), 0, st, thresholds, nT, metric, g->roc_tab,
@@ -394,17 +357,23 @@ int roc_run(Gallery* g, const float* probes, int B, int metric, const int64_t* p
   DIF_HIP(hipGetLastError());
   const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
   const size_t res_lds = (size_t)(nT + 2 * (nT + 2)) * 4;
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int nb = (int)(B - b0 < per ? B - b0 : per);
+  const int rc = for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
     const int64_t* fr = first_row ? first_row + b0 : nullptr;
     hipLaunchKernelGGL(roc_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits,
                        reinterpret_cast<f32x4*>(g->roc_thr));
     DIF_HIP(hipGetLastError());
-    const int rc = with_census_tile(nb, [&](auto tile) {
-      return launch_roc_census<decltype(tile)>(g, pr, nb, metric, nT, P, probe_labels + b0, row_labels, fr, st);
-    });
-    if (rc) return rc;
+    const int nparts = key_tiles_parts(g, nb);
+    if ((gtiles + nparts - 1) / nparts > ROC_BLOCK_TILES)      // (16 M rows per block: no device holds such a gallery)
+      return set_error("dif_match_roc: %lld gallery tiles over %d blocks would overflow a block's 32-bit counters", (long long)gtiles, nparts);
+    if (with_census_tile(nb, [&](auto tile) {
+          using T = decltype(tile);
+          return launch_key_tiles<roc_census_kernel<T>, T>(g, pr, nb, metric, st, T::LDS_BYTES, -1, nparts,
+                                                           reinterpret_cast<const f32x4*>(g->roc_thr), g->roc_tab, nT, P,
+                                                           probe_labels + b0, row_labels, fr, g->index_base, g->roc_mask,
+                                                           g->roc_bins);
+        }))
+      return -1;
     const int64_t nmask = gtiles * nb;
     const int64_t chunks = (nmask + ROC_CHUNK - 1) / ROC_CHUNK, cap = g->roc_blocks > 0 ? g->roc_blocks : 2048;
     const int64_t blocks = chunks < cap ? chunks : cap;
@@ -414,7 +383,9 @@ int roc_run(Gallery* g, const float* probes, int B, int metric, const int64_t* p
                        reinterpret_cast<const u32x4*>(g->roc_mask), nmask, nb, pr, g->rows, g->d, metric, clamp, plan,
                        thresholds, nT, probe_labels + b0, row_labels, g->roc_bins);
     DIF_HIP(hipGetLastError());
-  }
+    return 0;
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(roc_finish_kernel, dim3(1), dim3(256), 0, st, g->roc_bins, nT, accept_out, totals_out);
   DIF_HIP(hipGetLastError());
   return 0;

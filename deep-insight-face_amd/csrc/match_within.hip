@@ -15,10 +15,10 @@
 // The B x G distances are never materialised.  The tolerance is known before the first tile, so -- unlike the arg-min -- there
 // is no running state: two stages, no atomics on global memory, no lists, no overflow path, deterministic by construction.
 //
-//  1. within_census_kernel -- a sibling of match_tile_kernel<T, false>: the same tiles, the same f32 MFMA main loop on the
-//     rows themselves, the same XCD-aware block order, the same search key in the epilogue
+//  1. within_census_kernel -- key_tiles (key_tiles.hpp: match_tile_kernel<T, false>'s tiles, f32 MFMA main loop on the rows
+//     themselves and XCD-aware block order) with the census policy: the search key of the epilogue
 //        metric 1: key = -dot / |g|        metric 0: key = |g|^2 - 2 dot
-//     -- classifies every key against two per-probe thresholds (within_prep_kernel):
+//     is classified against two per-probe thresholds (within_prep_kernel):
 //        SURE        key <= T - E  and |key| < H      the reference's distance is <= t whatever the rounding
 //        OUT         key >  T + E                     ... is > t (or NaN) whatever the rounding
 //        BORDERLINE  everything else, a NaN key included (rows kept out of the filter carry a NaN ingredient: zero-norm,
@@ -51,10 +51,7 @@
 //        E = u 18 gmax^2 + (2 c + 2 u) |q| gmax  +  32 u (|q| + gmax)^2 + (D / 64 + 8) u (|q|^2 + gmax^2) + u (|t| + |q|^2).
 //   |q| enters as sqrt(sum) * 1.0001 as in probe_eps_one.  Deliberately generous: a wider E only costs resolved tiles.
 //   Probes whose |q|^2 leaves [NORM_LO, NORM_HI] (metric 0: exceeds NORM_HI) or is not finite: every tile is resolved.
-#include "gemm_core.hpp"
-#include "dif_internal.hpp"
-#include "match_ref.hpp"
-#include "match_band.hpp"
+#include "key_tiles.hpp"
 
 namespace dif {
 
@@ -149,99 +146,51 @@ __global__ __launch_bounds__(256) void mate_dist_kernel(const float* __restrict_
   owned_out[p] = mated ? 1 : 0;
 }
 
+// The census policy of key_tiles: two counts per probe column against the column's thresholds, a 16-bit word.  A NaN key is
+// neither SURE nor OUT.  Rows past G are OUT (key +inf; where T + E is +inf as well they count as borderline, and the resolve
+// stage, which stops at G, finds nothing in them).
+struct CensusEpi : KeyEpi {
+  const f32x4* __restrict__ thr;
+  unsigned short* __restrict__ census;
+  using Meet = int;                                           // sure | not out << 16
+  struct Col {
+    float ts, tm, hk;
+  };
+  struct State {
+    int sure, nout;
+  };
+  __device__ __forceinline__ CensusEpi(const f32x4* thr_, unsigned short* census_) : thr(thr_), census(census_) {}
+  __device__ __forceinline__ Col column(int p, int B) const {
+    // (a column that pads the probe block: its words are not stored)
+    const f32x4 v = (p < B) ? thr[p] : f32x4{0.f, 0.f, 0.f, 0.f};
+    return Col{v[0], v[1], v[2]};
+  }
+  __device__ __forceinline__ State start(const Tile&, int) const { return State{0, 0}; }
+  __device__ __forceinline__ void visit(State& s, const Col& c, const Rows&, int, float key, bool ok) const {
+    key = ok ? key : __builtin_inff();
+    s.sure += (key <= c.ts && fabsf(key) < c.hk) ? 1 : 0;
+    s.nout += !(key > c.tm) ? 1 : 0;
+  }
+  __device__ __forceinline__ Meet partial(const State& s) const { return s.sure | (s.nout << 16); }
+  __device__ static __forceinline__ Meet combine(Meet a, Meet b) { return a + b; }
+  __device__ __forceinline__ void store(int64_t i, Meet v) const {
+    const int sure = v & 0xffff, bord = (v >> 16) - sure;     // SURE implies not OUT (T - E <= T + E)
+    census[i] = (unsigned short)(sure | (bord << 8));
+  }
+};
+
 template <class T>
 __global__ __launch_bounds__(T::NT, 2) void within_census_kernel(const float* __restrict__ gallery, int64_t G,
                                                                const float* __restrict__ probes, int B, int D,
-                                                               const float* __restrict__ aux, int metric,
+                                                               const float* __restrict__ aux, int metric, int nparts,
                                                                const f32x4* __restrict__ thr,
-                                                               unsigned short* __restrict__ census, int nparts) {
-  constexpr int WM = T::WM, WN = T::WN;
-  static_assert(T::BM == WITHIN_BM, "one census word per 128 gallery rows");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  // block -> (gallery part, probe block) as match_tile_kernel: the probe blocks of one part share an XCD
-  const int cblocks = (B + T::BN - 1) / T::BN;
-  const int grp = (int)blockIdx.x / (8 * cblocks), rem = (int)blockIdx.x % (8 * cblocks);
-  const int part = grp * 8 + (rem & 7), cblk = rem >> 3;
-  if (part >= nparts) return;
-  int* s_cnt = reinterpret_cast<int*>(smem + T::LDS_FLOATS);   // [WGM][BN]: sure | not out << 16, per wave row
-  const int tid = threadIdx.x;
-  const int wc = T::wave_col();
-  const int p0 = cblk * T::BN;
-  const int ksteps = D / BK;
-  const int64_t gtiles = (G + T::BM - 1) / T::BM;
-
-  float ts[WN], tm[WN], hk[WN];
-  int col[WN];
-#pragma unroll
-  for (int n = 0; n < WN; ++n) {
-    col[n] = (wc * WN + n) * 32 + (tid & 31);
-    // (a column that pads the probe block: its words are not stored)
-    const f32x4 v = (p0 + col[n] < B) ? thr[p0 + col[n]] : f32x4{0.f, 0.f, 0.f, 0.f};
-    ts[n] = v[0];
-    tm[n] = v[1];
-    hk[n] = v[2];
-  }
-
-  for (int64_t gt = part; gt < gtiles; gt += nparts) {
-    const int64_t g0 = gt * T::BM;
-    f32x16 acc[WM][WN];
-    zero_acc<T>(acc);
-    RowLoader<T::NA, T::RP> al(gallery + g0 * D, G - g0, D);
-    RowLoader<T::NB, T::RP> bl(probes + (int64_t)p0 * D, (int64_t)B - p0, D);
-    gemm_mainloop<T>(al, bl, 0, ksteps, smem, acc);
-
-    // dots -> keys -> two counts per probe column.  aux[g] = -1/|g| (metric 1) or |g|^2 (metric 0), NaN for the rows kept
-    // out of the filter: a NaN key is neither SURE nor OUT.  Rows past G are OUT (key +inf; where T + E is +inf as well
-    // they count as borderline, and the resolve stage, which stops at G, finds nothing in them).
-    int lane = tid & 63;
-    asm volatile("" : "+v"(lane));                           // opaque per tile, as in match_tile_epilogue: no row index is hoisted
-    const int wr = T::wave_row();
-    const int64_t rows_left = G - g0;
-    const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(aux + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 4));
-    int cs[WN], cn[WN];
-#pragma unroll
-    for (int n = 0; n < WN; ++n) cs[n] = cn[n] = 0;
-#pragma unroll
-    for (int m = 0; m < WM; ++m) {
-      const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {                          // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
-        const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bool ok = rbase + 8 * q + j < rows_left;
-#pragma unroll
-          for (int n = 0; n < WN; ++n) {
-            const float dot = acc[m][n][4 * q + j];
-            float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
-            key = ok ? key : __builtin_inff();
-            cs[n] += (key <= ts[n] && fabsf(key) < hk[n]) ? 1 : 0;
-            cn[n] += !(key > tm[n]) ? 1 : 0;
-          }
-        }
-      }
-    }
-    // lanes l and l + 32 hold different rows of the same probe column; the WGM waves stacked on M meet in LDS
-#pragma unroll
-    for (int n = 0; n < WN; ++n) {
-      int v = cs[n] | (cn[n] << 16);
-      v += __shfl_xor(v, 32);
-      if (lane < 32) s_cnt[wr * T::BN + col[n]] = v;
-    }
-    lds_barrier();
-    for (int c = tid; c < T::BN; c += T::NT) {
-      int v = 0;
-#pragma unroll
-      for (int w = 0; w < T::WGM; ++w) v += s_cnt[w * T::BN + c];
-      const int sure = v & 0xffff, bord = (v >> 16) - sure;   // SURE implies not OUT (T - E <= T + E)
-      if (p0 + c < B) census[gt * B + p0 + c] = (unsigned short)(sure | (bord << 8));
-    }
-    // (s_cnt is written again only after the next tile's main loop, i.e. behind several barriers)
-  }
+                                                               unsigned short* __restrict__ census) {
+  key_tiles<T>(gallery, G, probes, B, D, aux, metric, nparts, CensusEpi(thr, census));
 }
 
 // One block per probe; `census` rows are B words apart.  All control flow is block-uniform: every wave derives the same
-// counts from the same LDS words.
+// counts from the same LDS words.  (This kernel and the two select kernels synchronise inside a tile and keep walk_words'
+// loop written out: on the shared function they measured 1 to 5 % slower)
 __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const unsigned short* __restrict__ census, int64_t G,
                                                                       int B, const f32x4* __restrict__ thr,
                                                                       const float* __restrict__ probes,
@@ -337,28 +286,21 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
   const bool all = thr[p][3] != 0.f;
   int64_t sure_rows = 0;                                      // the same in every thread
   int mine = 0;                                               // rows this wave evaluated and counted (G < 2^31)
-  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
-    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
-    s_word[tid] = w;
-    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
-    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
-    for (int j = 0; j < nw; ++j) {
-      const int sure = s_word[j] & 0xff, bord = s_word[j] >> 8;
-      if (!(all || bord > 0)) {
-        sure_rows += sure;
-        continue;
-      }
-      const int64_t g0 = (t0 + j) * WITHIN_BM;
-      const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
-      for (int r = wave; r < rows; r += WITHIN_NW) {
-        float d;
-        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
-        const bool lower = EXT ? index_base + g0 + r < m_ext : g0 + r < mt.row;
-        mine += (d < dm || (d == dm && lower)) ? 1 : 0;       // NaN: neither
-      }
+  walk_words(census, B, p, gtiles, s_word, [&](unsigned short w) { return all || w != 0; }, [&](int64_t tl, unsigned short w) {
+    const int sure = w & 0xff, bord = w >> 8;
+    if (!(all || bord > 0)) {
+      sure_rows += sure;
+      return;
     }
-    __syncthreads();                                          // s_word is rewritten by the next round
-  }
+    const int64_t g0 = tl * WITHIN_BM;
+    const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
+    for (int r = wave; r < rows; r += WITHIN_NW) {
+      float d;
+      (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+      const bool lower = EXT ? index_base + g0 + r < m_ext : g0 + r < mt.row;
+      mine += (d < dm || (d == dm && lower)) ? 1 : 0;         // NaN: neither
+    }
+  });
   if (lane == 0) s_part[wave] = mine;
   __syncthreads();
   if (tid == 0) {
@@ -369,26 +311,14 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
   }
 }
 
-// `rows`: the census covers gallery rows [0, rows) only (-1: all of them); its words are laid out as for a gallery of `rows` rows
-template <class T>
-static int launch_census(const Gallery* g, const float* probes, int B, int metric, hipStream_t st, int64_t rows = -1) {
-  auto kern = within_census_kernel<T>;
-  constexpr int lds = T::LDS_BYTES + T::WGM * T::BN * 4;
-  static bool done[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!done[dev]) {
-    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    done[dev] = true;
-  }
-  if (rows < 0) rows = g->n;
-  const int nparts = match_plan_parts(g, B, false, rows);
-  const int cblocks = (B + T::BN - 1) / T::BN;
-  dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
-  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, rows, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
-                     reinterpret_cast<const f32x4*>(g->within_thr), g->within_census, nparts);
-  DIF_HIP(hipGetLastError());
-  return 0;
+// The census of nb probes at the thresholds in g->within_thr, over gallery rows [0, rows) only (-1: all of them); its words are
+// laid out as for a gallery of `rows` rows
+static int census_pass(const Gallery* g, const float* pr, int nb, int metric, hipStream_t st, int64_t rows = -1) {
+  return with_census_tile(nb, [&](auto tile) {
+    using T = decltype(tile);
+    return launch_key_tiles<within_census_kernel<T>, T>(g, pr, nb, metric, st, key_tiles_lds<T>, rows, key_tiles_parts(g, nb, rows),
+                                                        reinterpret_cast<const f32x4*>(g->within_thr), g->within_census);
+  });
 }
 
 int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
@@ -404,33 +334,24 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
     return 0;
   }
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
-  // probes per round: whole 128-probe blocks whose census stays below WITHIN_CENSUS_MAX words
-  int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
-  if (g->within_round > 0 && g->within_round < per) per = g->within_round;
-  if (per < 128) per = 128;
-  if (per > B) per = B;
-  const size_t need_c = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
-  if (need_c > g->within_census_cap || need_t > g->within_thr_cap) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
-    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
-    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
-  }
+  const Rounds rounds = plan_rounds(gtiles, B, WITHIN_CENSUS_MAX, g->within_round, 128);
+  if (ensure(st, workspace(&g->within_census, &g->within_census_cap, (size_t)gtiles * (size_t)rounds.per, sizeof(unsigned short)),
+             workspace(&g->within_thr, &g->within_thr_cap, (size_t)rounds.per, 4 * sizeof(float))))
+    return -1;
   const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int nb = (int)(B - b0 < per ? B - b0 : per);
+  return for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
     hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
                        g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
     DIF_HIP(hipGetLastError());
-    const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st); });
-    if (rc) return rc;
+    if (census_pass(g, pr, nb, metric, st)) return -1;
     hipLaunchKernelGGL(within_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
                        reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
                        max_hits, g->index_base, count_out + b0, max_hits ? idx_out + b0 * max_hits : nullptr,
                        max_hits ? dist_out + b0 * max_hits : nullptr);
     DIF_HIP(hipGetLastError());
-  }
-  return 0;
+    return 0;
+  });
 }
 
 int mate_dist_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, float* mate_dist_out,
@@ -457,41 +378,26 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
-  // probes per round as in within_run (an empty gallery has no census: one round, every probe unmated)
-  int64_t per = gtiles > 0 ? (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128 : B;
-  if (g->within_round > 0 && g->within_round < per) per = g->within_round;
-  if (per < 128) per = 128;
-  if (per > B) per = B;
-  const size_t need_c = (size_t)gtiles * (size_t)per, need_t = (size_t)per;
-  if (need_c > g->within_census_cap || need_t > g->within_thr_cap || need_t > g->rank_mate_cap) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
-    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
-    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
-    if (grow(&g->rank_mate, &g->rank_mate_cap, need_t, sizeof(RankMate))) return -1;
-  }
+  // (an empty gallery has no census: one round, every probe unmated)
+  const Rounds rounds = plan_rounds(gtiles, B, WITHIN_CENSUS_MAX, g->within_round, 128);
+  if (ensure(st, workspace(&g->within_census, &g->within_census_cap, (size_t)gtiles * (size_t)rounds.per, sizeof(unsigned short)),
+             workspace(&g->within_thr, &g->within_thr_cap, (size_t)rounds.per, 4 * sizeof(float)),
+             workspace(&g->rank_mate, &g->rank_mate_cap, (size_t)rounds.per, sizeof(RankMate))))
+    return -1;
   const float cdot = g->d * U24;
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int nb = (int)(B - b0 < per ? B - b0 : per);
+  return for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
     hipLaunchKernelGGL(rank_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits,
                        g->rows, g->n, g->index_base, mates + b0, clamp, plan, reinterpret_cast<f32x4*>(g->within_thr),
                        g->rank_mate, mate_dist_out ? mate_dist_out + b0 : nullptr, dm_in ? dm_in + b0 : nullptr);
     DIF_HIP(hipGetLastError());
-    if (gtiles > 0) {
-      const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st); });
-      if (rc) return rc;
-    }
-    if (dm_in)
-      hipLaunchKernelGGL(rank_resolve_kernel<true>, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
-                         reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
-                         mates + b0, g->index_base, rank_out + b0);
-    else
-      hipLaunchKernelGGL(rank_resolve_kernel<false>, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
-                         reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
-                         mates + b0, g->index_base, rank_out + b0);
+    if (gtiles > 0 && census_pass(g, pr, nb, metric, st)) return -1;
+    hipLaunchKernelGGL(dm_in ? rank_resolve_kernel<true> : rank_resolve_kernel<false>, dim3(nb), dim3(64 * WITHIN_NW), 0, st,
+                       g->within_census, g->n, nb, reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows,
+                       g->d, metric, clamp, plan, mates + b0, g->index_base, rank_out + b0);
     DIF_HIP(hipGetLastError());
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -500,7 +406,7 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
 //   idx = keep + index_base;  dist = d[keep];  unused slots: idx -1, dist NaN
 // Built on ONE fact, the OUT bound of the header comment: for a tolerance t, a row whose search key is > T(t) + E(t) has a
 // reference distance > t, or NaN.  No inverse of T, no SURE bound, no lists in the MFMA stage, no atomics on global memory.
-//   topk_tilemin_kernel  a sibling of within_census_kernel: the same tiles, main loop, block order and keys; per (gallery tile
+//   topk_tilemin_kernel  key_tiles with the tile-minimum policy: the census' tiles, main loop, block order and keys; per (gallery tile
 //                        of 128 rows, probe) it stores ONE float, the minimum key of the tile ("word"): -inf when a key of
 //                        the tile is NaN (a row kept out of the filter), rows past G count as +inf.  It takes no thresholds.
 //   topk_select_kernel   one block per probe (|q|^2 and the band are formed here: there is no prep kernel).
@@ -536,6 +442,75 @@ __device__ __forceinline__ float unord_f32(unsigned o) {
   return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
+// the integer image of the need-th smallest word of probe p (1 <= need <= gtiles): a radix select on the order-preserving
+// integer image of the float, one byte per pass (exact counts: deterministic)
+__device__ __forceinline__ unsigned topk_kappa(const float* __restrict__ words, int B, int p, int64_t gtiles,
+                                                   unsigned need, unsigned* s_hist, unsigned* s_sel) {
+  constexpr int NT = 64 * WITHIN_NW;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  unsigned prefix = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) s_hist[tid] = 0;
+    __syncthreads();
+    for (int64_t t = tid; t < gtiles; t += NT) {
+      const unsigned o = ord_f32(words[t * B + p]);
+      if ((unsigned)((unsigned long long)o >> (shift + 8)) == prefix) atomicAdd(&s_hist[(o >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (wave == 0) {                                          // four bins per lane, a scan over the lanes
+      unsigned c[4], sum = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        c[i] = s_hist[4 * lane + i];
+        sum += c[i];
+      }
+      unsigned incl = sum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+      }
+      const unsigned excl = incl - sum;
+      if (excl < need && need <= incl) {                      // exactly one lane: 1 <= need <= the total
+        unsigned r = need - excl;
+        int d = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          if (d == i && r > c[i]) {
+            r -= c[i];
+            d = i + 1;
+          }
+        s_sel[0] = (unsigned)(4 * lane + d);
+        s_sel[1] = r;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | s_sel[0];
+    need = s_sel[1];
+    // (s_sel is written again only behind the two barriers of the next pass, or of the next call)
+  }
+  return prefix;
+}
+
+// The tile-minimum policy of key_tiles.  aux is NaN for the rows kept out of the filter: fminf drops a NaN, so a NaN key is
+// tested for and makes the minimum -inf.
+struct TileMinEpi : KeyEpi {
+  float* __restrict__ words;
+  using Meet = float;
+  struct State {
+    float mn;
+  };
+  __device__ __forceinline__ explicit TileMinEpi(float* words_) : words(words_) {}
+  __device__ __forceinline__ State start(const Tile&, int) const { return State{__builtin_inff()}; }
+  __device__ __forceinline__ void visit(State& s, const Col&, const Rows&, int, float key, bool ok) const {
+    key = ok ? key : __builtin_inff();                        // a row past G
+    s.mn = (key != key) ? -__builtin_inff() : fminf(s.mn, key);   // (once -inf it stays -inf)
+  }
+  __device__ __forceinline__ Meet partial(const State& s) const { return s.mn; }
+  __device__ static __forceinline__ Meet combine(Meet a, Meet b) { return fminf(a, b); }
+  __device__ __forceinline__ void store(int64_t i, Meet v) const { words[i] = v; }
+};
+
 // Tagged (dif_match_topk_tagged, dif_match_topk_ids_tagged): row r is eligible for probe p iff (row_tags[r] & probe_masks[p])
 // != 0, on the raw 64 bits.  The word becomes the minimum key over the ELIGIBLE rows of the tile (-inf when an eligible row's
 // key is NaN), and a tile with no eligible row for the probe stores a positive quiet NaN: "nothing here".  No eligible row can
@@ -545,123 +520,58 @@ __device__ __forceinline__ float unord_f32(unsigned o) {
 // under metric 0.)  The minimum starts as NaN, fminf drops a NaN operand, so the reductions over lanes and waves keep NaN
 // exactly when every part is NaN.  The tags of the thread's rows and the masks of its probe columns are read once per tile
 // through buffer descriptors bounded like `arsrc`: a row past G reads tag 0, a probe past B mask 0 -- never eligible.
-// Tagged = false is the kernel as it was; the two pointers are unused there.
+// The tagged tile-minimum policy: the four row tags per q step and the column masks per tile
+struct TaggedTileMinEpi : KeyEpi {
+  float* __restrict__ words;
+  const int64_t* __restrict__ row_tags;
+  const int64_t* __restrict__ probe_masks;
+  using Meet = float;
+  struct Tile {
+    __amdgpu_buffer_rsrc_t trsrc, mrsrc;
+  };
+  struct Rows {
+    u32x4 tg[2];                                              // four tags, {lo, hi} each
+  };
+  struct State {
+    float mn;
+    u32x2 msk;                                                // the column's mask, once per tile
+  };
+  __device__ __forceinline__ TaggedTileMinEpi(float* words_, const int64_t* row_tags_, const int64_t* probe_masks_)
+      : words(words_), row_tags(row_tags_), probe_masks(probe_masks_) {}
+  __device__ __forceinline__ Tile tile(int64_t g0, int rows, int p0, int cols) const {
+    return Tile{make_rsrc(row_tags + g0, (uint32_t)(rows * 8)), make_rsrc(probe_masks + p0, (uint32_t)(cols * 8))};
+  }
+  __device__ __forceinline__ State start(const Tile& t, int c) const {   // no eligible row yet
+    return State{__builtin_nanf(""), __builtin_amdgcn_raw_buffer_load_b64(t.mrsrc, (uint32_t)c * 8u, 0, 0)};
+  }
+  __device__ __forceinline__ Rows rows(const Tile& t, int r) const {
+    return Rows{{__builtin_amdgcn_raw_buffer_load_b128(t.trsrc, (uint32_t)r * 8u, 0, 0),
+                 __builtin_amdgcn_raw_buffer_load_b128(t.trsrc, (uint32_t)r * 8u + 16u, 0, 0)}};
+  }
+  __device__ __forceinline__ void visit(State& s, const Col&, const Rows& rw, int j, float key, bool ok) const {
+    // (a row past G reads tag 0 through the descriptor as well)
+    const unsigned tlo = ok ? rw.tg[j >> 1][2 * (j & 1)] : 0u, thi = ok ? rw.tg[j >> 1][2 * (j & 1) + 1] : 0u;
+    const bool elig = ((tlo & s.msk[0]) | (thi & s.msk[1])) != 0u;   // false for a row past G (tag 0)
+    const float with = (key != key) ? -__builtin_inff() : fminf(s.mn, key);   // fminf(NaN, key) = key
+    s.mn = elig ? with : s.mn;
+  }
+  __device__ __forceinline__ Meet partial(const State& s) const { return s.mn; }
+  __device__ static __forceinline__ Meet combine(Meet a, Meet b) { return fminf(a, b); }
+  __device__ __forceinline__ void store(int64_t i, Meet v) const {
+    words[i] = (v != v) ? __builtin_nanf("") : v;             // one bit pattern for "nothing here"
+  }
+};
+
+// Tagged = false takes no tags: the two pointers are unused there.
 template <class T, bool Tagged>
 __global__ __launch_bounds__(T::NT, 2) void topk_tilemin_kernel(const float* __restrict__ gallery, int64_t G,
                                                               const float* __restrict__ probes, int B, int D,
-                                                              const float* __restrict__ aux, int metric,
-                                                              float* __restrict__ words, int nparts,
+                                                              const float* __restrict__ aux, int metric, int nparts,
+                                                              float* __restrict__ words,
                                                               const int64_t* __restrict__ row_tags,
                                                               const int64_t* __restrict__ probe_masks) {
-  constexpr int WM = T::WM, WN = T::WN;
-  static_assert(T::BM == WITHIN_BM, "one word per 128 gallery rows");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  // block -> (gallery part, probe block) as within_census_kernel
-  const int cblocks = (B + T::BN - 1) / T::BN;
-  const int grp = (int)blockIdx.x / (8 * cblocks), rem = (int)blockIdx.x % (8 * cblocks);
-  const int part = grp * 8 + (rem & 7), cblk = rem >> 3;
-  if (part >= nparts) return;
-  float* s_min = smem + T::LDS_FLOATS;                         // [WGM][BN]: the minimum per wave row
-  const int tid = threadIdx.x;
-  const int wc = T::wave_col();
-  const int p0 = cblk * T::BN;
-  const int ksteps = D / BK;
-  const int64_t gtiles = (G + T::BM - 1) / T::BM;
-  const float inf = __builtin_inff();
-
-  int col[WN];
-#pragma unroll
-  for (int n = 0; n < WN; ++n) col[n] = (wc * WN + n) * 32 + (tid & 31);
-
-  for (int64_t gt = part; gt < gtiles; gt += nparts) {
-    const int64_t g0 = gt * T::BM;
-    f32x16 acc[WM][WN];
-    zero_acc<T>(acc);
-    RowLoader<T::NA, T::RP> al(gallery + g0 * D, G - g0, D);
-    RowLoader<T::NB, T::RP> bl(probes + (int64_t)p0 * D, (int64_t)B - p0, D);
-    gemm_mainloop<T>(al, bl, 0, ksteps, smem, acc);
-
-    // dots -> keys -> one minimum per probe column.  aux[g] = -1/|g| (metric 1) or |g|^2 (metric 0), NaN for the rows kept
-    // out of the filter: fminf drops a NaN, so a NaN key is tested for and makes the minimum -inf.
-    int lane = tid & 63;
-    asm volatile("" : "+v"(lane));                           // opaque per tile, as in within_census_kernel
-    const int wr = T::wave_row();
-    const int64_t rows_left = G - g0;
-    const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(aux + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 4));
-    float mn[WN];
-    if constexpr (!Tagged) {
-#pragma unroll
-      for (int n = 0; n < WN; ++n) mn[n] = inf;
-#pragma unroll
-      for (int m = 0; m < WM; ++m) {
-        const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {                        // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
-          const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const bool ok = rbase + 8 * q + j < rows_left;
-#pragma unroll
-            for (int n = 0; n < WN; ++n) {
-              const float dot = acc[m][n][4 * q + j];
-              float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
-              key = ok ? key : inf;                           // a row past G
-              mn[n] = (key != key) ? -inf : fminf(mn[n], key);  // (once -inf it stays -inf)
-            }
-          }
-        }
-      }
-    } else {
-      const int64_t cols_left = (int64_t)B - p0;
-      const __amdgpu_buffer_rsrc_t trsrc = make_rsrc(row_tags + g0, (uint32_t)((rows_left < T::BM ? rows_left : T::BM) * 8));
-      const __amdgpu_buffer_rsrc_t mrsrc = make_rsrc(probe_masks + p0, (uint32_t)((cols_left < T::BN ? cols_left : T::BN) * 8));
-      u32x2 msk[WN];                                          // the masks of this thread's probe columns, once per tile
-#pragma unroll
-      for (int n = 0; n < WN; ++n) {
-        msk[n] = __builtin_amdgcn_raw_buffer_load_b64(mrsrc, (uint32_t)col[n] * 8u, 0, 0);
-        mn[n] = __builtin_nanf("");                           // no eligible row yet
-      }
-#pragma unroll
-      for (int m = 0; m < WM; ++m) {
-        const int rbase = (wr * WM + m) * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {                        // rows rbase + 8q .. +3 <-> registers 4q .. 4q+3
-          const f32x4 ax = buf_load4(arsrc, (uint32_t)(rbase + 8 * q) * 4u);
-          u32x4 tg[2];                                        // their four tags, {lo, hi} each
-          tg[0] = __builtin_amdgcn_raw_buffer_load_b128(trsrc, (uint32_t)(rbase + 8 * q) * 8u, 0, 0);
-          tg[1] = __builtin_amdgcn_raw_buffer_load_b128(trsrc, (uint32_t)(rbase + 8 * q) * 8u + 16u, 0, 0);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const bool ok = rbase + 8 * q + j < rows_left;    // (a row past G reads tag 0 through the descriptor as well)
-            const unsigned tlo = ok ? tg[j >> 1][2 * (j & 1)] : 0u, thi = ok ? tg[j >> 1][2 * (j & 1) + 1] : 0u;
-#pragma unroll
-            for (int n = 0; n < WN; ++n) {
-              const float dot = acc[m][n][4 * q + j];
-              const float key = (metric == 1) ? dot * ax[j] : fmaf(-2.f, dot, ax[j]);
-              const bool elig = ((tlo & msk[n][0]) | (thi & msk[n][1])) != 0u;   // false for a row past G (tag 0)
-              const float with = (key != key) ? -inf : fminf(mn[n], key);     // fminf(NaN, key) = key
-              mn[n] = elig ? with : mn[n];
-            }
-          }
-        }
-      }
-    }
-    // lanes l and l + 32 hold different rows of the same probe column; the WGM waves stacked on M meet in LDS
-#pragma unroll
-    for (int n = 0; n < WN; ++n) {
-      const float v = fminf(mn[n], __shfl_xor(mn[n], 32));
-      if (lane < 32) s_min[wr * T::BN + col[n]] = v;
-    }
-    lds_barrier();
-    for (int c = tid; c < T::BN; c += T::NT) {
-      float v = s_min[c];
-#pragma unroll
-      for (int w = 1; w < T::WGM; ++w) v = fminf(v, s_min[w * T::BN + c]);
-      if constexpr (Tagged) v = (v != v) ? __builtin_nanf("") : v;   // one bit pattern for "nothing here"
-      if (p0 + c < B) words[gt * B + p0 + c] = v;
-    }
-    // (s_min is written again only after the next tile's main loop, i.e. behind several barriers)
-  }
+  if constexpr (Tagged) key_tiles<T>(gallery, G, probes, B, D, aux, metric, nparts, TaggedTileMinEpi(words, row_tags, probe_masks));
+  else key_tiles<T>(gallery, G, probes, B, D, aux, metric, nparts, TileMinEpi(words));
 }
 
 // One block per probe; `words` rows are B floats apart.  All control flow is block-uniform: every thread derives kappa, t and
@@ -704,52 +614,8 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const fl
   if (tid < 2 * TOPK_MAX) s_list[tid] = TOPK_NONE;
   __syncthreads();
 
-  // ---- seed: kappa = the seed-th smallest word, one byte of its integer image per pass (exact counts: deterministic)
-  unsigned kappa = ~0u;                                       // no more than `seed` tiles: all of them
-  if ((int64_t)seed < gtiles) {
-    unsigned prefix = 0, need = (unsigned)seed;               // the need-th smallest among the words that start with prefix
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (tid < 256) s_hist[tid] = 0;
-      __syncthreads();
-      for (int64_t t = tid; t < gtiles; t += NT) {
-        const unsigned o = ord_f32(words[t * B + p]);
-        if ((unsigned)((unsigned long long)o >> (shift + 8)) == prefix) atomicAdd(&s_hist[(o >> shift) & 255u], 1u);
-      }
-      __syncthreads();
-      if (wave == 0) {                                        // four bins per lane, a scan over the lanes
-        unsigned c[4], sum = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          c[i] = s_hist[4 * lane + i];
-          sum += c[i];
-        }
-        unsigned incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const unsigned v = __shfl_up(incl, o);
-          if (lane >= o) incl += v;
-        }
-        const unsigned excl = incl - sum;
-        if (excl < need && need <= incl) {                    // exactly one lane: 1 <= need <= the total
-          unsigned r = need - excl;
-          int d = 0;
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-            if (d == i && r > c[i]) {
-              r -= c[i];
-              d = i + 1;
-            }
-          s_sel[0] = (unsigned)(4 * lane + d);
-          s_sel[1] = r;
-        }
-      }
-      __syncthreads();
-      prefix = (prefix << 8) | s_sel[0];
-      need = s_sel[1];
-      // (s_sel is written again only behind the two barriers of the next pass)
-    }
-    kappa = prefix;
-  }
+  // ---- seed: kappa = the seed-th smallest word; no more than `seed` tiles: all of them
+  const unsigned kappa = (int64_t)seed < gtiles ? topk_kappa(words, B, p, gtiles, (unsigned)seed, s_hist, s_sel) : ~0u;
 
   unsigned ntiles = 0;                                        // Tagged: tiles this block evaluated row by row
   if (gtiles > 0) {
@@ -832,25 +698,22 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_select_kernel(const fl
   }
 }
 
-template <class T, bool Tagged = false>
-static int launch_tilemin(const Gallery* g, const float* probes, int B, int metric, hipStream_t st,
-                          const int64_t* row_tags = nullptr, const int64_t* probe_masks = nullptr) {
-  auto kern = topk_tilemin_kernel<T, Tagged>;
-  constexpr int lds = T::LDS_BYTES + T::WGM * T::BN * 4;
-  static bool done[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!done[dev]) {
-    DIF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    done[dev] = true;
-  }
-  const int nparts = match_plan_parts(g, B, false);
-  const int cblocks = (B + T::BN - 1) / T::BN;
-  dim3 grid((unsigned)(((nparts + 7) / 8) * 8 * cblocks));  // groups of 8 parts x all probe blocks (see match_tile_kernel)
-  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds, st, g->rows, g->n, probes, B, g->d, metric == 1 ? g->ninv : g->sq, metric,
-                     g->topk_min, nparts, row_tags, probe_masks);
-  DIF_HIP(hipGetLastError());
-  return 0;
+// What the four top-k entries share on the host.  The rounds, and the tile words' workspace for one of them:
+static int topk_plan(Gallery* g, int B, int64_t gtiles, hipStream_t st, Rounds* rounds) {
+  *rounds = plan_rounds(gtiles, B, TOPK_MIN_MAX, g->topk_round, 128);
+  return ensure(st, workspace(&g->topk_min, &g->topk_min_cap, (size_t)gtiles * (size_t)rounds->per, sizeof(float)));
+}
+// ... and the tile words of nb probes into g->topk_min; row_tags given: the tagged form, probe_masks being these probes'
+static int tilemin_pass(const Gallery* g, const float* pr, int nb, int metric, hipStream_t st, const int64_t* row_tags,
+                        const int64_t* probe_masks) {
+  const int nparts = key_tiles_parts(g, nb);
+  return with_census_tile(nb, [&](auto tile) {
+    using T = decltype(tile);
+    return row_tags ? launch_key_tiles<topk_tilemin_kernel<T, true>, T>(g, pr, nb, metric, st, key_tiles_lds<T>, -1, nparts, g->topk_min,
+                                                                        row_tags, probe_masks)
+                    : launch_key_tiles<topk_tilemin_kernel<T, false>, T>(g, pr, nb, metric, st, key_tiles_lds<T>, -1, nparts, g->topk_min,
+                                                                         row_tags, probe_masks);
+  });
 }
 
 // the counter of "topk_tagged_tiles", zeroed on the stream by every tagged call
@@ -871,37 +734,24 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
   const int clamp = g->clamp_nan ? 1 : 0;
   const int seed = g->topk_seed > 0 ? g->topk_seed : k;
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
-  // probes per round: whole 128-probe blocks whose tile words stay below TOPK_MIN_MAX (an empty gallery has none: one round)
-  int64_t per = gtiles > 0 ? (int64_t)(TOPK_MIN_MAX / (size_t)gtiles) / 128 * 128 : B;
-  if (g->topk_round > 0 && g->topk_round < per) per = g->topk_round;
-  if (per < 128) per = 128;
-  if (per > B) per = B;
-  const size_t need = (size_t)gtiles * (size_t)per;
-  if (need > g->topk_min_cap) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read it
-    if (grow(&g->topk_min, &g->topk_min_cap, need, sizeof(float))) return -1;
-  }
+  Rounds rounds;
+  if (topk_plan(g, B, gtiles, st, &rounds)) return -1;
   const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int nb = (int)(B - b0 < per ? B - b0 : per);
+  return for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
-    if (gtiles > 0) {
-      const int rc = tagged ? with_census_tile(nb, [&](auto tile) {
-        return launch_tilemin<decltype(tile), true>(g, pr, nb, metric, st, row_tags, probe_masks + b0);
-      }) : with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
-      if (rc) return rc;
-    }
+    const int64_t* pm = tagged ? probe_masks + b0 : nullptr;
+    if (gtiles > 0 && tilemin_pass(g, pr, nb, metric, st, row_tags, pm)) return -1;
     if (tagged)
       hipLaunchKernelGGL((topk_select_kernel<true, TopkTags>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows,
                          g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k,
-                         dist_out + b0 * k, TopkTags{row_tags, probe_masks + b0, g->topk_tagged_stat});
+                         dist_out + b0 * k, TopkTags{row_tags, pm, g->topk_tagged_stat});
     else
       hipLaunchKernelGGL((topk_select_kernel<false>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr, g->rows,
                          g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, idx_out + b0 * k,
                          dist_out + b0 * k);
     DIF_HIP(hipGetLastError());
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -932,56 +782,6 @@ int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t*
 // which only tightens the pre-filter "candidate < k-th kept word", never thr_out.  The seed schedule decides how tight t is,
 // never the answer.
 constexpr long long TOPK_NOLABEL = -1;                        // the label of an empty slot: no usable row carries it
-
-// the integer image of the need-th smallest word of probe p (1 <= need <= gtiles): topk_select_kernel's radix select, one byte
-// per pass, as a function -- that kernel is left as it is
-__device__ __forceinline__ unsigned topk_ids_kappa(const float* __restrict__ words, int B, int p, int64_t gtiles,
-                                                   unsigned need, unsigned* s_hist, unsigned* s_sel) {
-  constexpr int NT = 64 * WITHIN_NW;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  unsigned prefix = 0;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (tid < 256) s_hist[tid] = 0;
-    __syncthreads();
-    for (int64_t t = tid; t < gtiles; t += NT) {
-      const unsigned o = ord_f32(words[t * B + p]);
-      if ((unsigned)((unsigned long long)o >> (shift + 8)) == prefix) atomicAdd(&s_hist[(o >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (wave == 0) {                                          // four bins per lane, a scan over the lanes
-      unsigned c[4], sum = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        c[i] = s_hist[4 * lane + i];
-        sum += c[i];
-      }
-      unsigned incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-      }
-      const unsigned excl = incl - sum;
-      if (excl < need && need <= incl) {                      // exactly one lane: 1 <= need <= the total
-        unsigned r = need - excl;
-        int d = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          if (d == i && r > c[i]) {
-            r -= c[i];
-            d = i + 1;
-          }
-        s_sel[0] = (unsigned)(4 * lane + d);
-        s_sel[1] = r;
-      }
-    }
-    __syncthreads();
-    prefix = (prefix << 8) | s_sel[0];
-    need = s_sel[1];
-    // (s_sel is written again only behind the two barriers of the next pass, or of the next call)
-  }
-  return prefix;
-}
 
 // One block per probe, block-uniform control flow, as topk_select_kernel.  `tiles_stat` counts the (probe, tile) evaluations.
 // Tagged as topk_select_kernel<true>: a NaN word is never selected nor counted among the tiles left, an ineligible row is
@@ -1114,7 +914,7 @@ __global__ __launch_bounds__(64 * WITHIN_NW, 4) void topk_ids_select_kernel(
     bool sweep = false;
 #pragma unroll 1
     for (;;) {                                                // the seed passes, then the sweep: one call site of `pass`
-      if (!sweep) kappa = (int64_t)sd < gtiles ? topk_ids_kappa(words, B, p, gtiles, (unsigned)sd, s_hist, s_sel) : ~0u;
+      if (!sweep) kappa = (int64_t)sd < gtiles ? topk_kappa(words, B, p, gtiles, (unsigned)sd, s_hist, s_sel) : ~0u;
       pass(sweep);
       if (sweep || kappa == ~0u) break;                       // ~0u: every tile is evaluated (no word has a NaN's image)
       const unsigned long long kth = s_list[k - 1];
@@ -1165,42 +965,29 @@ int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, cons
   const int clamp = g->clamp_nan ? 1 : 0;
   const int seed = g->topk_seed > 0 ? g->topk_seed : k;
   const int64_t gtiles = (g->n + WITHIN_BM - 1) / WITHIN_BM;
-  // the rounds and the words are topk_run's
-  int64_t per = gtiles > 0 ? (int64_t)(TOPK_MIN_MAX / (size_t)gtiles) / 128 * 128 : B;
-  if (g->topk_round > 0 && g->topk_round < per) per = g->topk_round;
-  if (per < 128) per = 128;
-  if (per > B) per = B;
-  const size_t need = (size_t)gtiles * (size_t)per;
-  if (need > g->topk_min_cap) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read it
-    if (grow(&g->topk_min, &g->topk_min_cap, need, sizeof(float))) return -1;
-  }
+  Rounds rounds;
+  if (topk_plan(g, B, gtiles, st, &rounds)) return -1;
   if (!g->topk_ids_stat) DIF_HIP(hipMalloc(&g->topk_ids_stat, sizeof(unsigned long long)));
   DIF_HIP(hipMemsetAsync(g->topk_ids_stat, 0, sizeof(unsigned long long), st));
   const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int nb = (int)(B - b0 < per ? B - b0 : per);
+  return for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
-    if (gtiles > 0) {
-      const int rc = tagged ? with_census_tile(nb, [&](auto tile) {
-        return launch_tilemin<decltype(tile), true>(g, pr, nb, metric, st, row_tags, probe_masks + b0);
-      }) : with_census_tile(nb, [&](auto tile) { return launch_tilemin<decltype(tile)>(g, pr, nb, metric, st); });
-      if (rc) return rc;
-    }
+    const int64_t* pm = tagged ? probe_masks + b0 : nullptr;
+    if (gtiles > 0 && tilemin_pass(g, pr, nb, metric, st, row_tags, pm)) return -1;
     if (tagged)
       hipLaunchKernelGGL((topk_ids_select_kernel<true, TopkTags>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr,
                          g->rows, g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, row_labels,
                          exclude ? exclude + b0 : nullptr, idx_out + b0 * k, dist_out + b0 * k,
                          label_out ? label_out + b0 * k : nullptr, g->topk_ids_stat,
-                         TopkTags{row_tags, probe_masks + b0, g->topk_tagged_stat});
+                         TopkTags{row_tags, pm, g->topk_tagged_stat});
     else
       hipLaunchKernelGGL((topk_ids_select_kernel<false>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->topk_min, g->n, nb, pr,
                          g->rows, g->d, metric, cdot, g->sqmax_bits, clamp, plan, k, seed, g->index_base, row_labels,
                          exclude ? exclude + b0 : nullptr, idx_out + b0 * k, dist_out + b0 * k,
                          label_out ? label_out + b0 * k : nullptr, g->topk_ids_stat);
     DIF_HIP(hipGetLastError());
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1284,40 +1071,43 @@ __global__ __launch_bounds__(256) void cluster_init_kernel(int* __restrict__ par
   parent[i] = (int)v;
 }
 
-// One block per probe i = p0 + blockIdx.x; `census` rows are B words apart and cover tiles 0 .. (p0 + B - 1) / 128.  Which
-// tiles are evaluated is block-uniform (the same LDS words); a wave owns the rows it evaluates.
+// The walk of the self-join (cluster, DBSCAN): probe i's census words in ascending tile order up to i's own tile; every tile
+// with a sure or a borderline row -- a census word holds counts, not row numbers -- (every tile for a probe outside the bound's
+// validity) is evaluated row by row, a wave per row j < i, and lane 0 of that wave calls edge(j, d) where d <= t.
+// Block-uniform control flow; a wave owns its rows.
+template <class F>
+__device__ __forceinline__ void edge_walk(const unsigned short* __restrict__ census, int B, const f32x4* __restrict__ thr,
+                                          const float* __restrict__ gallery, int64_t i, int D, int metric, float t, int clamp,
+                                          const SumPlan& plan, float (*scratch)[NP_SCRATCH], unsigned short* s_word, F&& edge) {
+  const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* q = gallery + i * D;
+  const bool all = thr[p][3] != 0.f;
+  auto sel = [&](unsigned short w) { return all || w != 0; };
+  walk_words(census, B, p, i / WITHIN_BM + 1, s_word, sel, [&](int64_t tl, unsigned short w) {
+    if (!sel(w)) return;
+    const int64_t g0 = tl * WITHIN_BM;
+    const int rows = i - g0 < WITHIN_BM ? (int)(i - g0) : WITHIN_BM;   // rows j < i only: no self pair
+    for (int r = wave; r < rows; r += WITHIN_NW) {
+      float d;
+      (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
+      if (lane == 0 && d <= t) edge((int)(g0 + r), d);        // NaN: not an edge
+    }
+  });
+}
+
+// One block per probe i = p0 + blockIdx.x; `census` rows are B words apart and cover tiles 0 .. (p0 + B - 1) / 128.
 __global__ __launch_bounds__(64 * WITHIN_NW) void cluster_resolve_kernel(const unsigned short* __restrict__ census, int B,
                                                                        const f32x4* __restrict__ thr,
                                                                        const float* __restrict__ gallery, int64_t p0,
                                                                        int64_t first_row, int D, int metric, float t,
                                                                        int clamp, const SumPlan plan,
                                                                        int* __restrict__ parent) {
-  constexpr int NT = 64 * WITHIN_NW;
   __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
-  __shared__ unsigned short s_word[NT];
-  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t i = p0 + p;
+  __shared__ unsigned short s_word[64 * WITHIN_NW];
+  const int64_t i = p0 + blockIdx.x;
   if (i < first_row) return;                                  // (block-uniform) a row the earlier labels already cover
-  const float* q = gallery + i * D;
-  const int64_t gtiles = i / WITHIN_BM + 1;                   // up to the probe's own tile
-  const bool all = thr[p][3] != 0.f;
-  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
-    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
-    s_word[tid] = w;
-    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
-    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
-    for (int j = 0; j < nw; ++j) {
-      if (!(all || s_word[j] != 0)) continue;
-      const int64_t g0 = (t0 + j) * WITHIN_BM;
-      const int rows = i - g0 < WITHIN_BM ? (int)(i - g0) : WITHIN_BM;   // rows j < i only
-      for (int r = wave; r < rows; r += WITHIN_NW) {
-        float d;
-        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
-        if (lane == 0 && d <= t) cl_unite(parent, (int)i, (int)(g0 + r));   // NaN: not an edge
-      }
-    }
-    __syncthreads();                                          // s_word is rewritten by the next round
-  }
+  edge_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word,
+            [&](int j, float) { cl_unite(parent, (int)i, j); });
 }
 
 __global__ __launch_bounds__(256) void cluster_flatten_kernel(int* __restrict__ parent, int64_t G, int64_t index_base,
@@ -1338,6 +1128,31 @@ __global__ __launch_bounds__(256) void cluster_flatten_kernel(int* __restrict__ 
   }
 }
 
+// Rows per round of the self-join ("cluster_round"; dif_gallery_cluster and dif_gallery_dbscan): at most what the census cap
+// allows.  A round's census covers rows [0, its last probe], so R equal rounds do (R + 1) / 2R of the square's MFMA work: one
+// round would do all of it.  The default is a sixteenth of the rows (17 / 32 of the square), never below 2048 probes (a
+// launch that fills the chip).  ... and the census workspace for one such round, grown in one `ensure` with whatever else the
+// caller needs (`more`)
+template <class... W>
+static int selfjoin_plan(Gallery* g, int64_t gtiles, hipStream_t st, Rounds* rounds, W... more) {
+  int64_t want = g->cluster_round;
+  if (want <= 0) {
+    want = ((g->n + 15) / 16 + 127) / 128 * 128;
+    if (want < 2048) want = 2048;
+  }
+  *rounds = plan_rounds(gtiles, g->n, WITHIN_CENSUS_MAX, want, 1);
+  return ensure(st, workspace(&g->within_census, &g->within_census_cap, (size_t)gtiles * (size_t)rounds->per, sizeof(unsigned short)),
+                workspace(&g->within_thr, &g->within_thr_cap, (size_t)rounds->per, 4 * sizeof(float)), more...);
+}
+// the thresholds and the census of one round [b0, b0 + nb): the triangle -- no probe of the round looks past its last row
+static int selfjoin_census(Gallery* g, int64_t b0, int nb, int metric, float tolerance, hipStream_t st) {
+  const float* pr = g->rows + b0 * g->d;
+  hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, g->d * U24,
+                     g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));   // (g->d * U24: the f32 MFMA, a D-term fma chain)
+  DIF_HIP(hipGetLastError());
+  return census_pass(g, pr, nb, metric, st, b0 + nb);
+}
+
 int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, const int64_t* labels_in, int64_t* labels_out,
                 int64_t* n_clusters, hipStream_t st) {
   const int64_t n = g->n;
@@ -1348,46 +1163,25 @@ int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, cons
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
-  const int64_t gtiles = (n + WITHIN_BM - 1) / WITHIN_BM;
-  // probes per round: at most what the census cap allows, as in within_run.  A round's census covers rows [0, its last probe],
-  // so R equal rounds do (R + 1) / 2R of the square's MFMA work: one round would do all of it.  The default is a sixteenth of
-  // the rows (17 / 32 of the square), never below 2048 probes (a launch that fills the chip), or the "cluster_round" option
-  int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
-  if (per < 128) per = 128;
-  int64_t want = g->cluster_round;
-  if (want <= 0) {
-    want = ((n + 15) / 16 + 127) / 128 * 128;
-    if (want < 2048) want = 2048;
-  }
-  if (want < per) per = want;
-  const size_t need_t = (size_t)(per < n ? per : n), need_c = (size_t)gtiles * need_t;
-  if (need_c > g->within_census_cap || need_t > g->within_thr_cap || (size_t)n > g->cluster_parent_cap || !g->cluster_bad) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
-    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
-    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
-    if (grow(&g->cluster_parent, &g->cluster_parent_cap, (size_t)n, sizeof(int))) return -1;
-    if (!g->cluster_bad) DIF_HIP(hipMalloc(&g->cluster_bad, sizeof(int)));
-  }
+  Rounds rounds;
+  if (selfjoin_plan(g, (n + WITHIN_BM - 1) / WITHIN_BM, st, &rounds,
+                    workspace(&g->cluster_parent, &g->cluster_parent_cap, (size_t)n, sizeof(int))))
+    return -1;
+  if (!g->cluster_bad) DIF_HIP(hipMalloc(&g->cluster_bad, sizeof(int)));
   DIF_HIP(hipMemsetAsync(g->cluster_bad, 0, sizeof(int), st));
   const unsigned nblk = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(cluster_init_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, n, first_row, labels_in,
                      g->index_base, g->cluster_bad, n_clusters);
   DIF_HIP(hipGetLastError());
-  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
-  for (int64_t b0 = first_row / 128 * 128; b0 < n && first_row < n; b0 += per) {
-    const int nb = (int)(n - b0 < per ? n - b0 : per);
-    const float* pr = g->rows + b0 * g->d;
-    hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
-                       g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
-    DIF_HIP(hipGetLastError());
-    const int64_t limit = b0 + nb;                            // the triangle: no probe of this round looks past its last row
-    const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st, limit); });
-    if (rc) return rc;
+  const int rc = for_rounds(rounds, first_row / 128 * 128, first_row < n ? n : 0, [&](int64_t b0, int nb) {
+    if (selfjoin_census(g, b0, nb, metric, tolerance, st)) return -1;
     hipLaunchKernelGGL(cluster_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, nb,
                        reinterpret_cast<const f32x4*>(g->within_thr), g->rows, b0, first_row, g->d, metric, tolerance, clamp,
                        plan, g->cluster_parent);
     DIF_HIP(hipGetLastError());
-  }
+    return 0;
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(cluster_flatten_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, n, g->index_base, g->cluster_bad,
                      labels_out, n_clusters);
   DIF_HIP(hipGetLastError());
@@ -1401,7 +1195,7 @@ int cluster_run(Gallery* g, int metric, float tolerance, int64_t first_row, cons
 //   clusters  = connected components of (core rows, edges of E between two core rows);  label = index_base + smallest row
 //   a non-core row with a core neighbour takes the label of the NEAREST one (the edge's float32 value, ties to the lower row)
 //   every other row is noise: label -1
-// Two sweeps of the lower triangle with cluster_run's round loop; every edge is seen exactly once per sweep, by its probe i:
+// Two sweeps of the lower triangle in cluster_run's rounds; every edge is seen exactly once per sweep, by its probe i:
 //   dbscan_init_kernel     parent[i] = i, degree[i] = 1, anchor[i] = ~0, counts = {0, 0}
 //   degree sweep, per round: within_prep_kernel, within_census_kernel (both unchanged), dbscan_degree_kernel: the walk of
 //                          cluster_resolve_kernel; an edge adds 1 to degree[i] (summed per wave first) and to degree[j]
@@ -1435,38 +1229,6 @@ __global__ __launch_bounds__(256) void dbscan_init_kernel(int* __restrict__ pare
   anchor[i] = DBSCAN_NONE;
 }
 
-// The walk of cluster_resolve_kernel: probe i's census words in ascending tile order up to i's own tile; every tile with a
-// sure or a borderline row (every tile for a probe outside the bound's validity) is evaluated row by row, a wave per row
-// j < i, and lane 0 of that wave calls edge(j, d) where d <= t.  Block-uniform control flow; a wave owns its rows.
-template <class F>
-__device__ __forceinline__ void dbscan_walk(const unsigned short* __restrict__ census, int B, const f32x4* __restrict__ thr,
-                                            const float* __restrict__ gallery, int64_t i, int D, int metric, float t,
-                                            int clamp, const SumPlan& plan, float (*scratch)[NP_SCRATCH],
-                                            unsigned short* s_word, F&& edge) {
-  constexpr int NT = 64 * WITHIN_NW;
-  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const float* q = gallery + i * D;
-  const int64_t gtiles = i / WITHIN_BM + 1;                   // up to the probe's own tile
-  const bool all = thr[p][3] != 0.f;
-  for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
-    const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
-    s_word[tid] = w;
-    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
-    const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
-    for (int j = 0; j < nw; ++j) {
-      if (!(all || s_word[j] != 0)) continue;
-      const int64_t g0 = (t0 + j) * WITHIN_BM;
-      const int rows = i - g0 < WITHIN_BM ? (int)(i - g0) : WITHIN_BM;   // rows j < i only: no self pair
-      for (int r = wave; r < rows; r += WITHIN_NW) {
-        float d;
-        (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
-        if (lane == 0 && d <= t) edge((int)(g0 + r), d);      // NaN: not an edge
-      }
-    }
-    __syncthreads();                                          // s_word is rewritten by the next round
-  }
-}
-
 // One block per probe i = p0 + blockIdx.x; `census` rows are B words apart and cover tiles 0 .. (p0 + B - 1) / 128.
 __global__ __launch_bounds__(64 * WITHIN_NW) void dbscan_degree_kernel(const unsigned short* __restrict__ census, int B,
                                                                      const f32x4* __restrict__ thr,
@@ -1477,7 +1239,7 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void dbscan_degree_kernel(const uns
   __shared__ unsigned short s_word[64 * WITHIN_NW];
   const int64_t i = p0 + blockIdx.x;
   int mine = 0;                                               // lane 0: edges this wave found for probe i
-  dbscan_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word, [&](int j, float) {
+  edge_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word, [&](int j, float) {
     ++mine;
     atomicAdd(degree + j, 1);                                 // integer: order-free
   });
@@ -1496,7 +1258,7 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void dbscan_link_kernel(const unsig
   const int64_t i = p0 + blockIdx.x;
   const bool core_i = degree[i] >= min_samples;               // (final: the degree sweep ended before this kernel began)
   unsigned long long best = DBSCAN_NONE;                      // lane 0: the nearest core row this wave found for a non-core i
-  dbscan_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word, [&](int j, float d) {
+  edge_walk(census, B, thr, gallery, i, D, metric, t, clamp, plan, scratch, s_word, [&](int j, float d) {
     const bool core_j = degree[j] >= min_samples;
     const unsigned long long hi = (unsigned long long)__builtin_bit_cast(unsigned, d) << 32;   // d >= +0: ordered like d
     if (core_i && core_j) {
@@ -1550,44 +1312,21 @@ int dbscan_run(Gallery* g, int metric, float tolerance, int min_samples, int64_t
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
-  const int64_t gtiles = (n + WITHIN_BM - 1) / WITHIN_BM;
-  // probes per round: cluster_run's rule ("cluster_round")
-  int64_t per = (int64_t)(WITHIN_CENSUS_MAX / (size_t)gtiles) / 128 * 128;
-  if (per < 128) per = 128;
-  int64_t want = g->cluster_round;
-  if (want <= 0) {
-    want = ((n + 15) / 16 + 127) / 128 * 128;
-    if (want < 2048) want = 2048;
-  }
-  if (want < per) per = want;
-  const size_t need_t = (size_t)(per < n ? per : n), need_c = (size_t)gtiles * need_t;
-  if (need_c > g->within_census_cap || need_t > g->within_thr_cap || (size_t)n > g->cluster_parent_cap ||
-      (size_t)n > g->dbscan_degree_cap || (size_t)n > g->dbscan_anchor_cap) {
-    DIF_HIP(hipStreamSynchronize(st));                       // an earlier call on this stream may still read them
-    if (grow(&g->within_census, &g->within_census_cap, need_c, sizeof(unsigned short))) return -1;
-    if (grow(&g->within_thr, &g->within_thr_cap, need_t, 4 * sizeof(float))) return -1;
-    if (grow(&g->cluster_parent, &g->cluster_parent_cap, (size_t)n, sizeof(int))) return -1;
-    if (grow(&g->dbscan_degree, &g->dbscan_degree_cap, (size_t)n, sizeof(int))) return -1;
-    if (grow(&g->dbscan_anchor, &g->dbscan_anchor_cap, (size_t)n, sizeof(unsigned long long))) return -1;
-  }
+  Rounds rounds;
+  if (selfjoin_plan(g, (n + WITHIN_BM - 1) / WITHIN_BM, st, &rounds,
+                    workspace(&g->cluster_parent, &g->cluster_parent_cap, (size_t)n, sizeof(int)),
+                    workspace(&g->dbscan_degree, &g->dbscan_degree_cap, (size_t)n, sizeof(int)),
+                    workspace(&g->dbscan_anchor, &g->dbscan_anchor_cap, (size_t)n, sizeof(unsigned long long))))
+    return -1;
   const unsigned nblk = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(dbscan_init_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, g->dbscan_degree, g->dbscan_anchor, n,
                      counts);
   DIF_HIP(hipGetLastError());
-  const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
-  const bool one_round = per >= n;
+  const bool one_round = rounds.per >= n;
   for (int link = 0; link < 2; ++link) {
-    for (int64_t b0 = 0; b0 < n; b0 += per) {
-      const int nb = (int)(n - b0 < per ? n - b0 : per);
-      const float* pr = g->rows + b0 * g->d;
-      if (!(link && one_round)) {                             // one round: the degree sweep's census is the link sweep's
-        hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
-                           g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
-        DIF_HIP(hipGetLastError());
-        const int64_t limit = b0 + nb;                        // the triangle: no probe of this round looks past its last row
-        const int rc = with_census_tile(nb, [&](auto tile) { return launch_census<decltype(tile)>(g, pr, nb, metric, st, limit); });
-        if (rc) return rc;
-      }
+    const int rc = for_rounds(rounds, 0, n, [&](int64_t b0, int nb) {
+      // (one round: the degree sweep's census is the link sweep's)
+      if (!(link && one_round) && selfjoin_census(g, b0, nb, metric, tolerance, st)) return -1;
       if (!link) {
         hipLaunchKernelGGL(dbscan_degree_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, nb,
                            reinterpret_cast<const f32x4*>(g->within_thr), g->rows, b0, g->d, metric, tolerance, clamp, plan,
@@ -1598,7 +1337,9 @@ int dbscan_run(Gallery* g, int metric, float tolerance, int min_samples, int64_t
                            min_samples, g->dbscan_degree, g->cluster_parent, g->dbscan_anchor);
       }
       DIF_HIP(hipGetLastError());
-    }
+      return 0;
+    });
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(dbscan_flatten_kernel, dim3(nblk), dim3(256), 0, st, g->cluster_parent, g->dbscan_degree, g->dbscan_anchor,
                      n, min_samples, g->index_base, labels_out, degree_out, counts);

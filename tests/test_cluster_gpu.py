@@ -185,19 +185,23 @@ def test_cluster_degenerate_rows(cuda, metric, clamp):
 
 
 # ------------------------------------------------------------------------------------------- 4
-def test_cluster_incremental_and_index_base(cuda):
+@pytest.mark.parametrize('G0,G1,per', [(257, 387, 0), (130, 300, 128)])
+def test_cluster_incremental_and_index_base(cuda, G0, G1, per):
     """set 257 rows, cluster, update with 130 more, cluster(first_row=257, labels=prev) == the full call on 387 rows; the
-    same with first_row = G (labels copied) and 0; labels and labels_in shifted by index_base; a bad labels_in entry."""
+    same with first_row = G (labels copied) and 0; labels and labels_in shifted by index_base; a bad labels_in entry.
+    (130, 300) with "cluster_round" 128: first_row lies inside the first round's probe block -- the blocks of rows 128 and
+    129 return before the walk -- and a second round, [256, 300), follows."""
     from deep_insight_face import oneshot
-    G0, G1, D, base = 257, 387, 128, 1000
+    D, base = 128, 1000
     rows = _rows(G1, D)
     for metric in (0, 1):
         lower = _lower(G1, D, metric)
         (t,) = _gap_t(cr.pair_values(lower))
         want0 = cr.cluster_from(lower[:G0], G0, t, index_base=base)
         want1 = cr.cluster_from(lower, G1, t, index_base=base)
-        assert want1[0].min() == base and want0[1] == want1[1] == G1 // 4   # every identity has a row among the first 257
+        assert want1[0].min() == base and want0[1] == want1[1] == G1 // 4   # every identity has a row among the first G0
         gal = oneshot.Gallery(rows[:G0], index_base=base)
+        gal.set_option('cluster_round', per)
         prev, n0 = gal.cluster(t, metric)
         _same((prev.cpu().numpy(), int(n0)), want0)
         gal.update(rows[G0:])

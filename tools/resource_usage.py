@@ -49,11 +49,11 @@ def table(src):
 
 
 def main():
-    print('%-110s %5s %5s %7s %7s %8s %4s' % ('kernel', 'VGPR', 'AGPR', 'VGPRsp', 'SGPRsp', 'scratchB', 'occ'))
+    print('%-110s %5s %5s %7s %7s %8s %4s %6s' % ('kernel', 'VGPR', 'AGPR', 'VGPRsp', 'SGPRsp', 'scratchB', 'occ', 'LDS_B'))
     for src in sys.argv[1:]:
         print('# ' + src)
         for r in table(src):
-            print('%-110s %5d %5d %7d %7d %8d %4d' % tuple(r[:7]))
+            print('%-110s %5d %5d %7d %7d %8d %4d %6d' % tuple(r[:8]))
 
 
 if __name__ == '__main__':
