@@ -15,6 +15,53 @@ import torch
 from .. import _native as N
 
 
+MAX_TRACK_FACES, MAX_TRACK_GAP = 64, 32        # DIF_TRACKS_MAX_FACES, DIF_TRACKS_MAX_GAP
+
+
+class TrackState(typing.NamedTuple):
+    """What ``FrameFaces.tracks`` needs to go on with the next batch of frames: the faces of the last ``max_gap`` frames in
+    ``max_gap * k`` fixed slots on the device (``buf``: one buffer laid out as ``dif_tracks_link`` documents it -- the views
+    below name its parts), and three host integers.  Immutable: a call returns a new one."""
+    buf: typing.Optional[torch.Tensor]           # uint8 [dif_tracks_state_size(max_gap, k, d)], or None: no face stored yet
+    max_gap: int
+    k: int                                       # slots per frame
+    d: int
+    pad: int                                     # frames without a face that went by since ``buf`` was written
+    row_base: int                                # faces seen so far = the global row of the next batch's row 0
+
+    def _part(self, name):
+        s = self.max_gap * self.k
+        at = 0
+        for part, dtype, shape in (('labels', torch.int64, (s,)), ('age', torch.int64, (s,)), ('rows', torch.int64, (s,)),
+                                   ('boxes', torch.float32, (s, 4)), ('emb', torch.float32, (s, self.d)),
+                                   ('closed', torch.int32, (s,)), ('count', torch.int32, (self.max_gap,))):
+            size = int(np.prod(shape)) * (8 if dtype == torch.int64 else 4)
+            if part == name:
+                return self.buf[at:at + size].view(dtype).view(shape)
+            at += size
+        raise KeyError(name)
+
+    labels = property(lambda self: self._part('labels'))      # [max_gap * k] int64: slot (t, p) = position p of the t-th
+    age = property(lambda self: self._part('age'))            # of the last max_gap frames; the first count[t] slots of a
+    rows = property(lambda self: self._part('rows'))          # frame are filled.  rows: the face's global row
+    boxes = property(lambda self: self._part('boxes'))
+    emb = property(lambda self: self._part('emb'))
+    closed = property(lambda self: self._part('closed'))      # int32: 1 = has a successor already (no tail any more)
+    count = property(lambda self: self._part('count'))        # [max_gap] int32 (clipped faces are not stored)
+
+
+class Tracks(typing.NamedTuple):
+    """``FrameFaces.tracks``: per face of the batch, on the device.  Rows are GLOBAL: ``state.row_base`` of the state handed
+    in (0 without one) + the row of the batch."""
+    labels: torch.Tensor                         # [M] int64: the global row of the first face of the face's track
+    prev: torch.Tensor                           # [M] int64: the global row of the face it continues, -1 at a start
+    link_dist: torch.Tensor                      # [M] float32: the distance to that face, NaN at a start
+    age: torch.Tensor                            # [M] int64: 1 at a start, age[prev] + 1
+    n_new: torch.Tensor                          # [1] int64: tracks started in this batch
+    clipped: torch.Tensor                        # [1] int64: faces at a position >= max_faces_per_frame
+    state: TrackState
+
+
 class FrameFaces(typing.NamedTuple):
     """All faces of a batch of N frames, M rows in all.  Row order: frame-major; inside a frame the detector's pick order
     (descending score).  The faces of frame f are rows ``offsets[f] : offsets[f + 1]``."""
@@ -51,6 +98,67 @@ class FrameFaces(typing.NamedTuple):
             return torch.empty((0,), dtype=torch.int64, device=self.emb.device)
         from .. import oneshot
         return oneshot.dbscan(self.emb, tolerance, min_samples, distance_metric)[0]
+
+    def tracks(self, tolerance, min_iou: float = 0.3, max_gap: int = 1, distance_metric: int = 1,
+               state: typing.Optional[TrackState] = None, max_faces_per_frame: typing.Optional[int] = None) -> Tracks:
+        """The faces of the batch -- ONE sequence of frames, in order -- linked into tracks (``dif_tracks_link``, where the
+        rule is written out): a face continues the track whose last face, at most ``max_gap`` frames ago (frames without
+        faces count), has a box IoU >= ``min_iou`` with it and an embedding within ``tolerance`` (units of
+        ``evaluation.utility.distance``, bit for bit its values); nearest pairs first, ties to the lower rows; a track
+        holds one face per frame at most.  Unlike ``cluster`` it never joins two people who are on screen at once, looks
+        at neighbouring frames only, and goes on from batch to batch: hand ``state`` of the ``Tracks`` returned for the
+        previous batch to the call for the next, and labels, ages and link distances are those of one call over all
+        frames, bit for bit.  Labels are global rows, so ``templates(tracks.labels)`` pools a batch and
+        ``TemplatePool.add(faces.emb, tracks.labels)`` pools batch after batch.
+
+        ``max_faces_per_frame`` (at most 64): the faces of a frame beyond it (its lowest scores) are never linked and are
+        counted in ``clipped``.  Given, the call reads nothing back to the host.  ``None``: the size of the largest frame
+        -- at most 64 -- which is read back ONCE (8 bytes, one synchronisation of the stream).  ``M == 0`` returns empty
+        tensors and launches nothing; the state still moves on by the N frames."""
+        if self.emb is None:
+            raise ValueError('FrameFaces.tracks needs the embeddings (embed_and_match, or a pipeline\'s faces())')
+        if distance_metric not in (0, 1):
+            raise RuntimeError('Undefined distance metric %d' % distance_metric)
+        max_gap = int(max_gap)
+        if not 1 <= max_gap <= MAX_TRACK_GAP:
+            raise ValueError('max_gap must lie in [1, %d], got %d' % (MAX_TRACK_GAP, max_gap))
+        if max_faces_per_frame is not None and not 1 <= int(max_faces_per_frame) <= MAX_TRACK_FACES:
+            raise ValueError('max_faces_per_frame must lie in [1, %d], got %s' % (MAX_TRACK_FACES, max_faces_per_frame))
+        m, d = self.emb.shape
+        n = self.offsets.shape[0] - 1
+        if state is None:
+            state = TrackState(None, max_gap, 0, d, 0, 0)
+        elif (state.max_gap, state.d) != (max_gap, d):
+            raise ValueError('the state was written with max_gap %d and %d-d embeddings, this call has %d and %d'
+                             % (state.max_gap, state.d, max_gap, d))
+        dev = self.emb.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        if m == 0:
+            empty = torch.empty((0,), **i64)
+            return Tracks(empty, empty.clone(), torch.empty((0,), dtype=torch.float32, device=dev), empty.clone(),
+                          torch.zeros((1,), **i64), torch.zeros((1,), **i64), state._replace(pad=min(state.pad + n, max_gap)))
+        N.require_device()
+        offsets = self.offsets.to(dtype=torch.int64).contiguous()
+        if max_faces_per_frame is None:
+            largest = int((offsets[1:] - offsets[:-1]).max().item())          # the one host read
+            kmax = min(max(largest, 1), MAX_TRACK_FACES)
+        else:
+            kmax = int(max_faces_per_frame)
+        boxes = self.boxes.to(dtype=torch.float32).contiguous()
+        emb = self.emb.to(dtype=torch.float32).contiguous()
+        k_in = state.k if state.buf is not None else 0
+        k_out = max(kmax, k_in)
+        out_buf = torch.empty((N.lib.dif_tracks_state_size(max_gap, k_out, d),), dtype=torch.uint8, device=dev)
+        work = torch.empty((N.lib.dif_tracks_workspace_size(m, max_gap, kmax, k_in),), dtype=torch.uint8, device=dev)
+        labels, prev, age = torch.empty((m,), **i64), torch.empty((m,), **i64), torch.empty((m,), **i64)
+        link_dist = torch.empty((m,), dtype=torch.float32, device=dev)
+        n_new, clipped = torch.empty((1,), **i64), torch.empty((1,), **i64)
+        N.check(N.lib.dif_tracks_link(N.ptr(offsets), N.ptr(boxes), N.ptr(emb), n, m, d, float(tolerance), float(min_iou), max_gap,
+                                      distance_metric, kmax, state.row_base, N.ptr(state.buf) if k_in else None, k_in, state.pad,
+                                      N.ptr(prev), N.ptr(link_dist), N.ptr(labels), N.ptr(age), N.ptr(n_new), N.ptr(clipped),
+                                      N.ptr(out_buf), k_out, N.ptr(work), work.shape[0], 0, N.stream_ptr()))
+        return Tracks(labels, prev, link_dist, age, n_new, clipped,
+                      TrackState(out_buf, max_gap, k_out, d, 0, state.row_base + m))
 
     def templates(self, labels, weighted: bool = False, normalize: bool = True):
         """One template per person of the batch: the embeddings pooled by ``labels`` [M] (what ``cluster`` or ``dbscan``

@@ -815,6 +815,72 @@ int dif_pool_reduce(dif_pool* p, const float* state_sums_dev, const float* state
 int dif_pool_finish(const float* sums_dev, const float* wsum_dev, const int64_t* counts_dev, int64_t t, int d, int normalize,
                     float* out_dev, void* stream);
 
+/* ------------------------------------------------------------------ tracks
+ * The faces of a sequence of frames linked into tracks (csrc/tracks.hip; not in the reference, whose
+ * detect_multiple_faces sees one image at a time).  A face continues the track whose last face, at most max_gap frames
+ * ago, overlaps it in the image and lies within the embedding tolerance; a track holds at most one face per frame.
+ * One sequence per call: n_frames frames with m faces in frame-major order, offsets_dev int64 [n_frames + 1] (read on
+ * the device only), boxes_dev float [m][4] left / top / right / bottom, emb_dev float [m][d].  offsets must ascend from
+ * offsets[0] = 0 to offsets[n_frames] = m; the host cannot check that without a read.  Whatever they hold, no row outside
+ * [0, m) is touched (values are clamped to [0, m] and a descending one closes an empty frame), but a row that no frame
+ * covers receives NO output and is not counted in n_new_out_dev.
+ *   position   of a face = its index inside its frame; a face at a position >= kmax is CLIPPED: never linked in either
+ *              direction, a track of its own, counted in clipped_out_dev.  kmax in [1, DIF_TRACKS_MAX_FACES].
+ *   open tail  at frame f: an unclipped face i that nothing has been linked after yet, 1 <= f - frame[i] <= max_gap
+ *              (frames without faces count as frames); max_gap in [1, DIF_TRACKS_MAX_GAP].
+ *   Frames in ascending order.  The candidates of frame f are the pairs (open tail i, unclipped face j of f) with
+ *     iou(box_i, box_j) >= min_iou    box_iou of the detectors' suppression in float32, every product and sum rounded on
+ *                                     its own; a NaN IoU is no candidate; a box without area has IoU 0
+ *     dist <= tolerance               dist = dif_pairwise's value for (emb_j, emb_i) bit for bit: metric 0 squared L2,
+ *                                     metric 1 arccos(cos) / pi, NaN where the reference has NaN; a NaN is no candidate
+ *   taken in ascending (dist, i, j) -- dist as a float32 number, ties to the lower i, then the lower j -- and accepted
+ *   when neither i nor j was accepted earlier in the frame: prev[j] = i, link_dist[j] = dist, i is no tail any more.
+ *   A face of the frame left without a predecessor starts a track: prev -1, link_dist NaN.
+ * Outputs, per face: prev_out_dev int64 [m] (a GLOBAL row: row_base + the row of the call, or the row a stored face
+ *   had in its own call), link_dist_out_dev float [m], labels_out_dev int64 [m] (the global row of the first face of the
+ *   track), age_out_dev int64 [m] (1 at a start, age[prev] + 1); n_new_out_dev int64 [1] the tracks started,
+ *   clipped_out_dev int64 [1].  Every output is a function of the inputs alone, whatever the order of threads and blocks.
+ * Continuing: state_out_dev (or NULL) receives the last max_gap frames -- stored faces, skipped frames and frames of this
+ *   call alike -- in max_gap x state_k_out fixed slots (dif_tracks_state_size bytes: per slot label, age, global row,
+ *   box, embedding and whether it is still a tail; per frame its number of unclipped faces; clipped faces are not kept,
+ *   they are never tails).  state_k_out >= kmax and >= state_k_in.  The next call takes it as state_in_dev with
+ *   state_k_in = that state_k_out, the same max_gap and d, row_base = the faces seen so far, and state_pad = the frames
+ *   of batches without a face that the caller skipped since (no call is needed for those).  The stored frames precede
+ *   the call's: their links stand and they only serve as tails.  A sequence walked in chunks of any sizes gives the
+ *   labels, ages, link distances and (global) prevs of one call over the whole, bit for bit.  state_in_dev NULL: a new
+ *   sequence.  The state is not modified; state_out_dev may not overlap it.
+ * workspace_dev: dif_tracks_workspace_size(m, max_gap, kmax, state_k_in) bytes of the caller's (0 for state_k_in when
+ *   there is no state), aligned to 8 bytes like the states; contents need not be kept between calls, and calls that
+ *   share a workspace must be ordered on one stream.  It holds the candidate table float [m][max_gap][max(kmax,
+ *   state_k_in)] and one flag per face.
+ * passes: 0 = all three, which is what every caller but a measurement passes; or a set of DIF_TRACKS_PASS_* to time a
+ *   pass alone (tools/tracks_bench.py).  A pass run alone reads what the pass before it left in the workspace -- the walk
+ *   the candidate table, the state pass the walk's flags -- so its outputs mean something only directly after a call with
+ *   passes = 0 and the same arguments on the same workspace; on any other workspace contents they are unspecified (no
+ *   row outside the buffers is touched: table values are only compared).
+ * Costs: the candidate pass is one block per (face, gap): the IoU of every pair, the distance -- one wave per pair, as
+ *   dif_pairwise -- only of the pairs the IoU admits.  The walk is one block and sequential in the frames.  The three
+ *   launches are stream-ordered; nothing is read back and nothing waits.  m = 0 is allowed (the state still advances).
+ * Fails before any launch on: a NULL pointer where one is needed, kmax, state_k_in or state_k_out outside
+ *   [1, DIF_TRACKS_MAX_FACES], max_gap outside [1, DIF_TRACKS_MAX_GAP], a metric other than 0 or 1, d outside [1, 8192]
+ *   (dif_pairwise's range), negative sizes, n_frames above 2^30 or m above 2^31 - 1, faces without a frame, a workspace
+ *   that is too small or misaligned.
+ * The two size functions return -1 on such arguments. */
+#define DIF_TRACKS_MAX_FACES 64
+#define DIF_TRACKS_MAX_GAP 32
+#define DIF_TRACKS_PASS_CAND 1
+#define DIF_TRACKS_PASS_WALK 2
+#define DIF_TRACKS_PASS_STATE 4
+int64_t dif_tracks_state_size(int max_gap, int k, int d);
+int64_t dif_tracks_workspace_size(int64_t m, int max_gap, int kmax, int state_k_in);
+int dif_tracks_link(const int64_t* offsets_dev /* [n_frames + 1] */, const float* boxes_dev /* [m][4] */,
+                    const float* emb_dev /* [m][d] */, int64_t n_frames, int64_t m, int d, float tolerance, float min_iou,
+                    int max_gap, int metric, int kmax, int64_t row_base, const void* state_in_dev /* or NULL */,
+                    int state_k_in, int64_t state_pad, int64_t* prev_out_dev /* [m] */, float* link_dist_out_dev /* [m] */,
+                    int64_t* labels_out_dev /* [m] */, int64_t* age_out_dev /* [m] */, int64_t* n_new_out_dev /* [1] */,
+                    int64_t* clipped_out_dev /* [1] */, void* state_out_dev /* or NULL */, int state_k_out,
+                    void* workspace_dev, int64_t workspace_bytes, int passes, void* stream);
+
 /* ------------------------------------------------------------------ ArcMargin logits
  * Not in the reference (north_star only; ArcFace, Deng et al. 2019):
  * logits = s * cos(theta + m * onehot(label)); labels_dev NULL -> s * cos(theta). */
