@@ -16,6 +16,7 @@
 //   reduce  pool_reduce_kernel     one thread per (segment, float4 column): the segment's rows in sorted -- that is, row --
 //                                  order into ONE accumulator, the loads of kLookAhead rows issued in front of their
 //                                  adds and their positions a chunk earlier
+//   best    pool_best_kernel       one thread per segment: the row with the greatest key, in the segment's order (best shot)
 //   finish  pool_finish_kernel     one wave per template: sums / divisor, and the row's norm in NumPy's order (np_sum)
 // The only atomics are the ORs of pool_stats_kernel and LDS counters whose totals do not depend on the order; every
 // output is a function of the input alone.
@@ -354,6 +355,49 @@ __global__ __launch_bounds__(256) void pool_reduce_kernel(const PoolMeta* __rest
   }
 }
 
+// One thread per segment: the stored entry, if the segment has one, then the new rows in ascending row; a row is taken
+// when nothing was taken yet or its key is strictly greater, so a tie keeps the lower row and a NaN never wins.
+__global__ __launch_bounds__(256) void pool_best_kernel(const PoolMeta* __restrict__ meta, const unsigned long long* __restrict__ k0,
+                                                        const unsigned long long* __restrict__ k1, const int* __restrict__ p0,
+                                                        const int* __restrict__ p1, const int* __restrict__ seg_start, int t0,
+                                                        const float* __restrict__ state_key, const int64_t* __restrict__ state_row,
+                                                        const int64_t* __restrict__ state_counts, const float* __restrict__ key, int64_t row_base,
+                                                        int64_t t, int64_t* __restrict__ labels_out, float* __restrict__ key_out,
+                                                        int64_t* __restrict__ row_out, int64_t* __restrict__ counts_out) {
+  if (meta->T != t) return;                     // as pool_reduce_kernel: nothing into buffers of a wrong size
+  const int64_t seg = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (seg >= t) return;
+  const int fin = meta->final_buf;
+  const int* __restrict__ order = fin ? p1 : p0;
+  const int b = seg_start[seg], e = seg_start[seg + 1];
+  float best = __builtin_nanf("");
+  int64_t row = -1, cnt = e - b;
+  int i = b;
+  const int first = order[b];
+  if (first < t0) {
+    best = state_key[first];
+    row = state_row[first];
+    if (row < 0 || best != best) {              // a label that has shown NaN keys only
+      best = __builtin_nanf("");
+      row = -1;
+    }
+    cnt = state_counts[first] + (e - b - 1);
+    i = b + 1;
+  }
+  for (; i < e; ++i) {
+    const int p = order[i] - t0;
+    const float k = key[p];
+    if (k == k && (row < 0 || k > best)) {
+      best = k;
+      row = row_base + p;
+    }
+  }
+  labels_out[seg] = (int64_t)(fin ? k1 : k0)[b];
+  key_out[seg] = best;
+  row_out[seg] = row;
+  counts_out[seg] = cnt;
+}
+
 __global__ __launch_bounds__(256) void pool_finish_kernel(const float* __restrict__ sums, const float* __restrict__ wsum,
                                                           const int64_t* __restrict__ counts, int64_t t, int d, int normalize,
                                                           const SumPlan plan, float* __restrict__ out) {
@@ -515,6 +559,29 @@ int dif_pool_reduce(dif_pool* p, const float* state_sums_dev, const float* state
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, p->meta, p->keys[0], p->keys[1], p->pos[0], p->pos[1], p->seg_start,
                      (int)p->t0, (const float4*)state_sums_dev, state_wsum_dev, state_counts_dev, (const float4*)rows_dev, weights_dev, t, q,
                      labels_out_dev, (float4*)sums_out_dev, wsum_out_dev, counts_out_dev);
+  DIF_HIP(hipGetLastError());
+  return 0;
+}
+
+int dif_pool_best(dif_pool* p, const float* state_key_dev, const int64_t* state_row_dev, const int64_t* state_counts_dev, const float* key_dev,
+                  int64_t row_base, int64_t t, int64_t* labels_out_dev, float* key_out_dev, int64_t* row_out_dev, int64_t* counts_out_dev,
+                  void* stream) {
+  if (!p) return set_error("dif_pool_best: null handle");
+  if (!p->grouped) return set_error("dif_pool_best: no dif_pool_group on this handle left an order behind");
+  if (t < p->t0 || t > p->t0 + p->n)
+    return set_error("dif_pool_best: t %lld disagrees with the group (%lld stored templates, %lld rows)", (long long)t, (long long)p->t0,
+                     (long long)p->n);
+  const hipError_t seen = hipEventQuery(p->t_event);
+  (void)hipGetLastError();                      // (not ready is no error)
+  if (seen == hipSuccess && *p->t_host != t)
+    return set_error("dif_pool_best: t %lld disagrees with the %lld templates the group found", (long long)t, (long long)*p->t_host);
+  if ((p->t0 > 0 && (!state_key_dev || !state_row_dev || !state_counts_dev)) || (p->n > 0 && !key_dev) ||
+      (t > 0 && (!labels_out_dev || !key_out_dev || !row_out_dev || !counts_out_dev)))
+    return set_error("dif_pool_best: null pointer");
+  if (t == 0) return 0;
+  hipLaunchKernelGGL(pool_best_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->meta, p->keys[0], p->keys[1],
+                     p->pos[0], p->pos[1], p->seg_start, (int)p->t0, state_key_dev, state_row_dev, state_counts_dev, key_dev, row_base, t,
+                     labels_out_dev, key_out_dev, row_out_dev, counts_out_dev);
   DIF_HIP(hipGetLastError());
   return 0;
 }

@@ -63,6 +63,10 @@ SIGNATURES = {
     'dif_pool_reduce': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
     'dif_pool_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    'dif_pool_best': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    'dif_face_quality': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p]),
     'dif_tracks_state_size': (c_int64, [c_int, c_int, c_int]),
     'dif_tracks_workspace_size': (c_int64, [c_int64, c_int, c_int, c_int]),
     'dif_tracks_link': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_int, c_int, c_int, c_int64,

@@ -160,12 +160,40 @@ class FrameFaces(typing.NamedTuple):
         return Tracks(labels, prev, link_dist, age, n_new, clipped,
                       TrackState(out_buf, max_gap, k_out, d, 0, state.row_base + m))
 
-    def templates(self, labels, weighted: bool = False, normalize: bool = True):
+    def quality(self, frame_hw=None, lo: int = 0, hi: int = 255):
+        """``quality.face_quality`` on the crops, landmarks and boxes of these faces -> ``quality.FaceQuality``, on the device.
+        ``frame_hw`` = (H, W) of the frames lets the boxes count (``inside``, and its factor of the score); without it they
+        are left out.  Without landmarks the pose columns are NaN."""
+        from . import quality
+        return quality.face_quality(self.crops, self.landmarks, self.boxes if frame_hw is not None else None, frame_hw, lo, hi)
+
+    def best(self, labels, key=None, frame_hw=None):
+        """The best shot of every label: the ONE face with the greatest ``key`` [M] float32 -- default: ``quality(frame_hw)
+        .score`` -- among the faces that carry it -> (best_row [T] int64, template_labels [T] int64 ascending, best_key [T]
+        float32, counts [T] int64) on the device.  Ties go to the lower row, a NaN key is never chosen, and a label whose
+        keys are all NaN has row -1 and key NaN (``templates.BestShots``, where the rule is written out).  A negative label
+        leaves the face out; ``M == 0`` gives empty tensors."""
+        dev = self.crops.device
+        if self.crops.shape[0] == 0:
+            i64 = dict(dtype=torch.int64, device=dev)
+            return (torch.empty((0,), **i64), torch.empty((0,), **i64), torch.empty((0,), dtype=torch.float32, device=dev),
+                    torch.empty((0,), **i64))
+        from .. import templates
+        if key is None:
+            key = self.quality(frame_hw).score
+        shots = templates.BestShots(device=dev if dev.type == 'cuda' else None)
+        try:
+            shots.add(labels, key.contiguous() if torch.is_tensor(key) else key)
+            return shots.row, shots.labels, shots.key, shots.counts
+        finally:
+            shots.close()
+
+    def templates(self, labels, weighted=False, normalize: bool = True):
         """One template per person of the batch: the embeddings pooled by ``labels`` [M] (what ``cluster`` or ``dbscan``
         returned; a negative label -- noise -- leaves the face out) -> (templates [T, d] float32, template_labels [T] int64
         ascending, counts [T] int64) on the device.  A template is the mean of its faces in row order, exact
-        (``templates.pool_templates``), divided by its norm with ``normalize``; ``weighted`` weighs every face by its detection
-        score.  ``M == 0`` gives empty tensors."""
+        (``templates.pool_templates``), divided by its norm with ``normalize``; ``weighted`` = True weighs every face by its
+        detection score, a float32 tensor [M] -- ``quality().score``, say -- by that.  ``M == 0`` gives empty tensors."""
         if self.emb is None:
             raise ValueError('FrameFaces.templates needs the embeddings (embed_and_match, or a pipeline\'s faces())')
         if self.emb.shape[0] == 0:
@@ -173,7 +201,13 @@ class FrameFaces(typing.NamedTuple):
             return (torch.empty((0, self.emb.shape[1]), dtype=torch.float32, device=dev),
                     torch.empty((0,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int64, device=dev))
         from .. import templates
-        return templates.pool_templates(self.emb, labels, self.scores if weighted else None, normalize)[:3]
+        if torch.is_tensor(weighted):
+            weights = weighted
+            if weights.dtype != torch.float32 or tuple(weights.shape) != (self.emb.shape[0],):
+                raise ValueError('weights must be a float32 tensor [%d], got %s %s' % (self.emb.shape[0], weights.dtype, tuple(weights.shape)))
+        else:
+            weights = self.scores if weighted else None
+        return templates.pool_templates(self.emb, labels, weights, normalize)[:3]
 
 
 def _tensor(x):

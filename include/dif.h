@@ -814,6 +814,63 @@ int dif_pool_reduce(dif_pool* p, const float* state_sums_dev, const float* state
                     float* wsum_out_dev, int64_t* counts_out_dev, void* stream);
 int dif_pool_finish(const float* sums_dev, const float* wsum_dev, const int64_t* counts_dev, int64_t t, int d, int normalize,
                     float* out_dev, void* stream);
+/* dif_pool_best: the best shot of every label -- the ONE row with the greatest key (a face quality, say) -- on the order a
+ *   dif_pool_group on the same handle left behind, with dif_pool_reduce's checks: it fails without a group, for a t outside
+ *   [t0, t0 + n] and, once the group has run, for a t that is not the T it wrote; behind a group that is still running the
+ *   kernel checks t on the device and writes nothing.  State (NULL when t0 = 0): state_key_dev float [t0],
+ *   state_row_dev int64 [t0], state_counts_dev int64 [t0], as an earlier call wrote them for the labels the group was
+ *   given as its state.  key_dev float [n]: the key of new row i, whose GLOBAL row is row_base + i; a caller advances
+ *   row_base by n per call, so that stored rows lie below new ones.  Per distinct non-negative label, ascending:
+ *     labels_out_dev [t]   the label
+ *     key_out_dev [t], row_out_dev [t]   the entry with the greatest key among the stored entry and the label's new
+ *                          rows, and its global row.  Exact ties go to the lower global row; -0.0 ties with +0.0; a NaN
+ *                          key is never chosen; -inf is an ordinary key and beats "nothing".  A label whose keys are
+ *                          all NaN: row -1, key NaN (and such a stored entry is "nothing" to the next call)
+ *     counts_out_dev [t]   the rows seen for the label, NaN keys included (stored count + new rows)
+ *   One thread per label walks its segment in order -- the stored entry, then the new rows in ascending row -- and takes
+ *   a row when its key is strictly greater: no atomics, no dependence on thread order, and calls over chunks equal one
+ *   call over all rows, bit for bit.  Outputs may not overlap the state.  t = 0 is a no-op. */
+int dif_pool_best(dif_pool* p, const float* state_key_dev, const int64_t* state_row_dev, const int64_t* state_counts_dev,
+                  const float* key_dev, int64_t row_base, int64_t t, int64_t* labels_out_dev, float* key_out_dev,
+                  int64_t* row_out_dev, int64_t* counts_out_dev, void* stream);
+
+/* ------------------------------------------------------------------ face quality (csrc/quality.hip)
+ * Per-face image and pose measures from what the video path already holds on the device: the crops the embedder is
+ * given, the five landmarks and the boxes (deep_insight_face.detector.quality: face_quality; FrameFaces.quality / .best).
+ * Not in the reference.  tests/quality_ref.py restates every column in NumPy, bit for bit.
+ * crops_dev uint8 [m][S][S][3], 3 <= S <= 256; landmarks_dev float [m][5][2] or NULL -- left eye (le), right eye (re),
+ * nose, left mouth corner (ml), right mouth corner (mr), as (x, y) in frame pixels; boxes_dev float [m][4] left, top,
+ * right, bottom or NULL, with the frame size frame_h, frame_w; lo, hi in [0, 255].
+ * stats_out_dev int64 [m][6], exact.  With c the three stored channels of a pixel as integers,
+ *     g      = (c0 + 2*c1 + c2 + 2) >> 2          symmetric in channels 0 and 2: RGB and BGR crops measure the same
+ *     L(y,x) = g(y-1,x) + g(y+1,x) + g(y,x-1) + g(y,x+1) - 4*g(y,x)   for the interior 1 <= y, x <= S-2 only: nothing
+ *              outside the crop is read and nothing wraps from one row into the next
+ *   the columns are  sum g, sum g*g, sum L, sum L*L, #{g <= lo}, #{g >= hi}; the first, second, fifth and sixth over all
+ *   n = S*S pixels, the third and fourth over the k = (S-2)^2 interior pixels.
+ * out_dev float [m][DIF_QUALITY_COLS]; each value is formed in float64 exactly as written (no contraction) and rounded once:
+ *   0 brightness  sum_g / (n*255)
+ *   1 contrast    sqrt((n*sum_g2 - sum_g^2) / (n*n)) / 255
+ *   2 sharpness   (k*sum_L2 - sum_L^2) / (k*k)                       the variance of the Laplacian
+ *   3 clipped     (n_dark + n_bright) / n
+ *   4 eye_dist    sqrt(e2),  ex = re.x-le.x, ey = re.y-le.y, e2 = ex*ex + ey*ey
+ *   5 roll        ey / eye_dist                                     the sine of the in-plane angle
+ *   6 yaw         2*t - 1,  t = ((nose.x-le.x)*ex + (nose.y-le.y)*ey) / e2      0: the nose projects onto the middle
+ *   7 nose_drop   ((nose.x-cx)*vx + (nose.y-cy)*vy) / (vx*vx + vy*vy),  c = (le+re)*0.5, v = (ml+mr)*0.5 - c
+ *   8 inside      (iw*ih) / ((r-l)*(b-t)),  iw = max(min(r, W) - max(l, 0), 0), ih = max(min(b, H) - max(t, 0), 0)
+ *   9 score       sharpness * (1 - clipped) * max(0, 1 - abs(yaw)) * inside
+ *   The numerators of columns 0 to 3 are formed in int64 and converted to double exactly (below 2^53 for S <= 256).  The
+ *   factors of column 9 are the float32 values of columns 2, 3, 6 and 8 converted back to double, multiplied left to
+ *   right; the yaw factor is left out without landmarks, the inside factor without boxes.  Columns 4 to 7 are NaN for
+ *   every row without landmarks, column 8 without boxes.  min and max propagate NaN (np.minimum, np.maximum): a NaN
+ *   landmark or box coordinate gives NaN in the columns that use it and in the score.  Coincident eyes give 0/0 = NaN
+ *   for roll and yaw, a box without area NaN.  The score is a convention without parameters; nobody has measured it
+ *   against recognition accuracy.
+ * One block per crop: the crop is read once, gray is staged in LDS as bytes, partial sums are kept per thread and reduced
+ * by wave and block in 64-bit; no atomics, no dependence on thread order.  m = 0 launches nothing.  A size outside
+ * [3, 256], lo or hi outside [0, 255], m outside [0, 2^31) and a NULL pointer where one is needed fail. */
+#define DIF_QUALITY_COLS 10
+int dif_face_quality(const uint8_t* crops_dev, int64_t m, int size, const float* landmarks_dev, const float* boxes_dev,
+                     float frame_h, float frame_w, int lo, int hi, int64_t* stats_out_dev, float* out_dev, void* stream);
 
 /* ------------------------------------------------------------------ tracks
  * The faces of a sequence of frames linked into tracks (csrc/tracks.hip; not in the reference, whose
