@@ -101,7 +101,7 @@ int dif_gallery_destroy(dif_gallery* h) {
                   (void*)g.pcls, (void*)g.anti_cnt, (void*)g.anti_idx, (void*)g.flags, (void*)g.within_census,
                   (void*)g.within_thr, (void*)g.rank_mate, (void*)g.remove_ws, (void*)g.topk_min, (void*)g.cluster_parent,
                   (void*)g.cluster_bad, (void*)g.dbscan_degree, (void*)g.dbscan_anchor, (void*)g.roc_mask, (void*)g.roc_thr, (void*)g.roc_tab, (void*)g.roc_bins,
-                  (void*)g.topk_ids_stat, (void*)g.topk_tagged_stat})
+                  (void*)g.topk_ids_stat, (void*)g.topk_tagged_stat, (void*)g.within_tagged_stat})
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -374,6 +374,15 @@ int dif_gallery_get_stat(dif_gallery* h, const char* key, int64_t* out, void* st
     *out = (int64_t)v;
     return 0;
   }
+  if (k == "within_tagged_tiles") {            // (probe, tile) pairs the last tagged within / rank / rank_at call evaluated row by row
+    unsigned long long v = 0;
+    if (g.within_tagged_stat) {
+      DIF_HIP(hipMemcpyAsync(&v, g.within_tagged_stat, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      DIF_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
+    *out = (int64_t)v;
+    return 0;
+  }
   return set_error("dif_gallery_get_stat: unknown key '%s'", key);
 }
 
@@ -430,6 +439,77 @@ int dif_match_rank_at(dif_gallery* h, const float* probes_dev, int n, int metric
   if (n == 0) return 0;
   if (!probes_dev || !mate_idx_dev || !mate_dist_in_dev || !count_out_dev) return set_error("dif_match_rank_at: null pointer");
   return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, mate_dist_in_dev, count_out_dev, nullptr, (hipStream_t)stream);
+}
+
+// The tagged range search and rank: with rows enrolled both arrays are needed; an empty gallery reads neither (the run
+// functions are handed a null pair: their untagged path, which evaluates no tile) and the counter reads 0 all the same.
+static int tagged_pair(const char* fn, dif_gallery* h, const int64_t*& row_tags_dev, const int64_t*& probe_masks_dev, void* stream) {
+  if (h->g.n > 0) {
+    if (!row_tags_dev || !probe_masks_dev) return set_error("%s: null row tags or probe masks", fn);
+    return 0;
+  }
+  row_tags_dev = probe_masks_dev = nullptr;
+  if (h->g.within_tagged_stat) DIF_HIP(hipMemsetAsync(h->g.within_tagged_stat, 0, sizeof(unsigned long long), (hipStream_t)stream));
+  return 0;
+}
+
+int dif_match_within_tagged(dif_gallery* h, const float* probes_dev, int n, int metric, float tolerance, int max_hits,
+                            const int64_t* row_tags_dev, const int64_t* probe_masks_dev, int64_t* count_out_dev,
+                            int64_t* idx_out_dev, float* dist_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_within_tagged: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_within_tagged: negative probe count");
+  if (max_hits < 0 || max_hits > DIF_WITHIN_MAX_HITS)
+    return set_error("dif_match_within_tagged: max_hits %d outside [0, %d]", max_hits, DIF_WITHIN_MAX_HITS);
+  if (tolerance != tolerance) return set_error("dif_match_within_tagged: the tolerance is NaN");
+  if (n == 0) return 0;
+  if (!probes_dev || !count_out_dev) return set_error("dif_match_within_tagged: null pointer");
+  if (max_hits > 0 && (!idx_out_dev || !dist_out_dev))
+    return set_error("dif_match_within_tagged: null list pointer with max_hits > 0");
+  if (tagged_pair("dif_match_within_tagged", h, row_tags_dev, probe_masks_dev, stream)) return -1;
+  return within_run(&h->g, probes_dev, n, metric, tolerance, max_hits, count_out_dev, idx_out_dev, dist_out_dev,
+                    (hipStream_t)stream, row_tags_dev, probe_masks_dev);
+}
+
+int dif_match_rank_tagged(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev,
+                          const int64_t* row_tags_dev, const int64_t* probe_masks_dev, int64_t* rank_out_dev,
+                          float* mate_dist_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_rank_tagged: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_rank_tagged: negative probe count");
+  if (n == 0) return 0;
+  if (!probes_dev || !mate_idx_dev || !rank_out_dev) return set_error("dif_match_rank_tagged: null pointer");
+  if (tagged_pair("dif_match_rank_tagged", h, row_tags_dev, probe_masks_dev, stream)) return -1;
+  return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, nullptr, rank_out_dev, mate_dist_out_dev, (hipStream_t)stream,
+                  row_tags_dev, probe_masks_dev);
+}
+
+int dif_match_mate_dist_tagged(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev,
+                               const int64_t* row_tags_dev, const int64_t* probe_masks_dev, float* mate_dist_out_dev,
+                               int64_t* owned_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_mate_dist_tagged: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_mate_dist_tagged: negative probe count");
+  if (n == 0) return 0;
+  if (!probes_dev || !mate_idx_dev || !mate_dist_out_dev || !owned_out_dev)
+    return set_error("dif_match_mate_dist_tagged: null pointer");
+  if (h->g.n > 0 && (!row_tags_dev || !probe_masks_dev)) return set_error("dif_match_mate_dist_tagged: null row tags or probe masks");
+  if (h->g.n == 0) row_tags_dev = probe_masks_dev = nullptr;   // nothing owned: neither array is read
+  return mate_dist_run(&h->g, probes_dev, n, metric, mate_idx_dev, mate_dist_out_dev, owned_out_dev, (hipStream_t)stream,
+                       row_tags_dev, probe_masks_dev);
+}
+
+int dif_match_rank_at_tagged(dif_gallery* h, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev,
+                             const float* mate_dist_in_dev, const int64_t* row_tags_dev, const int64_t* probe_masks_dev,
+                             int64_t* count_out_dev, void* stream) {
+  if (!h) return set_error("dif_match_rank_at_tagged: null handle");
+  if (check_metric(metric)) return -1;
+  if (n < 0) return set_error("dif_match_rank_at_tagged: negative probe count");
+  if (n == 0) return 0;
+  if (!probes_dev || !mate_idx_dev || !mate_dist_in_dev || !count_out_dev) return set_error("dif_match_rank_at_tagged: null pointer");
+  if (tagged_pair("dif_match_rank_at_tagged", h, row_tags_dev, probe_masks_dev, stream)) return -1;
+  return rank_run(&h->g, probes_dev, n, metric, mate_idx_dev, mate_dist_in_dev, count_out_dev, nullptr, (hipStream_t)stream,
+                  row_tags_dev, probe_masks_dev);
 }
 
 int dif_match_topk(dif_gallery* h, const float* probes_dev, int n, int metric, int k, int64_t* idx_out_dev,

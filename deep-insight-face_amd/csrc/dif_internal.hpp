@@ -65,6 +65,8 @@ struct Gallery {
   float* within_thr = nullptr;               // per probe: {key <= [0]: sure, key > [1]: out, |key| >= [2]: borderline, [3] != 0: resolve all}
   size_t within_thr_cap = 0;                 // ... in probes
   int within_round = 0;                      // "within_round": probes per round of dif_match_within / _rank / _rank_at (0: what the census' cap allows)
+  // the tagged forms (dif_match_within_tagged, _rank_tagged, _rank_at_tagged) add the counter of "within_tagged_tiles"
+  unsigned long long* within_tagged_stat = nullptr;
   // dif_match_rank shares the two above (stream-ordered calls) and adds, per probe, the mate's distance and local row
   struct RankMate* rank_mate = nullptr;
   size_t rank_mate_cap = 0;                  // ... in probes
@@ -111,11 +113,13 @@ int gallery_remove_rows(Gallery* g, const int64_t* rows_dev, int64_t k, int64_t*
 int match_run(Gallery* g, const float* probes, int B, int metric, int64_t* idx_out, float* dist_out,
               float* key_out, hipStream_t st);
 int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
-               int64_t* idx_out, float* dist_out, hipStream_t st);
+               int64_t* idx_out, float* dist_out, hipStream_t st, const int64_t* row_tags = nullptr,
+               const int64_t* probe_masks = nullptr);                                     // tags given: dif_match_within_tagged
 int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, const float* dm_in, int64_t* rank_out,
-             float* mate_dist_out, hipStream_t st);   // dm_in null: dif_match_rank; else dif_match_rank_at (rank_out: the shard's count)
+             float* mate_dist_out, hipStream_t st, const int64_t* row_tags = nullptr,
+             const int64_t* probe_masks = nullptr);   // dm_in null: dif_match_rank; else dif_match_rank_at (rank_out: the shard's count); tags given: the tagged forms
 int mate_dist_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, float* mate_dist_out,
-                  int64_t* owned_out, hipStream_t st);
+                  int64_t* owned_out, hipStream_t st, const int64_t* row_tags = nullptr, const int64_t* probe_masks = nullptr);
 int topk_run(Gallery* g, const float* probes, int B, int metric, int k, int64_t* idx_out, float* dist_out, hipStream_t st,
              const int64_t* row_tags = nullptr, const int64_t* probe_masks = nullptr);   // tags given: dif_match_topk_tagged
 int topk_ids_run(Gallery* g, const float* probes, int B, int metric, int k, const int64_t* row_labels, const int64_t* exclude,

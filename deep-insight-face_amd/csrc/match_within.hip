@@ -3,7 +3,8 @@
 // mate the shard need not hold; the section starts at rank_prep_kernel), and the k nearest rows in order
 // (dif_match_topk; its section, with the argument for its exactness, starts at topk_tilemin_kernel), the k nearest distinct
 // identities over a label per row (dif_match_topk_ids; its section follows topk_run) -- both also over the rows each probe is
-// eligible for (dif_match_topk_tagged, dif_match_topk_ids_tagged: the `Tagged` form of their three kernels) --, and the connected components
+// eligible for (dif_match_topk_tagged, dif_match_topk_ids_tagged: the `Tagged` form of their three kernels; likewise the range search and
+// the rank, dif_match_within_tagged / _rank_tagged / _mate_dist_tagged / _rank_at_tagged: WithinTags and TaggedCensusEpi) --, and the connected components
 // of the gallery's own rows under a tolerance (dif_gallery_cluster; its section, with the union-find argument, starts at cl_find),
 // and density clustering with noise on the same edges (dif_gallery_dbscan; its section starts at dbscan_init_kernel).
 // hipcc-flags: -ffp-contract=off
@@ -90,13 +91,29 @@ struct RankMate {
   int row;                                                    // its local row, or -1: unmated
 };
 
+// Tagged (dif_match_within_tagged, dif_match_rank_tagged, dif_match_mate_dist_tagged, dif_match_rank_at_tagged): row r is
+// eligible for probe p iff (row_tags[r] & probe_masks[p]) != 0 on the raw 64 bits, and every query is the untagged one with the
+// distance of an ineligible row taken as NaN: never a hit, never closer, never a tie.  The tagged kernels below are the
+// `Tagged` instantiations of the untagged ones and take one WithinTags by value through a parameter pack that is empty for
+// Tagged = false, so the untagged kernels keep the argument lists -- and the code -- they had.
+struct WithinTags {
+  const int64_t* row_tags;                                    // [G]
+  const int64_t* probe_masks;                                 // [B], this launch's probes
+  unsigned long long* tiles_stat;                             // "within_tagged_tiles"
+};
+__device__ __forceinline__ const WithinTags& within_tags(const WithinTags& t) { return t; }
+
+// Tagged: the mate's eligibility is tested first.  An ineligible mate has the distance NaN -- thresholds all OUT, nothing
+// resolved, rank = G, "behind every row" -- and stays mated (RankMate.row >= 0), which tells it from an unmated probe (-1).
+template <bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict__ probes, int B, int D, int metric, float cdot,
                                                         const unsigned* __restrict__ sqmax_bits,
                                                         const float* __restrict__ gallery, int64_t G, int64_t index_base,
                                                         const int64_t* __restrict__ mates, int clamp, const SumPlan plan,
                                                         f32x4* __restrict__ thr, RankMate* __restrict__ mate,
                                                         float* __restrict__ mate_dist_out,
-                                                        const float* __restrict__ dm_in) {
+                                                        const float* __restrict__ dm_in, const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one WithinTags exactly when Tagged");
   __shared__ float scratch[4][NP_SCRATCH];
   const int wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
   if (p >= B) return;                                         // (wave-uniform, like everything below)
@@ -110,8 +127,13 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict_
   float dm = __builtin_nanf("");
   // dif_match_rank_at (dm_in): the mate's distance is handed in -- the shard need not hold the mate -- and RankMate.row is
   // not used: rank_resolve_kernel<true> compares global rows with mates[p] itself
+  bool elig = true;                                           // (dm_in: the owning shard has tested the mate)
+  if constexpr (Tagged) {
+    const WithinTags& tg = within_tags(tagargs...);
+    if (!dm_in && mated) elig = ((unsigned long long)tg.row_tags[ml] & (unsigned long long)tg.probe_masks[p]) != 0;
+  }
   if (dm_in) dm = dm_in[p];
-  else if (mated) (void)ref_distance(plan, scratch[wave], q, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
+  else if (mated && elig) (void)ref_distance(plan, scratch[wave], q, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
   const float s = probe_sq(q, D, lane);
   if (lane != 0) return;
   mate[p] = RankMate{dm, dm_in ? 0 : (mated ? (int)ml : -1)};
@@ -129,17 +151,26 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict_
 
 // dif_match_mate_dist: the ref_distance part of rank_prep_kernel alone, a wave per probe -- the mate's distance where this
 // shard holds the mate (owned 1), NaN and owned 0 where it does not.  No census, no gallery pass.
+// Tagged: a mate this shard holds but the probe is not eligible for is owned (1) with the distance NaN.
+template <bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(256) void mate_dist_kernel(const float* __restrict__ probes, int B, int D, int metric,
                                                         const float* __restrict__ gallery, int64_t G, int64_t index_base,
                                                         const int64_t* __restrict__ mates, int clamp, const SumPlan plan,
-                                                        float* __restrict__ mate_dist_out, int64_t* __restrict__ owned_out) {
+                                                        float* __restrict__ mate_dist_out, int64_t* __restrict__ owned_out,
+                                                        const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one WithinTags exactly when Tagged");
   __shared__ float scratch[4][NP_SCRATCH];
   const int wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
   if (p >= B) return;                                         // (wave-uniform, like everything below)
   const uint64_t ml = (uint64_t)mates[p] - (uint64_t)index_base;   // (unsigned: as in rank_prep_kernel)
   const bool mated = ml < (uint64_t)G;
   float dm = __builtin_nanf("");
-  if (mated)
+  bool elig = true;
+  if constexpr (Tagged) {
+    const WithinTags& tg = within_tags(tagargs...);
+    if (mated) elig = ((unsigned long long)tg.row_tags[ml] & (unsigned long long)tg.probe_masks[p]) != 0;
+  }
+  if (mated && elig)
     (void)ref_distance(plan, scratch[wave], probes + (int64_t)p * D, gallery + (int64_t)ml * D, metric, lane, &dm, clamp != 0);
   if (lane != 0) return;
   mate_dist_out[p] = dm;
@@ -179,18 +210,89 @@ struct CensusEpi : KeyEpi {
   }
 };
 
-template <class T>
+// The tagged census policy: CensusEpi's two counts over the ELIGIBLE rows only.  The tags of the thread's four rows are read
+// beside each `aux` load and the column's mask once per tile, through buffer descriptors bounded like `arsrc` (row_tags + g0
+// over min(rows left, 128) * 8 bytes, probe_masks + p0 over the columns that exist): a row past G reads tag 0, a probe past B
+// mask 0 -- never eligible.  Nothing is loaded per pair.  An ineligible row, like a row past G, adds to neither count, so
+//   word == 0  <=>  the tile holds no eligible row that is SURE or not OUT.
+// A tile with word 0 contributes nothing to a count and nothing to a list: its eligible rows are all OUT (distance > t, or
+// NaN), its other rows are not the probe's.  Under the "resolve everything" flag the thresholds are (-inf, +inf): no key is
+// SURE (key <= -inf only for key = -inf, which fails |key| < H), every key -- a NaN key included -- is "not OUT"
+// (!(key > +inf)), so nout, and with it bord, is the number of ELIGIBLE rows of the tile: word 0 means "no eligible row here"
+// there too, and the resolve kernels may skip it for such a probe as well.  (An untagged census counts the rows past G as
+// borderline under that flag; here they read tag 0 and are not counted.)  bord <= 128 fits the word's upper byte as before.
+struct TaggedCensusEpi : KeyEpi {
+  const f32x4* __restrict__ thr;
+  unsigned short* __restrict__ census;
+  const int64_t* __restrict__ row_tags;
+  const int64_t* __restrict__ probe_masks;
+  using Meet = int;                                           // sure | not out << 16
+  using Col = CensusEpi::Col;
+  struct Tile {
+    __amdgpu_buffer_rsrc_t trsrc, mrsrc;
+  };
+  struct Rows {
+    u32x4 tg[2];                                              // four tags, {lo, hi} each
+  };
+  struct State {
+    int sure, nout;
+    u32x2 msk;                                                // the column's mask, once per tile
+  };
+  __device__ __forceinline__ TaggedCensusEpi(const f32x4* thr_, unsigned short* census_, const int64_t* row_tags_,
+                                             const int64_t* probe_masks_)
+      : thr(thr_), census(census_), row_tags(row_tags_), probe_masks(probe_masks_) {}
+  __device__ __forceinline__ Col column(int p, int B) const {
+    const f32x4 v = (p < B) ? thr[p] : f32x4{0.f, 0.f, 0.f, 0.f};
+    return Col{v[0], v[1], v[2]};
+  }
+  __device__ __forceinline__ Tile tile(int64_t g0, int rows, int p0, int cols) const {
+    return Tile{make_rsrc(row_tags + g0, (uint32_t)(rows * 8)), make_rsrc(probe_masks + p0, (uint32_t)(cols * 8))};
+  }
+  __device__ __forceinline__ State start(const Tile& t, int c) const {
+    return State{0, 0, __builtin_amdgcn_raw_buffer_load_b64(t.mrsrc, (uint32_t)c * 8u, 0, 0)};
+  }
+  __device__ __forceinline__ Rows rows(const Tile& t, int r) const {
+    return Rows{{__builtin_amdgcn_raw_buffer_load_b128(t.trsrc, (uint32_t)r * 8u, 0, 0),
+                 __builtin_amdgcn_raw_buffer_load_b128(t.trsrc, (uint32_t)r * 8u + 16u, 0, 0)}};
+  }
+  __device__ __forceinline__ void visit(State& s, const Col& c, const Rows& rw, int j, float key, bool ok) const {
+    // (a row past G reads tag 0 through the descriptor as well)
+    const unsigned tlo = ok ? rw.tg[j >> 1][2 * (j & 1)] : 0u, thi = ok ? rw.tg[j >> 1][2 * (j & 1) + 1] : 0u;
+    const bool elig = ((tlo & s.msk[0]) | (thi & s.msk[1])) != 0u;
+    s.sure += (elig && key <= c.ts && fabsf(key) < c.hk) ? 1 : 0;
+    s.nout += (elig && !(key > c.tm)) ? 1 : 0;
+  }
+  __device__ __forceinline__ Meet partial(const State& s) const { return s.sure | (s.nout << 16); }
+  __device__ static __forceinline__ Meet combine(Meet a, Meet b) { return a + b; }
+  __device__ __forceinline__ void store(int64_t i, Meet v) const {
+    const int sure = v & 0xffff, bord = (v >> 16) - sure;     // SURE implies not OUT (T - E <= T + E)
+    census[i] = (unsigned short)(sure | (bord << 8));
+  }
+};
+
+// Tagged = false: the census as it was, with the arguments it had (`tagargs` is one WithinTags when Tagged, nothing otherwise)
+template <class T, bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(T::NT, 2) void within_census_kernel(const float* __restrict__ gallery, int64_t G,
                                                                const float* __restrict__ probes, int B, int D,
                                                                const float* __restrict__ aux, int metric, int nparts,
                                                                const f32x4* __restrict__ thr,
-                                                               unsigned short* __restrict__ census) {
-  key_tiles<T>(gallery, G, probes, B, D, aux, metric, nparts, CensusEpi(thr, census));
+                                                               unsigned short* __restrict__ census,
+                                                               const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one WithinTags exactly when Tagged");
+  if constexpr (Tagged)
+    key_tiles<T>(gallery, G, probes, B, D, aux, metric, nparts,
+                 TaggedCensusEpi(thr, census, within_tags(tagargs...).row_tags, within_tags(tagargs...).probe_masks));
+  else key_tiles<T>(gallery, G, probes, B, D, aux, metric, nparts, CensusEpi(thr, census));
 }
 
 // One block per probe; `census` rows are B words apart.  All control flow is block-uniform: every wave derives the same
 // counts from the same LDS words.  (This kernel and the two select kernels synchronise inside a tile and keep walk_words'
 // loop written out: on the shared function they measured 1 to 5 % slower)
+// Tagged (the words are within_census_kernel<T, true>'s): a tile whose word is 0 holds no eligible row that could be a hit
+// and is never evaluated, also for a probe under the "resolve everything" flag (TaggedCensusEpi has the argument); inside an
+// evaluated tile an ineligible row is skipped before ref_distance -- a wave handles one row, so the test is wave-uniform, and
+// which tiles are evaluated still follows from the LDS words alone.  Every evaluated tile counts one into "within_tagged_tiles".
+template <bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const unsigned short* __restrict__ census, int64_t G,
                                                                       int B, const f32x4* __restrict__ thr,
                                                                       const float* __restrict__ probes,
@@ -198,7 +300,9 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const un
                                                                       float t, int clamp, const SumPlan plan, int K,
                                                                       int64_t index_base, int64_t* __restrict__ count_out,
                                                                       int64_t* __restrict__ idx_out,
-                                                                      float* __restrict__ dist_out) {
+                                                                      float* __restrict__ dist_out,
+                                                                      const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one WithinTags exactly when Tagged");
   constexpr int NT = 64 * WITHIN_NW;
   __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
   __shared__ unsigned short s_word[NT];
@@ -208,21 +312,35 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const un
   const float* q = probes + (int64_t)p * D;
   const int64_t gtiles = (G + WITHIN_BM - 1) / WITHIN_BM;
   const bool all = gtiles > 0 && thr[p][3] != 0.f;
+  unsigned long long pm = 0;                                  // Tagged: the probe's mask
+  if constexpr (Tagged) pm = (unsigned long long)within_tags(tagargs...).probe_masks[p];
+  unsigned ntiles = 0;                                        // Tagged: tiles this block evaluated row by row
   int64_t count = 0;                                          // hits so far; the list holds the first min(count, K) of them
   for (int64_t t0 = 0; t0 < gtiles; t0 += NT) {
     const unsigned short w = t0 + tid < gtiles ? census[(t0 + tid) * B + p] : (unsigned short)0;
     s_word[tid] = w;
-    if (!__syncthreads_or(all || w != 0)) continue;           // (also the barrier between two rounds of words)
+    // (also the barrier between two rounds of words)
+    if (!__syncthreads_or(Tagged ? w != 0 : (all || w != 0))) continue;
     const int nw = gtiles - t0 < NT ? (int)(gtiles - t0) : NT;
     for (int j = 0; j < nw; ++j) {
       const int sure = s_word[j] & 0xff, bord = s_word[j] >> 8;
+      if constexpr (Tagged) {
+        if (s_word[j] == 0) continue;                         // no eligible row that is SURE or not OUT; `all`: no eligible row
+      }
       if (!(all || bord > 0 || (sure > 0 && count < K))) {
         count += sure;
         continue;
       }
+      if constexpr (Tagged) ++ntiles;
       const int64_t g0 = (t0 + j) * WITHIN_BM;
       const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
       for (int r = wave; r < rows; r += WITHIN_NW) {
+        if constexpr (Tagged) {
+          if (((unsigned long long)within_tags(tagargs...).row_tags[g0 + r] & pm) == 0) {   // not eligible: never a hit
+            if (lane == 0) s_hit[r] = 0;
+            continue;
+          }
+        }
         float d;
         (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
         if (lane == 0) {
@@ -252,6 +370,9 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const un
     idx_out[(int64_t)p * K + i] = -1;
     dist_out[(int64_t)p * K + i] = __builtin_nanf("");
   }
+  if constexpr (Tagged) {
+    if (tid == 0 && ntiles) atomicAdd(within_tags(tagargs...).tiles_stat, (unsigned long long)ntiles);
+  }
 }
 
 // One block per probe, as within_resolve_kernel without the lists: a tile without a borderline row adds its SURE count (no
@@ -260,7 +381,9 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void within_resolve_kernel(const un
 // its own rows; they meet once, in LDS, at the end.  Which tiles are evaluated is block-uniform (the same LDS words).
 // EXT (dif_match_rank_at): the mate is named by its GLOBAL index mates[p] -- below, inside or above this shard -- and its
 // distance was handed in: there is no "unmated", and a tie counts when the row's global index is below the mate's.
-template <bool EXT>
+// Tagged: as in within_resolve_kernel -- a tile whose word is 0 is never evaluated, whatever the flag; an ineligible row is
+// skipped before ref_distance: it is neither closer nor a tie; every evaluated tile counts one into "within_tagged_tiles".
+template <bool EXT, bool Tagged, class... TagArgs>
 __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsigned short* __restrict__ census, int64_t G,
                                                                     int B, const f32x4* __restrict__ thr,
                                                                     const RankMate* __restrict__ mate,
@@ -268,7 +391,9 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
                                                                     const float* __restrict__ gallery, int D, int metric,
                                                                     int clamp, const SumPlan plan,
                                                                     const int64_t* __restrict__ mates, int64_t index_base,
-                                                                    int64_t* __restrict__ rank_out) {
+                                                                    int64_t* __restrict__ rank_out,
+                                                                    const TagArgs... tagargs) {
+  static_assert(sizeof...(TagArgs) == (Tagged ? 1 : 0), "one WithinTags exactly when Tagged");
   constexpr int NT = 64 * WITHIN_NW;
   __shared__ float scratch[WITHIN_NW][NP_SCRATCH];
   __shared__ unsigned short s_word[NT];
@@ -286,15 +411,26 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
   const bool all = thr[p][3] != 0.f;
   int64_t sure_rows = 0;                                      // the same in every thread
   int mine = 0;                                               // rows this wave evaluated and counted (G < 2^31)
-  walk_words(census, B, p, gtiles, s_word, [&](unsigned short w) { return all || w != 0; }, [&](int64_t tl, unsigned short w) {
+  unsigned long long pm = 0;                                  // Tagged: the probe's mask
+  if constexpr (Tagged) pm = (unsigned long long)within_tags(tagargs...).probe_masks[p];
+  unsigned ntiles = 0;                                        // Tagged: tiles this block evaluated row by row
+  walk_words(census, B, p, gtiles, s_word, [&](unsigned short w) { return Tagged ? w != 0 : (all || w != 0); },
+             [&](int64_t tl, unsigned short w) {
     const int sure = w & 0xff, bord = w >> 8;
+    if constexpr (Tagged) {
+      if (w == 0) return;                                     // no eligible row that is SURE or not OUT; `all`: no eligible row
+    }
     if (!(all || bord > 0)) {
       sure_rows += sure;
       return;
     }
+    if constexpr (Tagged) ++ntiles;
     const int64_t g0 = tl * WITHIN_BM;
     const int rows = G - g0 < WITHIN_BM ? (int)(G - g0) : WITHIN_BM;
     for (int r = wave; r < rows; r += WITHIN_NW) {
+      if constexpr (Tagged) {
+        if (((unsigned long long)within_tags(tagargs...).row_tags[g0 + r] & pm) == 0) continue;   // not eligible: neither
+      }
       float d;
       (void)ref_distance(plan, scratch[wave], q, gallery + (g0 + r) * D, metric, lane, &d, clamp != 0);
       const bool lower = EXT ? index_base + g0 + r < m_ext : g0 + r < mt.row;
@@ -308,27 +444,46 @@ __global__ __launch_bounds__(64 * WITHIN_NW) void rank_resolve_kernel(const unsi
 #pragma unroll
     for (int w = 0; w < WITHIN_NW; ++w) rank += s_part[w];
     rank_out[p] = rank;
+    if constexpr (Tagged) {
+      if (ntiles) atomicAdd(within_tags(tagargs...).tiles_stat, (unsigned long long)ntiles);
+    }
   }
 }
 
 // The census of nb probes at the thresholds in g->within_thr, over gallery rows [0, rows) only (-1: all of them); its words are
-// laid out as for a gallery of `rows` rows
-static int census_pass(const Gallery* g, const float* pr, int nb, int metric, hipStream_t st, int64_t rows = -1) {
+// laid out as for a gallery of `rows` rows.  `tags` given: the tagged census, tags->probe_masks being these probes'.
+static int census_pass(const Gallery* g, const float* pr, int nb, int metric, hipStream_t st, int64_t rows = -1,
+                       const WithinTags* tags = nullptr) {
   return with_census_tile(nb, [&](auto tile) {
     using T = decltype(tile);
-    return launch_key_tiles<within_census_kernel<T>, T>(g, pr, nb, metric, st, key_tiles_lds<T>, rows, key_tiles_parts(g, nb, rows),
-                                                        reinterpret_cast<const f32x4*>(g->within_thr), g->within_census);
+    const int nparts = key_tiles_parts(g, nb, rows);
+    const f32x4* thr = reinterpret_cast<const f32x4*>(g->within_thr);
+    return tags ? launch_key_tiles<within_census_kernel<T, true, WithinTags>, T>(g, pr, nb, metric, st, key_tiles_lds<T>, rows, nparts,
+                                                                                 thr, g->within_census, *tags)
+                : launch_key_tiles<within_census_kernel<T, false>, T>(g, pr, nb, metric, st, key_tiles_lds<T>, rows, nparts, thr,
+                                                                      g->within_census);
   });
 }
 
+// the counter of "within_tagged_tiles", zeroed on the stream by every tagged within / rank / rank_at call
+static int within_tagged_stat_reset(Gallery* g, hipStream_t st) {
+  if (!g->within_tagged_stat) DIF_HIP(hipMalloc(&g->within_tagged_stat, sizeof(unsigned long long)));
+  DIF_HIP(hipMemsetAsync(g->within_tagged_stat, 0, sizeof(unsigned long long), st));
+  return 0;
+}
+
+// row_tags null: dif_match_within; else dif_match_within_tagged (probe_masks [B]).  The masks advance with the probes from
+// round to round, the tags belong to the rows and do not.
 int within_run(Gallery* g, const float* probes, int B, int metric, float tolerance, int max_hits, int64_t* count_out,
-               int64_t* idx_out, float* dist_out, hipStream_t st) {
+               int64_t* idx_out, float* dist_out, hipStream_t st, const int64_t* row_tags, const int64_t* probe_masks) {
   if (B <= 0) return 0;
+  const bool tagged = row_tags != nullptr;
+  if (tagged && within_tagged_stat_reset(g, st)) return -1;
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
   const int clamp = g->clamp_nan ? 1 : 0;
   if (g->n <= 0) {                                           // np.flatnonzero of an empty array: counts 0, lists all padding
-    hipLaunchKernelGGL(within_resolve_kernel, dim3(B), dim3(64 * WITHIN_NW), 0, st, nullptr, (int64_t)0, B, nullptr, probes,
+    hipLaunchKernelGGL(within_resolve_kernel<false>, dim3(B), dim3(64 * WITHIN_NW), 0, st, nullptr, (int64_t)0, B, nullptr, probes,
                        nullptr, g->d, metric, tolerance, clamp, plan, max_hits, g->index_base, count_out, idx_out, dist_out);
     DIF_HIP(hipGetLastError());
     return 0;
@@ -341,35 +496,51 @@ int within_run(Gallery* g, const float* probes, int B, int metric, float toleran
   const float cdot = g->d * U24;                              // the f32 MFMA: a D-term fma chain
   return for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
+    const WithinTags tags{row_tags, tagged ? probe_masks + b0 : nullptr, g->within_tagged_stat};
     hipLaunchKernelGGL(within_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, tolerance, cdot,
                        g->sqmax_bits, reinterpret_cast<f32x4*>(g->within_thr));
     DIF_HIP(hipGetLastError());
-    if (census_pass(g, pr, nb, metric, st)) return -1;
-    hipLaunchKernelGGL(within_resolve_kernel, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
-                       reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
-                       max_hits, g->index_base, count_out + b0, max_hits ? idx_out + b0 * max_hits : nullptr,
-                       max_hits ? dist_out + b0 * max_hits : nullptr);
+    if (census_pass(g, pr, nb, metric, st, -1, tagged ? &tags : nullptr)) return -1;
+    if (tagged)
+      hipLaunchKernelGGL((within_resolve_kernel<true, WithinTags>), dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
+                         reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
+                         max_hits, g->index_base, count_out + b0, max_hits ? idx_out + b0 * max_hits : nullptr,
+                         max_hits ? dist_out + b0 * max_hits : nullptr, tags);
+    else
+      hipLaunchKernelGGL(within_resolve_kernel<false>, dim3(nb), dim3(64 * WITHIN_NW), 0, st, g->within_census, g->n, nb,
+                         reinterpret_cast<const f32x4*>(g->within_thr), pr, g->rows, g->d, metric, tolerance, clamp, plan,
+                         max_hits, g->index_base, count_out + b0, max_hits ? idx_out + b0 * max_hits : nullptr,
+                         max_hits ? dist_out + b0 * max_hits : nullptr);
     DIF_HIP(hipGetLastError());
     return 0;
   });
 }
 
+// row_tags null: dif_match_mate_dist; else dif_match_mate_dist_tagged (no tile is evaluated: the counter is left alone)
 int mate_dist_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, float* mate_dist_out,
-                  int64_t* owned_out, hipStream_t st) {
+                  int64_t* owned_out, hipStream_t st, const int64_t* row_tags, const int64_t* probe_masks) {
   if (B <= 0) return 0;
   SumPlan plan;
   if (make_sum_plan(g->d, &plan)) return -1;
-  hipLaunchKernelGGL(mate_dist_kernel, dim3((B + 3) / 4), dim3(256), 0, st, probes, B, g->d, metric, g->rows, g->n,
-                     g->index_base, mates, g->clamp_nan ? 1 : 0, plan, mate_dist_out, owned_out);
+  if (row_tags)
+    hipLaunchKernelGGL((mate_dist_kernel<true, WithinTags>), dim3((B + 3) / 4), dim3(256), 0, st, probes, B, g->d, metric, g->rows,
+                       g->n, g->index_base, mates, g->clamp_nan ? 1 : 0, plan, mate_dist_out, owned_out,
+                       WithinTags{row_tags, probe_masks, nullptr});
+  else
+    hipLaunchKernelGGL(mate_dist_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, st, probes, B, g->d, metric, g->rows, g->n,
+                       g->index_base, mates, g->clamp_nan ? 1 : 0, plan, mate_dist_out, owned_out);
   DIF_HIP(hipGetLastError());
   return 0;
 }
 
 // `dm_in` null: dif_match_rank.  Not null: dif_match_rank_at -- the mates' distances are the caller's, rank_out receives the
-// shard's count and mate_dist_out is not written.
+// shard's count and mate_dist_out is not written.  row_tags given: the tagged forms (probe_masks [B], advancing with the
+// probes from round to round; the tags do not).
 int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* mates, const float* dm_in, int64_t* rank_out,
-             float* mate_dist_out, hipStream_t st) {
+             float* mate_dist_out, hipStream_t st, const int64_t* row_tags, const int64_t* probe_masks) {
   if (B <= 0) return 0;
+  const bool tagged = row_tags != nullptr;
+  if (tagged && within_tagged_stat_reset(g, st)) return -1;
   if (dm_in && g->n <= 0) {                                   // an empty shard counts nothing, whatever dm is (NaN: its size, 0);
     DIF_HIP(hipMemsetAsync(rank_out, 0, (size_t)B * sizeof(int64_t), st));   // a handle never filled has no sqmax_bits for the band
     return 0;
@@ -387,14 +558,27 @@ int rank_run(Gallery* g, const float* probes, int B, int metric, const int64_t* 
   const float cdot = g->d * U24;
   return for_rounds(rounds, 0, B, [&](int64_t b0, int nb) {
     const float* pr = probes + b0 * g->d;
-    hipLaunchKernelGGL(rank_prep_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits,
-                       g->rows, g->n, g->index_base, mates + b0, clamp, plan, reinterpret_cast<f32x4*>(g->within_thr),
-                       g->rank_mate, mate_dist_out ? mate_dist_out + b0 : nullptr, dm_in ? dm_in + b0 : nullptr);
+    const WithinTags tags{row_tags, tagged ? probe_masks + b0 : nullptr, g->within_tagged_stat};
+    const dim3 pgrid((nb + 3) / 4), rblock(64 * WITHIN_NW);
+    f32x4* thr = reinterpret_cast<f32x4*>(g->within_thr);
+    float* md = mate_dist_out ? mate_dist_out + b0 : nullptr;
+    const float* dmi = dm_in ? dm_in + b0 : nullptr;
+    if (tagged)
+      hipLaunchKernelGGL((rank_prep_kernel<true, WithinTags>), pgrid, dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits,
+                         g->rows, g->n, g->index_base, mates + b0, clamp, plan, thr, g->rank_mate, md, dmi, tags);
+    else
+      hipLaunchKernelGGL(rank_prep_kernel<false>, pgrid, dim3(256), 0, st, pr, nb, g->d, metric, cdot, g->sqmax_bits, g->rows, g->n,
+                         g->index_base, mates + b0, clamp, plan, thr, g->rank_mate, md, dmi);
     DIF_HIP(hipGetLastError());
-    if (gtiles > 0 && census_pass(g, pr, nb, metric, st)) return -1;
-    hipLaunchKernelGGL(dm_in ? rank_resolve_kernel<true> : rank_resolve_kernel<false>, dim3(nb), dim3(64 * WITHIN_NW), 0, st,
-                       g->within_census, g->n, nb, reinterpret_cast<const f32x4*>(g->within_thr), g->rank_mate, pr, g->rows,
-                       g->d, metric, clamp, plan, mates + b0, g->index_base, rank_out + b0);
+    if (gtiles > 0 && census_pass(g, pr, nb, metric, st, -1, tagged ? &tags : nullptr)) return -1;
+    if (tagged)
+      hipLaunchKernelGGL((dm_in ? rank_resolve_kernel<true, true, WithinTags> : rank_resolve_kernel<false, true, WithinTags>), dim3(nb),
+                         rblock, 0, st, g->within_census, g->n, nb, thr, g->rank_mate, pr, g->rows, g->d, metric, clamp, plan,
+                         mates + b0, g->index_base, rank_out + b0, tags);
+    else
+      hipLaunchKernelGGL((dm_in ? rank_resolve_kernel<true, false> : rank_resolve_kernel<false, false>), dim3(nb), rblock, 0, st,
+                         g->within_census, g->n, nb, thr, g->rank_mate, pr, g->rows, g->d, metric, clamp, plan, mates + b0,
+                         g->index_base, rank_out + b0);
     DIF_HIP(hipGetLastError());
     return 0;
   });

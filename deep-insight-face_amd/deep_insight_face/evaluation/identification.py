@@ -74,17 +74,27 @@ def open_set_rates(rank, mate_dist, unmated_min_dist, thresholds, k=1):
     return dirs, far
 
 
-def evaluate_identification(gallery, probes, mates, distance_metric=1, max_rank=10, thresholds=None):
+def evaluate_identification(gallery, probes, mates, distance_metric=1, max_rank=10, thresholds=None, row_tags=None,
+                            probe_masks=None):
     """One 1:N evaluation run: `gallery` an oneshot.Gallery (or the rows to enrol), `probes` [B, d], `mates` [B] the
     global row of each probe's enrolled mate, -1 for a probe of nobody enrolled.
 
     One Gallery.rank call on all probes and -- when thresholds are given -- one Gallery.match call on the unmated ones.
     -> {'rank', 'mate_dist', 'cmc'} and, with thresholds, {'dir', 'far', 'thresholds'} (rank-1 DIR).  NumPy probes give
-    NumPy results, CUDA tensors give CUDA tensors."""
+    NumPy results, CUDA tensors give CUDA tensors.
+
+    Watch-lists: with `row_tags` [len(gallery)] and `probe_masks` [B] (oneshot.Gallery.rank's; both or neither) the run is
+    the one of a gallery that holds, for every probe, only the rows it is eligible for: the tagged rank -- a mate the probe
+    may not see is a miss at every rank (rank len(gallery), mate_dist NaN) --, and for the unmated probes the distance of
+    the nearest ELIGIBLE row, ``Gallery.topk(k=1, row_tags=, probe_masks=)``'s dist[:, 0]: NaN where the probe sees no row,
+    which raises no alarm at any threshold."""
     from .. import oneshot
     g = gallery if isinstance(gallery, oneshot.Gallery) else oneshot.Gallery(gallery)
     try:
-        rank, mate_dist = g.rank(probes, mates, distance_metric)
+        if (row_tags is None) != (probe_masks is None):
+            raise ValueError('row_tags and probe_masks go together: give both or neither')
+        tagged = row_tags is not None
+        rank, mate_dist = g.rank(probes, mates, distance_metric, row_tags, probe_masks)
         out = {'rank': rank, 'mate_dist': mate_dist, 'cmc': cmc(rank, max_rank)}
         if thresholds is not None:
             unmated = rank < 0
@@ -92,7 +102,11 @@ def evaluate_identification(gallery, probes, mates, distance_metric=1, max_rank=
             if p.ndim == 1:
                 p = p[None, :]
             pu = p[unmated]
-            if pu.shape[0] and len(g):
+            if pu.shape[0] and len(g) and tagged:
+                pm = oneshot._bit_sets(probe_masks, 'probe_masks', p.shape[0], g._dev, scalar=True)
+                _, um = g.topk(pu, 1, distance_metric, row_tags, pm[torch.as_tensor(unmated, device=g._dev)])
+                um = um[:, 0]
+            elif pu.shape[0] and len(g):
                 _, um = g.match(pu, distance_metric)
             else:                                            # nobody unmated, or nothing enrolled: no alarm can be raised
                 um = mate_dist[unmated]                      # (NaN for every unmated probe)

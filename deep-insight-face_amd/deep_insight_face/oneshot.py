@@ -179,7 +179,7 @@ class Gallery:
         results for every value (include/dif.h).
         'roc_round': probes per round of `roc`, a multiple of 128 -- 0 (default): what its workspace allows; same results for
         every value (include/dif.h).
-        'within_round': probes per round of `within`, `rank` and `rank_at`, a multiple of 128 -- 0 (default): what the census
+        'within_round': probes per round of `within`, `rank` and `rank_at`, plain and tagged, a multiple of 128 -- 0 (default): what the census
         workspace allows; same results for every value (include/dif.h).
         'topk_round': probes per round of `topk` and `topk_ids`, plain and tagged, a multiple of 128 -- 0 (default): what the
         tile-word workspace allows; same results for every value (include/dif.h).
@@ -196,10 +196,26 @@ class Gallery:
         'roc_resolved': pairs the last `roc` evaluated one by one, too close to a threshold to call (synchronises);
         'topk_ids_tiles': (probe, 128-row tile) pairs the last `topk_ids` evaluated row by row (synchronises);
         'topk_tagged_tiles': the same for the last `topk` or `topk_ids` given `row_tags` and `probe_masks` -- a tile without
-        a row eligible for the probe is never among them (synchronises)."""
+        a row eligible for the probe is never among them (synchronises);
+        'within_tagged_tiles': the same for the last `within`, `rank` or `rank_at_into` given `row_tags` and `probe_masks`
+        -- a tile without an eligible row that could be a hit (resp. closer or tied) is never among them (synchronises)."""
         v = ctypes.c_int64(0)
         N.check(N.lib.dif_gallery_get_stat(self._h, key.encode(), ctypes.byref(v), N.stream_ptr()), ValueError)
         return int(v.value)
+
+    def _tags_into(self, fn, row_tags, probe_masks, B):
+        """The checks of the `_into` forms of the tagged range search and rank: both None -> False; else both dense int64
+        CUDA tensors, [len(self)] and [B] -> True."""
+        if (row_tags is None) != (probe_masks is None):
+            raise ValueError('row_tags and probe_masks go together: give both or neither')
+        if row_tags is None:
+            return False
+        for name, t, shape in (('row_tags', row_tags, (len(self),)), ('probe_masks', probe_masks, (B,))):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != self._dev or not t.is_contiguous():
+                raise ValueError('%s: %s must be a contiguous %s tensor on %s' % (fn, name, torch.int64, self._dev))
+            if tuple(t.shape) != shape:
+                raise ValueError('%s: %s must have shape %s, got %s' % (fn, name, list(shape), tuple(t.shape)))
+        return True
 
     def match_into(self, probes, distance_metric, idx, dist, key=None):
         """Allocation-free form for a serving loop: `probes` [B, d] float32 CUDA, results written into the
@@ -249,9 +265,10 @@ class Gallery:
             idx, dist, key = idx.cpu().numpy(), dist.cpu().numpy(), key.cpu().numpy()
         return (idx, dist, key) if return_key else (idx, dist)
 
-    def within_into(self, probes, tolerance, distance_metric, count, idx, dist):
+    def within_into(self, probes, tolerance, distance_metric, count, idx, dist, row_tags=None, probe_masks=None):
         """Allocation-free form of `within`: `probes` [B, d] float32 CUDA, results written into the caller's CUDA tensors
-        count [B] int64, idx [B, K] int64 and dist [B, K] float32 (K = max_hits, taken from idx; K may be 0)."""
+        count [B] int64, idx [B, K] int64 and dist [B, K] float32 (K = max_hits, taken from idx; K may be 0).  `row_tags`
+        [len(self)] and `probe_masks` [B], both int64 CUDA or both None, restrict every probe to its eligible rows (`within`)."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         tolerance = float(tolerance)
@@ -272,11 +289,17 @@ class Gallery:
         if tuple(dist.shape) != tuple(idx.shape):
             raise ValueError('within_into: dist must have shape %s, got %s' % (tuple(idx.shape), tuple(dist.shape)))
         K = idx.shape[1]
+        if self._tags_into('within_into', row_tags, probe_masks, B):
+            if B:
+                N.check(N.lib.dif_match_within_tagged(self._h, N.ptr(probes), B, distance_metric, tolerance, K,
+                                                      N.ptr(row_tags) if len(self) else None, N.ptr(probe_masks), N.ptr(count),
+                                                      N.ptr(idx) if K else None, N.ptr(dist) if K else None, N.stream_ptr()))
+            return
         if B:
             N.check(N.lib.dif_match_within(self._h, N.ptr(probes), B, distance_metric, tolerance, K, N.ptr(count),
                                            N.ptr(idx) if K else None, N.ptr(dist) if K else None, N.stream_ptr()))
 
-    def within(self, probes, tolerance, distance_metric=1, max_hits=64):
+    def within(self, probes, tolerance, distance_metric=1, max_hits=64, row_tags=None, probe_masks=None):
         """Range search: every enrolled row whose distance to a probe is <= `tolerance`, exact.
         -> (count[B] int64, idx[B, K] int64, dist[B, K] float32) with K = max_hits; NumPy in -> NumPy out.
 
@@ -286,7 +309,13 @@ class Gallery:
         The tolerance is in the units of utility.distance: metric 0 is the SQUARED L2 distance, metric 1 arccos(sim)/pi.
         A NaN distance is never a hit: with the default 'clamp_nan' 0 a similarity that rounding pushes beyond +-1 is NaN in
         the reference -- a probe identical to an enrolled row can miss it this way; set_option('clamp_nan', 1) compares
-        the clamped distance (0 or 1) instead.  An empty gallery gives counts of 0."""
+        the clamped distance (0 or 1) instead.  An empty gallery gives counts of 0.
+
+        Watch-lists: `row_tags` [len(self)] and `probe_masks` [B] (a Python int stands for every probe) are `topk`'s -- row r
+        is eligible for probe b iff ``(row_tags[r] & probe_masks[b]) != 0`` on the raw 64 bits -- and the answer is the one
+        above with ``d[~eligible[b]] = NaN``: an ineligible row is never counted and never listed, however many of them
+        precede the first permitted hit; a tag of 0 is never eligible, a mask of 0 gives count 0 and all padding.  Give both
+        or neither (ValueError otherwise).  `stat('within_tagged_tiles')` tells how many tiles the call evaluated row by row."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         max_hits = int(max_hits)
@@ -301,14 +330,16 @@ class Gallery:
         count = torch.empty((B,), dtype=torch.int64, device=self._dev)
         idx = torch.empty((B, max_hits), dtype=torch.int64, device=self._dev)
         dist = torch.empty((B, max_hits), dtype=torch.float32, device=self._dev)
-        self.within_into(p, tolerance, distance_metric, count, idx, dist)
+        rt, pm = _tag_pair(row_tags, probe_masks, len(self), B, self._dev)
+        self.within_into(p, tolerance, distance_metric, count, idx, dist, rt, pm)
         if was_np:
             count, idx, dist = count.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
         return count, idx, dist
 
-    def rank_into(self, probes, mates, distance_metric, rank, mate_dist):
+    def rank_into(self, probes, mates, distance_metric, rank, mate_dist, row_tags=None, probe_masks=None):
         """Allocation-free form of `rank`: `probes` [B, d] float32 and `mates` [B] int64 CUDA, results written into the
-        caller's CUDA tensors rank [B] int64 and mate_dist [B] float32."""
+        caller's CUDA tensors rank [B] int64 and mate_dist [B] float32.  `row_tags` [len(self)] and `probe_masks` [B], both
+        int64 CUDA or both None: the rank among the rows each probe is eligible for (`rank`)."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[1] != self.emd_size:
@@ -321,11 +352,17 @@ class Gallery:
                 raise ValueError('rank_into: %s must be a contiguous %s tensor on %s' % (name, dt, self._dev))
             if name != 'probes' and (t.dim() != 1 or t.shape[0] != B):
                 raise ValueError('rank_into: %s must have shape [%d], got %s' % (name, B, tuple(t.shape)))
+        if self._tags_into('rank_into', row_tags, probe_masks, B):
+            if B:
+                N.check(N.lib.dif_match_rank_tagged(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates),
+                                                    N.ptr(row_tags) if len(self) else None, N.ptr(probe_masks), N.ptr(rank),
+                                                    N.ptr(mate_dist), N.stream_ptr()))
+            return
         if B:
             N.check(N.lib.dif_match_rank(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(rank),
                                          N.ptr(mate_dist), N.stream_ptr()))
 
-    def rank(self, probes, mates, distance_metric=1):
+    def rank(self, probes, mates, distance_metric=1, row_tags=None, probe_masks=None):
         """Rank of the mate: where row `mates[b]` (global index, any integer dtype, shape [B]) ranks among ALL enrolled rows
         by distance to probe b, exact.  -> (rank[B] int64, mate_dist[B] float32); NumPy in -> NumPy out.
 
@@ -334,7 +371,13 @@ class Gallery:
         ``np.argsort(d, kind='stable')`` when no distance is NaN; ``mate_dist = dm``.  A NaN distance is never closer.
         A mate of -1 (or any index outside the gallery) marks an unmated probe: rank -1, mate_dist NaN.  A mate whose own
         distance is NaN gets rank len(self), a miss at every k.  Without NaNs rank == 0 exactly when `match` returns the mate.
-        Rows of the mate's identity count like any other row."""
+        Rows of the mate's identity count like any other row.
+
+        Watch-lists: with `row_tags` [len(self)] and `probe_masks` [B] (as in `topk` and `within`; a Python int stands for
+        every probe) the rank is the one among the rows the probe is eligible for -- the formula above with
+        ``d[~eligible[b]] = NaN``: ineligible rows are never closer and never tie.  A mate the probe is NOT eligible for is a
+        mate whose distance is NaN: rank len(self), mate_dist NaN -- distinct from an unmated probe (rank -1).  Give both or
+        neither (ValueError otherwise)."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         p, was_np = N.to_device_f32(probes, self._dev)
@@ -361,7 +404,8 @@ class Gallery:
         m = m.to(device=self._dev, dtype=torch.int64).contiguous()
         rank = torch.empty((B,), dtype=torch.int64, device=self._dev)
         mate_dist = torch.empty((B,), dtype=torch.float32, device=self._dev)
-        self.rank_into(p, m, distance_metric, rank, mate_dist)
+        rt, pm = _tag_pair(row_tags, probe_masks, len(self), B, self._dev)
+        self.rank_into(p, m, distance_metric, rank, mate_dist, rt, pm)
         if was_np:
             rank, mate_dist = rank.cpu().numpy(), mate_dist.cpu().numpy()
         return rank, mate_dist
@@ -379,27 +423,43 @@ class Gallery:
                 raise ValueError('%s: %s must have shape [%d], got %s' % (fn, name, B, tuple(t.shape)))
         return B
 
-    def mate_dist_into(self, probes, mates, distance_metric, mate_dist, owned):
+    def mate_dist_into(self, probes, mates, distance_metric, mate_dist, owned, row_tags=None, probe_masks=None):
         """The first shard-local half of a sharded `rank` (parallel.ShardedGallery.rank): for `probes` [B, d] float32 and
         `mates` [B] int64 (global indices) CUDA, writes mate_dist [B] float32 -- the distance to the mate where THIS gallery
-        holds it, NaN where it does not -- and owned [B] int64 (1 / 0).  O(B d): no pass over the gallery."""
+        holds it, NaN where it does not -- and owned [B] int64 (1 / 0).  O(B d): no pass over the gallery.
+        With `row_tags` [len(self)] and `probe_masks` [B] (int64 CUDA, both or neither) a mate this gallery holds but the
+        probe is not eligible for is owned (1) with the distance NaN."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         B = self._rank_args('mate_dist_into', probes, (('mates', mates, torch.int64), ('mate_dist', mate_dist, torch.float32),
                                                        ('owned', owned, torch.int64)))
+        if self._tags_into('mate_dist_into', row_tags, probe_masks, B):
+            if B:
+                N.check(N.lib.dif_match_mate_dist_tagged(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates),
+                                                         N.ptr(row_tags) if len(self) else None, N.ptr(probe_masks),
+                                                         N.ptr(mate_dist), N.ptr(owned), N.stream_ptr()))
+            return
         if B:
             N.check(N.lib.dif_match_mate_dist(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(mate_dist),
                                               N.ptr(owned), N.stream_ptr()))
 
-    def rank_at_into(self, probes, mates, mate_dist, distance_metric, count):
+    def rank_at_into(self, probes, mates, mate_dist, distance_metric, count, row_tags=None, probe_masks=None):
         """The second half: this gallery's share of the rank of a mate it need not hold.  `mate_dist` [B] float32 is the
         mate's distance dm, from whichever shard owns it; count [B] int64 receives
         ``count(d < dm) + count((d == dm) & (index_base + row < mates))`` over this gallery's rows (NaN is never closer;
-        dm NaN gives len(self)).  The counts of disjoint shards add up to `rank` over all their rows."""
+        dm NaN gives len(self)).  The counts of disjoint shards add up to `rank` over all their rows.
+        With `row_tags` [len(self)] and `probe_masks` [B] (int64 CUDA, both or neither) only the rows the probe is eligible
+        for are counted (dm NaN still gives len(self))."""
         if distance_metric not in (0, 1):
             raise RuntimeError('Undefined distance metric %d' % distance_metric)
         B = self._rank_args('rank_at_into', probes, (('mates', mates, torch.int64), ('mate_dist', mate_dist, torch.float32),
                                                      ('count', count, torch.int64)))
+        if self._tags_into('rank_at_into', row_tags, probe_masks, B):
+            if B:
+                N.check(N.lib.dif_match_rank_at_tagged(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(mate_dist),
+                                                       N.ptr(row_tags) if len(self) else None, N.ptr(probe_masks), N.ptr(count),
+                                                       N.stream_ptr()))
+            return
         if B:
             N.check(N.lib.dif_match_rank_at(self._h, N.ptr(probes), B, distance_metric, N.ptr(mates), N.ptr(mate_dist),
                                             N.ptr(count), N.stream_ptr()))
@@ -782,23 +842,24 @@ def match(probes, gallery, distance_metric=1):
             g.close()
 
 
-def within(probes, gallery, tolerance, distance_metric=1, max_hits=64):
+def within(probes, gallery, tolerance, distance_metric=1, max_hits=64, row_tags=None, probe_masks=None):
     """One-call form of Gallery.within: per probe, how many gallery rows lie within `tolerance` and the first
-    `max_hits` of them -> (count[B], idx[B, K], dist[B, K])."""
+    `max_hits` of them -> (count[B], idx[B, K], dist[B, K]); with `row_tags` and `probe_masks`, among the rows the probe is
+    eligible for."""
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
-        return g.within(probes, tolerance, distance_metric, max_hits)
+        return g.within(probes, tolerance, distance_metric, max_hits, row_tags, probe_masks)
     finally:
         if g is not gallery:
             g.close()
 
 
-def rank(probes, gallery, mates, distance_metric=1):
+def rank(probes, gallery, mates, distance_metric=1, row_tags=None, probe_masks=None):
     """One-call form of Gallery.rank: per probe, the rank of its mate row among all gallery rows and the mate's distance
-    -> (rank[B], mate_dist[B])."""
+    -> (rank[B], mate_dist[B]); with `row_tags` and `probe_masks`, among the rows the probe is eligible for."""
     g = gallery if isinstance(gallery, Gallery) else Gallery(gallery)
     try:
-        return g.rank(probes, mates, distance_metric)
+        return g.rank(probes, mates, distance_metric, row_tags, probe_masks)
     finally:
         if g is not gallery:
             g.close()

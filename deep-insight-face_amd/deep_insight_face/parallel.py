@@ -345,7 +345,7 @@ class ShardedGallery:
         return tuple(t.cpu().numpy() for t in ts) if was_np else ts
 
     def _tags(self, row_tags, probe_masks, b):
-        """The watch-list pair of `topk` / `topk_ids`: -> (this shard's row tags [len(shard)], the masks of ALL ranks' probes
+        """The watch-list pair of `topk` / `topk_ids` / `within` / `rank`: -> (this shard's row tags [len(shard)], the masks of ALL ranks' probes
         [R*b]) as int64 on the shard's device, or (None, None); exactly one given raises ValueError."""
         if row_tags is None and probe_masks is None:
             return None, None
@@ -393,15 +393,20 @@ class ShardedGallery:
                              [(torch.int64, (B, k)), (torch.int64, (B, k)), (torch.float32, (B, k))])
         return self._back(was_np, *merge_topk_ids(gi, gd, gl))
 
-    def within(self, local_probes, tolerance, distance_metric=1, max_hits=64):
+    def within(self, local_probes, tolerance, distance_metric=1, max_hits=64, row_tags=None, probe_masks=None):
         """oneshot.Gallery.within over the whole sharded gallery: -> (count [R*b] int64, idx [R*b, K] int64, dist [R*b, K]
         float32), K = max_hits, identical on every rank and equal to one Gallery holding every row: the counts are exact, the
         lists hold the K lowest global rows.  Exchange: the probes, then one gather of R records of R*b*(8 + 12 K) bytes.
         Every rank receives every shard's lists: R * R*b * max_hits * 12 bytes.  Above 2^30 bytes the call raises ValueError
-        before it allocates anything -- lower max_hits (0 gives the counts alone), or bring fewer probes per step."""
+        before it allocates anything -- lower max_hits (0 gives the counts alone), or bring fewer probes per step.
+        `row_tags` [len(shard)] are THIS shard's tags in its local row order; `probe_masks` [b] (or a Python int; None on
+        every rank alike) belong to this rank's probes and are gathered with them (oneshot.Gallery.within).  The merge is
+        unchanged: counts over the eligible rows of disjoint shards add, and the K lowest eligible hits of all shards are
+        among each shard's K lowest."""
         if self._local():
-            return self.gallery.within(local_probes, tolerance, distance_metric, max_hits)
+            return self.gallery.within(local_probes, tolerance, distance_metric, max_hits, row_tags, probe_masks)
         p, was_np, b = self._begin('within', local_probes)
+        rt, pm = self._tags(row_tags, probe_masks, b)
         K = int(max_hits)
         need = within_gather_bytes(self.world, b, K)
         if need > WITHIN_GATHER_MAX:
@@ -409,32 +414,37 @@ class ShardedGallery:
                              '12) > 2^30: lower max_hits' % (need, self.world, self.world * b, K))
         probes = self.all_gather_embeddings(p)
         B = probes.shape[0]
-        cnt, idx, d = self.gallery.within(probes, tolerance, distance_metric, K)
+        cnt, idx, d = self.gallery.within(probes, tolerance, distance_metric, K, rt, pm)
         gc, gi, gd = _unpack(self._gather(_pack([cnt, idx, d])),
                              [(torch.int64, (B,)), (torch.int64, (B, K)), (torch.float32, (B, K))])
         return self._back(was_np, *merge_within(gc, gi, gd))
 
-    def rank(self, local_probes, mates, distance_metric=1):
+    def rank(self, local_probes, mates, distance_metric=1, row_tags=None, probe_masks=None):
         """oneshot.Gallery.rank over the whole sharded gallery: -> (rank [R*b] int64, mate_dist [R*b] float32), identical on
         every rank and equal to one Gallery holding every row.  `mates` [b] are global indices (any shard's; -1 or an index
         no shard holds: unmated, rank -1).  Two result exchanges, because a shard cannot count against a mate it does not
         hold: the probes and mates; every shard's (owned, mate_dist) -- R records of R*b*12 bytes -- from which every rank
         takes the owner's distance; then every shard's count against that distance -- R records of R*b*8 bytes -- summed
-        (merge_rank)."""
+        (merge_rank).
+        `row_tags` (this shard's) and `probe_masks` (this rank's probes', gathered with them) as in `within`: the rank among
+        the rows each probe is eligible for.  The merge is unchanged: the owning shard reports owned = 1 and a NaN distance
+        for a mate the probe may not see (rank = the size of every shard, summed: len of the whole gallery), and counts over
+        the eligible rows of disjoint shards add."""
         if self._local():
-            return self.gallery.rank(local_probes, mates, distance_metric)
+            return self.gallery.rank(local_probes, mates, distance_metric, row_tags, probe_masks)
         p, was_np, b = self._begin('rank', local_probes)
+        rt, pm = self._tags(row_tags, probe_masks, b)
         m = self._gather(self._ints(mates, 'mates', b)).view(-1)
         probes = self.all_gather_embeddings(p)
         B = probes.shape[0]
         dev = probes.device
         md = torch.empty((B,), dtype=torch.float32, device=dev)
         own = torch.empty((B,), dtype=torch.int64, device=dev)
-        self.gallery.mate_dist_into(probes, m, distance_metric, md, own)
+        self.gallery.mate_dist_into(probes, m, distance_metric, md, own, rt, pm)
         g_own, g_md = _unpack(self._gather(_pack([own, md])), [(torch.int64, (B,)), (torch.float32, (B,))])
         _, dm = merge_rank(torch.zeros_like(g_own), g_own, g_md)        # the owner's distance, on every rank
         cnt = torch.empty((B,), dtype=torch.int64, device=dev)
-        self.gallery.rank_at_into(probes, m, dm, distance_metric, cnt)
+        self.gallery.rank_at_into(probes, m, dm, distance_metric, cnt, rt, pm)
         return self._back(was_np, *merge_rank(self._gather(cnt), g_own, g_md))
 
     def roc(self, local_probes, probe_labels, row_labels, thresholds, distance_metric=1, first_row=None):

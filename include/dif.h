@@ -296,7 +296,7 @@ int64_t dif_gallery_capacity(const dif_gallery* g);
  * "roc_round": 0 (default) dif_match_roc takes as many probes per round as its mask workspace allows (2^24 masks of 16 bytes /
  * the number of 128-row tiles, in whole blocks of 128, at least 128); n > 0, a multiple of 128, makes it n probes when that is
  * fewer.  Same answers for every value (tests: several rounds at a small shape).
- * "within_round": 0 (default) dif_match_within, dif_match_rank and dif_match_rank_at take as many probes per round as the census
+ * "within_round": 0 (default) dif_match_within, dif_match_rank, dif_match_rank_at and their tagged forms take as many probes per round as the census
  * workspace allows (2^27 words / the number of 128-row tiles, in whole blocks of 128, at least 128); n > 0, a multiple of 128,
  * makes it n probes when that is fewer.  Same answers for every value (tests: several rounds at a small shape).
  * "topk_round": 0 (default) dif_match_topk, dif_match_topk_ids and their tagged forms take as many probes per round as the
@@ -315,7 +315,11 @@ int dif_gallery_set_option(dif_gallery* g, const char* key, int value);
  * "topk_ids_tiles": how many (probe, 128-row tile) pairs the last dif_match_topk_ids on `stream` evaluated row by row, over
  * all its probes (synchronises the stream); "topk_tagged_tiles": the same count for the last dif_match_topk_tagged or
  * dif_match_topk_ids_tagged on `stream` -- a tile without a row eligible for the probe is never among them, so with few rows
- * eligible it is about the number of tiles that hold one (synchronises the stream; 0 before the first tagged call). */
+ * eligible it is about the number of tiles that hold one (synchronises the stream; 0 before the first tagged call);
+ * "within_tagged_tiles": the same count for the last dif_match_within_tagged, dif_match_rank_tagged or
+ * dif_match_rank_at_tagged on `stream`: the (probe, 128-row tile) pairs evaluated row by row -- a tile without an eligible row
+ * that could be a hit (resp. closer or tied) is never among them, whatever the probe (synchronises the stream; 0 before the
+ * first such call). */
 int dif_gallery_get_stat(dif_gallery* g, const char* key, int64_t* out, void* stream);
 /* top-1 search of n probes [n][d]: idx_out_dev[n] = np.argmin over the reference's float32 distances
  * (int64 global index; first minimum; a row whose reference distance is NaN ranks first, as in
@@ -633,6 +637,48 @@ int dif_match_mate_dist(dif_gallery* g, const float* probes_dev, int n, int metr
                         float* mate_dist_out_dev /* [n] */, int64_t* owned_out_dev /* [n]: 0 / 1 */, void* stream);
 int dif_match_rank_at(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
                       const float* mate_dist_in_dev /* [n] */, int64_t* count_out_dev /* [n] */, void* stream);
+/* watch-lists on the range search and the rank: dif_match_within, dif_match_rank and the two shard-local halves over the rows
+ * each probe is allowed to see.  row_tags_dev [size] int64 and probe_masks_dev [n] int64 are dif_match_topk_tagged's: the
+ * gallery stores no tags (keep them as row labels are kept, permuted by dif_gallery_remove's moves), and
+ *     eligible[p][r] = (row_tags[r] & probe_masks[p]) != 0         on the raw 64 bits
+ *   A tag of 0 is never eligible, a mask of 0 sees no row.  Per probe q
+ *     d = utility.distance(q[None, :], gallery, metric);  d[~eligible[p]] = NaN
+ *   and the result is the untagged call's for that d:
+ * dif_match_within_tagged: hits = flatnonzero(d <= tolerance): an ineligible row is never counted and never listed -- the
+ *   count and the max_hits lowest hits are those of the eligible rows, however many foreign rows precede them; a mask of 0
+ *   gives count 0 and all padding.
+ * dif_match_rank_tagged: the rank among the rows the probe may see, rank = count(d < dm) + count(d[:m] == dm): ineligible rows
+ *   are never closer and never tie.  An INELIGIBLE mate is a mate whose distance is NaN: rank = dif_gallery_size ("behind every
+ *   row", a miss at every k) and mate_dist NaN -- distinct from an unmated probe (rank -1).
+ * dif_match_mate_dist_tagged: owned as before (the shard holds the row); the distance is NaN where the mate is not eligible.
+ * dif_match_rank_at_tagged: the count over the shard's ELIGIBLE rows; dm NaN gives dif_gallery_size, as before.  The sums of
+ *   dif_shard_merge_within / dif_shard_merge_rank are unchanged: counts over eligible rows add.
+ * Everything else is the untagged calls': the inclusive <=, NaN never a hit, "clamp_nan", index_base, max_hits in
+ *   [0, DIF_WITHIN_MAX_HITS], "within_round", metric 0 bit-identical to the reference, metric 1 up to the arccos.
+ * n = 0 is a no-op; an empty gallery gives counts 0 / every probe unmated (rank_at: 0) and reads neither array; with rows
+ *   enrolled a NULL row_tags_dev or probe_masks_dev fails, as do the untagged calls' own argument errors.
+ * Relations: with every pair eligible (all tags and masks -1) the results are the untagged calls', bit for bit; the tagged
+ *   answer of a probe equals the untagged answer over a gallery of its eligible rows alone, indices (and the mate's row) mapped.
+ * Costs the untagged call's MFMA pass with 8 more bytes read per row: the census counts eligible rows only, so its 16-bit
+ *   word is 0 exactly when the tile holds no eligible row that is SURE or not OUT, and such a tile is never evaluated row by
+ *   row -- also for a probe outside the bound's validity, whose census counts every eligible row as borderline.  Within an
+ *   evaluated tile an ineligible row is skipped before any arithmetic.  dif_gallery_get_stat "within_tagged_tiles" counts the
+ *   tiles evaluated (dif_match_mate_dist_tagged evaluates none and leaves it alone).  No host synchronisation in steady state;
+ *   shares the untagged calls' workspace plus one 8-byte counter.  The untagged entries run the kernels they ran before. */
+int dif_match_within_tagged(dif_gallery* g, const float* probes_dev, int n, int metric, float tolerance, int max_hits,
+                            const int64_t* row_tags_dev /* [size] */, const int64_t* probe_masks_dev /* [n] */,
+                            int64_t* count_out_dev /* [n] */, int64_t* idx_out_dev /* [n][max_hits] */,
+                            float* dist_out_dev /* [n][max_hits] */, void* stream);
+int dif_match_rank_tagged(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
+                          const int64_t* row_tags_dev /* [size] */, const int64_t* probe_masks_dev /* [n] */,
+                          int64_t* rank_out_dev /* [n] */, float* mate_dist_out_dev /* [n], or NULL */, void* stream);
+int dif_match_mate_dist_tagged(dif_gallery* g, const float* probes_dev, int n, int metric,
+                               const int64_t* mate_idx_dev /* [n] */, const int64_t* row_tags_dev /* [size] */,
+                               const int64_t* probe_masks_dev /* [n] */, float* mate_dist_out_dev /* [n] */,
+                               int64_t* owned_out_dev /* [n]: 0 / 1 */, void* stream);
+int dif_match_rank_at_tagged(dif_gallery* g, const float* probes_dev, int n, int metric, const int64_t* mate_idx_dev /* [n] */,
+                             const float* mate_dist_in_dev /* [n] */, const int64_t* row_tags_dev /* [size] */,
+                             const int64_t* probe_masks_dev /* [n] */, int64_t* count_out_dev /* [n] */, void* stream);
 
 /* ------------------------------------------------------------------ embedding network
  * Stands behind the Keras model object of the reference:
