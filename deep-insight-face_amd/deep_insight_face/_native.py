@@ -72,6 +72,9 @@ SIGNATURES = {
     'dif_tracks_link': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_int, c_int, c_int, c_int64,
                                 c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p, c_int64, c_int, c_void_p]),
+    'dif_frames_redact_workspace_size': (c_int64, [c_int64, c_int]),
+    'dif_frames_redact': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                  c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'dif_gallery_create': (c_int, [P(c_void_p), c_int]),
     'dif_gallery_destroy': (c_int, [c_void_p]),
     'dif_gallery_set': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),

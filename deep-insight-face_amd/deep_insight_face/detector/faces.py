@@ -188,6 +188,18 @@ class FrameFaces(typing.NamedTuple):
         finally:
             shots.close()
 
+    def redact(self, frames, select=None, mode: str = 'pixelate', cells: int = 8, min_cell: int = 4, margin: float = 0.0,
+               shape: str = 'box', fill=(0, 0, 0), out=None):
+        """The frames these faces came from with the faces hidden, on the device (``redact.redact_frames``;
+        ``dif_frames_redact``, where the rule is written out): ``frames`` uint8 [N, H, W, 3] -> ``out`` (``frames.clone()``
+        unless given; ``out=frames`` works in place).  ``select`` [M] bool or uint8 picks the faces to hide, ``None`` hides
+        all: ``faces.redact(frames, select=faces.dist > tol)`` hides everyone the gallery does not know.  ``mode``:
+        'pixelate' (``cells`` x ``cells`` means over the box grown by ``margin`` of its size), 'smooth' (the same means
+        interpolated: no block edges) or 'fill'; ``shape`` 'box' or 'ellipse'.  Where faces overlap, the lowest row (the best
+        face) is what shows; every value comes from ``frames``.  Nothing is read back."""
+        from . import redact
+        return redact.redact_frames(frames, self.offsets, self.boxes, select, mode, cells, min_cell, margin, shape, fill, out)
+
     def templates(self, labels, weighted=False, normalize: bool = True):
         """One template per person of the batch: the embeddings pooled by ``labels`` [M] (what ``cluster`` or ``dbscan``
         returned; a negative label -- noise -- leaves the face out) -> (templates [T, d] float32, template_labels [T] int64

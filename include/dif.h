@@ -984,6 +984,73 @@ int dif_tracks_link(const int64_t* offsets_dev /* [n_frames + 1] */, const float
                     int64_t* clipped_out_dev /* [1] */, void* state_out_dev /* or NULL */, int state_k_out,
                     void* workspace_dev, int64_t workspace_bytes, int passes, void* stream);
 
+/* ------------------------------------------------------------------ redaction (csrc/redact.hip)
+ * The faces of a batch of frames hidden in the frames themselves, on the device: filled, pixelated or smoothed
+ * (deep_insight_face.detector.redact: redact_frames; FrameFaces.redact).  Not in the reference, whose detector/run.py only
+ * crops.  tests/redact_ref.py restates the rule in NumPy, bit for bit.  All arithmetic on pixels is integer and exact; the
+ * box arithmetic is float32, every product and every sum rounded on its own (no contraction).
+ * Inputs: frames_dev uint8 [n][h][w][3], 1 <= h, w <= DIF_REDACT_MAX_SIDE; offsets_dev int64 [n + 1], the CSR offsets of the
+ *   faces per frame, ascending from 0 to m (read on the device only; whatever they hold, no row outside [0, m) and no frame
+ *   outside [0, n) is touched, and a row that no frame covers is left out); boxes_dev float [m][4] left, top, right, bottom
+ *   in frame pixels; select_dev uint8 [m] or NULL = every face, non-zero = redact; mode 0 (fill), 1 (pixelate), 2 (smooth);
+ *   shape 0 (box), 1 (ellipse); cells in [1, DIF_REDACT_MAX_CELLS]; min_cell in [1, DIF_REDACT_MAX_SIDE]; margin float32,
+ *   finite; fill three bytes ON THE HOST, one per channel.
+ * Region of face i, from its box (l, t, r, b):
+ *    1. bw = r - l; bh = b - t.
+ *    2. any of l, t, r, b not finite, or !(bw > 0), or !(bh > 0): the face has no region.
+ *    3. le = l - margin*bw; re = r + margin*bw; te = t - margin*bh; be = b + margin*bh.
+ *    4. any of the four not finite, or !(re > le), or !(be > te): no region.
+ *    5. each of the four is clamped to [-4096, 12288].
+ *    6. X0 = floor(le), X1 = ceil(re), Y0 = floor(te), Y1 = ceil(be).
+ *    7. X1 <= X0 or Y1 <= Y0: no region.
+ *    8. the unclipped region is [X0, X1) x [Y0, Y1), Rw x Rh pixels; both sides are at most 16384.
+ *    9. the clipped region is its intersection with the frame [0, w) x [0, h);
+ *   10. empty: no region.
+ * Cells: c = max(ceil(max(Rw, Rh) / cells), min_cell) in integers; pixel (x, y) of the unclipped region lies in cell
+ *   ((x - X0) / c, (y - Y0) / c): the grid is anchored at the UNCLIPPED corner, and both indices are below `cells`.  Without
+ *   min_cell a face narrower than `cells` pixels would get c = 1 and leave untouched; min_cell = 1 keeps the plain rule.
+ * Cell mean, per channel and per cell that meets the frame: S and k = the sum and the count of the SOURCE pixels of
+ *   the cell inside the frame -- pixels outside the shape and pixels under other faces count like any other --, v = (2 S + k) / (2 k)
+ *   in integers: the mean rounded half up.  S reaches 255 * 2^26: the sums are 64-bit.
+ * Shape: box covers every pixel of the clipped region; ellipse covers the pixel at dx = x - X0, dy = y - Y0 iff
+ *   Rh^2 (2 dx + 1 - Rw)^2 + Rw^2 (2 dy + 1 - Rh)^2 <= Rw^2 Rh^2 in int64 (every term below 2^57).  A 4 x 4 region covers all
+ *   but its four corners; a side of one pixel is covered.
+ * Value of a covered pixel:
+ *   fill      the three bytes of `fill`.
+ *   pixelate  its cell's mean.
+ *   smooth    the bilinear interpolation of the rounded cell means between cell centres, in integers:
+ *               a = 2 dx + 1 - c;  i0 = floor(a / 2c);  fa = a - 2c i0 in [0, 2c);  b, j0, fb likewise from dy
+ *               i0, i1 = i0 + 1, j0, j1 = j0 + 1 are clamped to the cells that meet the frame: from the cell of the clipped
+ *               region's first pixel to the cell of its last pixel, per axis
+ *               V = (2c - fa)(2c - fb) v[j0][i0] + fa (2c - fb) v[j0][i1] + (2c - fa) fb v[j1][i0] + fa fb v[j1][i1]
+ *               value = (V + 2 c^2) / (4 c^2);  V reaches 255 * 2^30: 64-bit.
+ *             It hides exactly what pixelate hides -- cells^2 means -- without the block edges, and needs nothing but the
+ *             means; a windowed blur would read neighbours that another block is writing.
+ * Overlap: a pixel that several selected faces of its frame cover takes the value of the LOWEST row among them (rows are
+ *   best first inside a frame).  Every value comes from the source frames, so the result depends on neither launch nor
+ *   thread order, and every output byte has one writer.  An unselected face is never a reason to write a pixel; its pixels
+ *   under a selected face's region are redacted all the same.
+ * out_dev uint8 [n][h][w][3] receives the values of the covered pixels; every other byte of it is left as it was.  out_dev ==
+ *   frames_dev (in place) is allowed in every mode and gives the bytes of the out-of-place call on a copy; an out that
+ *   overlaps the frames in part fails.
+ * Two stream-ordered launches, both sized from m and cells alone: pass 1 writes the means of every (face, cell) that has
+ *   pixels into the workspace (skipped in mode 0), pass 2 paints from the workspace and the boxes and reads no frame.  A cell's
+ *   sum is split over up to 16 waves whose partial sums are added in wave order.  Nothing is read back, no atomics.
+ * workspace_dev: dif_frames_redact_workspace_size(m, cells) = m * cells * cells * 4 bytes of the caller's, aligned to 4
+ *   bytes; contents need not be kept between calls, and calls that share a workspace must be ordered on one stream.
+ * n = 0 or m = 0 launches nothing.  Fails before any launch on: h or w outside [1, DIF_REDACT_MAX_SIDE], cells, min_cell,
+ *   mode or shape outside their ranges, a margin that is not finite, negative sizes, n above 2^31 - 1 or m * cells above
+ *   2^31 - 1, a NULL pointer where one is needed (select_dev may be NULL), a workspace that is too small or misaligned, an
+ *   out that overlaps the frames in part.  dif_frames_redact_workspace_size returns -1 on such arguments. */
+#define DIF_REDACT_MAX_CELLS 64
+#define DIF_REDACT_MAX_SIDE 8192
+int64_t dif_frames_redact_workspace_size(int64_t m, int cells);
+int dif_frames_redact(const uint8_t* frames_dev /* [n][h][w][3] */, int64_t n, int h, int w,
+                      const int64_t* offsets_dev /* [n + 1] */, const float* boxes_dev /* [m][4] */, int64_t m,
+                      const uint8_t* select_dev /* [m], or NULL */, int mode, int shape, int cells, int min_cell, float margin,
+                      const uint8_t* fill /* [3], host */, uint8_t* out_dev /* [n][h][w][3] */, void* workspace_dev,
+                      int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ ArcMargin logits
  * Not in the reference (north_star only; ArcFace, Deng et al. 2019):
  * logits = s * cos(theta + m * onehot(label)); labels_dev NULL -> s * cos(theta). */
