@@ -17,6 +17,7 @@
 // No atomics, one writer per output byte, nothing read back.
 #include "../../include/dif.h"
 #include "dif_internal.hpp"
+#include "frame_region.hpp"
 
 namespace dif {
 
@@ -26,38 +27,15 @@ constexpr int kPaintThreads = 256;
 constexpr int kPaintWaves = kPaintThreads / 64;
 constexpr int kListFaces = kPaintThreads;        // lower faces of the frame that one pass of the block can list
 
-struct RedactRegion {                            // the unclipped region [X0, X1) x [Y0, Y1)
-  int X0, Y0, X1, Y1;
-};
-
 struct RedactFace {
-  RedactRegion g;
+  FrameRegion g;
   int cx0, cy0, cx1, cy1;                        // the clipped region
   int c;                                         // side of a cell
   long long frame, first;                        // the face's frame and that frame's first row
 };
 
-__device__ __forceinline__ bool redact_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }   // false for NaN
-__device__ __forceinline__ float redact_clamp(float v) { return __builtin_fminf(__builtin_fmaxf(v, -4096.0f), 12288.0f); }
-
-// steps 1 to 8 of the rule
-__device__ bool redact_region(const float* __restrict__ box, float margin, RedactRegion* out) {
-#pragma clang fp contract(off)
-  const float l = box[0], t = box[1], r = box[2], b = box[3];
-  const float bw = r - l, bh = b - t;
-  if (!(redact_finite(l) && redact_finite(t) && redact_finite(r) && redact_finite(b)) || !(bw > 0.0f) || !(bh > 0.0f)) return false;
-  const float mw = margin * bw, mh = margin * bh;
-  const float le = l - mw, re = r + mw, te = t - mh, be = b + mh;
-  if (!(redact_finite(le) && redact_finite(re) && redact_finite(te) && redact_finite(be)) || !(re > le) || !(be > te)) return false;
-  out->X0 = (int)__builtin_floorf(redact_clamp(le));
-  out->X1 = (int)__builtin_ceilf(redact_clamp(re));
-  out->Y0 = (int)__builtin_floorf(redact_clamp(te));
-  out->Y1 = (int)__builtin_ceilf(redact_clamp(be));
-  return out->X1 > out->X0 && out->Y1 > out->Y0;
-}
-
 // is pixel (x, y) of the frame covered by the face of region g?
-__device__ __forceinline__ bool redact_covers(const RedactRegion& g, int shape, int x, int y) {
+__device__ __forceinline__ bool redact_covers(const FrameRegion& g, int shape, int x, int y) {
   if (x < g.X0 || x >= g.X1 || y < g.Y0 || y >= g.Y1) return false;
   if (shape == 0) return true;
   const long long rw = g.X1 - g.X0, rh = g.Y1 - g.Y0;
@@ -71,23 +49,9 @@ __device__ bool redact_face(long long i, long long n, long long m, int h, int w,
                             RedactFace* face) {
   if (select && !select[i]) return false;
   if (i < offsets[0] || i >= offsets[n]) return false;       // a row that no frame covers
-  // offsets[lo] <= i < offsets[hi], narrowed 64-fold per step: every lane looks at one of 64 evenly spaced entries and the
-  // wave counts the lanes at or below i (ascending offsets make them a prefix).  A chain of ceil(log64 n) loads instead of
-  // log2 n; whatever offsets hold, lo and hi stay inside [0, n] and the span shrinks to 1.
-  const int lane = threadIdx.x & 63;
-  long long lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const long long step = (hi - lo + 63) / 64, at = lo + lane * step;
-    const int below = __popcll(__ballot(at < hi && offsets[at] <= i));
-    const long long next = lo + (below > 0 ? below - 1 : 0) * step;
-    hi = next + step < hi ? next + step : hi;
-    lo = next;
-  }
-  face->frame = lo;
-  const long long first = offsets[lo];
-  face->first = first < 0 ? 0 : (first > i ? i : first);
-  if (!redact_region(boxes + 4 * i, margin, &face->g)) return false;
-  const RedactRegion& g = face->g;
+  frame_of_row(i, n, offsets, &face->frame, &face->first);   // the 64-way search
+  if (!frame_region(boxes + 4 * i, margin, &face->g)) return false;
+  const FrameRegion& g = face->g;
   face->cx0 = g.X0 > 0 ? g.X0 : 0;
   face->cy0 = g.Y0 > 0 ? g.Y0 : 0;
   face->cx1 = g.X1 < w ? g.X1 : w;
@@ -183,14 +147,14 @@ __global__ __launch_bounds__(kPaintThreads) void redact_paint_kernel(unsigned ch
                                                                      const unsigned char* __restrict__ select, int mode, int shape, int cells,
                                                                      int min_cell, float margin, unsigned fill,
                                                                      const unsigned* __restrict__ means) {
-  __shared__ RedactRegion listed[kListFaces];
+  __shared__ FrameRegion listed[kListFaces];
   __shared__ int wave_hits[kPaintWaves];
   const long long i = blockIdx.x / (unsigned)cells;
   const int j = (int)(blockIdx.x % (unsigned)cells);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   RedactFace face;
   if (!redact_face(i, n, m, h, w, offsets, boxes, select, cells, min_cell, margin, &face)) return;
-  const RedactRegion g = face.g;
+  const FrameRegion g = face.g;
   const int c = face.c;
   const int top = g.Y0 + j * c;
   const int y0 = top > face.cy0 ? top : face.cy0, y1 = top + c < face.cy1 ? top + c : face.cy1;
@@ -201,10 +165,10 @@ __global__ __launch_bounds__(kPaintThreads) void redact_paint_kernel(unsigned ch
   int n_listed = 0;
   if (use_list) {
     bool hit = false;
-    RedactRegion q;
+    FrameRegion q;
     if (tid < lower) {
       const long long r = face.first + tid;
-      if ((!select || select[r]) && redact_region(boxes + 4 * r, margin, &q))
+      if ((!select || select[r]) && frame_region(boxes + 4 * r, margin, &q))
         hit = q.X0 < face.cx1 && q.X1 > face.cx0 && q.Y0 < y1 && q.Y1 > y0;
     }
     const unsigned long long votes = __ballot(hit);
@@ -244,8 +208,8 @@ __global__ __launch_bounds__(kPaintThreads) void redact_paint_kernel(unsigned ch
         for (int e = 0; e < n_listed && !taken; ++e) taken = redact_covers(listed[e], shape, x, y);
       } else {
         for (long long r = face.first; r < i && !taken; ++r) {
-          RedactRegion q;
-          taken = (!select || select[r]) && redact_region(boxes + 4 * r, margin, &q) && redact_covers(q, shape, x, y);
+          FrameRegion q;
+          taken = (!select || select[r]) && frame_region(boxes + 4 * r, margin, &q) && redact_covers(q, shape, x, y);
         }
       }
       if (taken) continue;

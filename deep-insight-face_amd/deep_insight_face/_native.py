@@ -75,6 +75,10 @@ SIGNATURES = {
     'dif_frames_redact_workspace_size': (c_int64, [c_int64, c_int]),
     'dif_frames_redact': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'dif_annotate_glyph': (c_int, [c_int, c_void_p]),
+    'dif_annotate_compose': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_int64, c_void_p, c_int, c_void_p]),
+    'dif_frames_annotate': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
     'dif_gallery_create': (c_int, [P(c_void_p), c_int]),
     'dif_gallery_destroy': (c_int, [c_void_p]),
     'dif_gallery_set': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),

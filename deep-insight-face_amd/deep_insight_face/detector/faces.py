@@ -200,6 +200,26 @@ class FrameFaces(typing.NamedTuple):
         from . import redact
         return redact.redact_frames(frames, self.offsets, self.boxes, select, mode, cells, min_cell, margin, shape, fill, out)
 
+    def annotate(self, frames, names=None, known=None, values=None, text=None, colors=None, select=None, decimals: int = 2,
+                 unknown: str = '?', length: int = 32, margin: float = 0.0, thickness: int = 2, scale: int = 2, mark: int = 1,
+                 out=None):
+        """The frames these faces came from with the faces marked, on the device (``annotate.annotate_frames``;
+        ``dif_frames_annotate``, where the rule is written out): ``frames`` uint8 [N, H, W, 3] -> ``out`` (``frames.clone()``
+        unless given; ``out=frames`` paints in place) with a ring round every selected face, a square on each of its
+        landmarks and a plate with its label.  The label is ``text`` uint8 [M, L] if given; otherwise, with ``names`` (an
+        ``annotate.NameTable`` over the gallery's rows) or ``values`` given, it is composed on the device from ``idx``
+        (``annotate.compose_text``): the name where ``known`` holds, ``unknown`` elsewhere, then the value -- ``faces.annotate(
+        frames, names=table, known=faces.dist <= tol, values=faces.dist, colors=annotate.palette(tracks.labels))``.  With
+        none of the three there are no plates.  It composes with redaction: ``faces.annotate(faces.redact(frames,
+        select=faces.dist > tol), ...)``.  Nothing is read back."""
+        from . import annotate
+        if text is None and (names is not None or values is not None):
+            if names is not None and self.idx is None:
+                raise ValueError('FrameFaces.annotate with names needs the gallery rows (a pipeline\'s faces() with a gallery)')
+            text = annotate.compose_text(names, self.idx if names is not None else None, known, values, decimals, unknown, length)
+        return annotate.annotate_frames(frames, self.offsets, self.boxes, self.landmarks, text, colors, select, margin, thickness, scale,
+                                        mark, out)
+
     def templates(self, labels, weighted=False, normalize: bool = True):
         """One template per person of the batch: the embeddings pooled by ``labels`` [M] (what ``cluster`` or ``dbscan``
         returned; a negative label -- noise -- leaves the face out) -> (templates [T, d] float32, template_labels [T] int64

@@ -1051,6 +1051,80 @@ int dif_frames_redact(const uint8_t* frames_dev /* [n][h][w][3] */, int64_t n, i
                       const uint8_t* fill /* [3], host */, uint8_t* out_dev /* [n][h][w][3] */, void* workspace_dev,
                       int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ annotation (csrc/annotate.hip)
+ * The opposite picture to redaction: a ring round every face of a batch of frames, a filled plate with its label next to
+ * it and a square on every landmark, painted into the frames on the device (deep_insight_face.detector.annotate:
+ * compose_text, NameTable, annotate_frames, palette; FrameFaces.annotate).  The reference draws with OpenCV on the host
+ * (detector/utility.py draw_boxes, detector/yolov3.py draw, api.py show_plot); nothing of OpenCV's rasterisation or of its
+ * Hershey font is restated here -- parity with cv2.rectangle / cv2.putText is unpinned.  tests/annotate_ref.py restates both
+ * rules below in NumPy, bit for bit.  The paint is opaque: no pixel is read, nothing is blended.
+ *
+ * dif_annotate_compose: the label of every face, written on the device.
+ * Inputs: names_dev uint8 [g][ln], one NUL-padded name per gallery row, or NULL; idx_dev int64 [m], the gallery row of each
+ *   face, or NULL; known_dev uint8 [m], non-zero = the face is known, or NULL = every face is; values_dev float32 [m], the
+ *   value to print after the name, or NULL; decimals in [0, 4]; unknown, a string ON THE HOST of at most
+ *   DIF_ANNOTATE_MAX_TEXT bytes, which may be empty; text_dev uint8 [m][l], the output, 1 <= l <= DIF_ANNOTATE_MAX_TEXT.
+ * Row i:
+ *   base   names and idx given, the face known and 0 <= idx[i] < g: the bytes of names[idx[i]] up to its first NUL or ln.
+ *          Otherwise: the bytes of unknown.
+ *   value  values given: one space if the base is not empty, then the number.  A NaN prints as "nan".  Otherwise
+ *          a = min(|v|, 99999) in float32; c = (int64) floor((double) a * 10^decimals + 0.5), one float64 product and one
+ *          sum; '-' if v < 0 and c > 0; c / 10^decimals in decimal; with decimals > 0 a '.' and c % 10^decimals padded with
+ *          zeros to `decimals` digits.  (At two decimals 0.125 prints 0.13, -0.004 prints 0.00 and infinity 99999.00; the float32
+ *          nearest to 0.005 is 0.00499999989 and prints 0.00, the least float32 not below 0.005 prints 0.01.)
+ *   cut    the result is cut at l bytes and padded with NUL; a text of l bytes has no NUL.
+ * One thread per row.  m = 0 launches nothing.  Fails before any launch on: decimals or l outside their ranges, unknown NULL
+ *   or too long, m negative or above 2^31 - 1, names_dev given with g < 0 or ln < 1, text_dev NULL.
+ *
+ * dif_frames_annotate: the drawing.
+ * Inputs: out_dev uint8 [n][h][w][3], 1 <= h, w <= DIF_REDACT_MAX_SIDE, the frames, painted in place (there is no source:
+ *   out of place is a copy first); offsets_dev, boxes_dev, select_dev and margin as dif_frames_redact takes them -- whatever
+ *   offsets hold, no row outside [0, m) and no frame outside [0, n) is touched, and a row that no frame covers is left out;
+ *   landmarks_dev float [m][5][2] (x, y) or NULL; text_dev uint8 [m][l] or NULL, 1 <= l <= DIF_ANNOTATE_MAX_TEXT (l is not
+ *   looked at without text); colors_dev uint8 [m][3] or NULL = the three bytes `color` ON THE HOST for every face;
+ *   thickness t in [0, DIF_ANNOTATE_MAX_THICKNESS]; scale s in [1, DIF_ANNOTATE_MAX_SCALE]; mark r in
+ *   [-1, DIF_ANNOTATE_MAX_MARK], -1 = no marks.
+ * What face i paints, in its colour C:
+ *   box     [X0, X1) x [Y0, Y1) from steps 1 to 8 of the redaction rule with the same margin.  A face without a region there
+ *           paints nothing at all; a region wholly outside the frame may still paint, its ring or plate can reach in.
+ *   ring    the pixels of [X0 - t, X1 + t) x [Y0 - t, Y1 + t) outside the box: round the face, never over it.
+ *   plate   only with len > 0, len = the bytes of text[i] before the first NUL, at most l.  Tw = (6 len - 1) s, Th = 7 s,
+ *           Pw = Tw + 2 s, Ph = 9 s.  PX0 = X0 - t; if PX0 + Pw > w then PX0 = w - Pw; if PX0 < 0 then PX0 = 0.
+ *           PY0 = Y0 - t - Ph; if PY0 < 0 then PY0 = Y1 + t: no room above puts the plate below the box.
+ *           The plate is [PX0, PX0 + Pw) x [PY0, PY0 + Ph).
+ *   glyphs  (u, v) = (x - PX0 - s, y - PY0 - s) inside [0, Tw) x [0, Th): character k = u / (6 s), column (u % (6 s)) / s,
+ *           row v / s.  Column 5 is the gap between characters; otherwise the pixel is a text pixel iff bit 4 - column of
+ *           that row of the glyph of byte text[i][k] is set.  Text pixels are black if 299 R + 587 G + 114 B >= 128000 for
+ *           C = (R, G, B), else white.
+ *   font    5 x 7, drawn for this project (csrc/font5x7.hpp): printable ASCII 0x20 .. 0x7E, any other byte shows a glyph
+ *           with every pixel set.  dif_annotate_glyph(code, rows) writes the seven rows of the glyph of byte `code`, top
+ *           first, bit 4 = the left column (a host call; code outside 0x20 .. 0x7E gives the all-set glyph).
+ *   marks   with r >= 0, for each of the five landmarks whose two coordinates are finite: both are clamped to
+ *           [-4096, 12288]; mx = floor(px + 0.5f) in float32, my likewise; the mark is [mx - r, mx + r] x [my - r, my + r].
+ *   Inside one face the plate with its glyphs comes first, then the marks, then the ring.
+ * Between faces: a pixel that several selected faces of its frame paint takes the paint of the LOWEST row among them (best
+ *   first), as in redaction.  What a lower face takes is its whole footprint: its ring, its whole plate -- opaque whether or
+ *   not a pixel is a text pixel -- and its marks; never the inside of its box.  An unselected face paints nothing and shields
+ *   nothing.  Every output byte has at most one writer, so the result depends on neither launch nor thread order.
+ * One launch of a fixed number of blocks per face.  Nothing is read back, no atomics; every loop is bounded by h, w, l or two
+ *   values of offsets.  n = 0 or m = 0 launches nothing.  Fails before any launch on: h or w outside
+ *   [1, DIF_REDACT_MAX_SIDE], thickness, scale or mark outside their ranges, a margin that is not finite, text_dev given
+ *   with l outside its range, negative sizes, n above 2^31 - 1 or 4 m above 2^31 - 1, out_dev, offsets_dev or boxes_dev NULL,
+ *   colors_dev and color both NULL. */
+#define DIF_ANNOTATE_MAX_TEXT 64
+#define DIF_ANNOTATE_MAX_THICKNESS 64
+#define DIF_ANNOTATE_MAX_SCALE 8
+#define DIF_ANNOTATE_MAX_MARK 16
+int dif_annotate_glyph(int code, uint8_t* rows /* [7], host */);
+int dif_annotate_compose(const uint8_t* names_dev /* [g][ln], or NULL */, int64_t g, int ln, const int64_t* idx_dev /* [m], or NULL */,
+                         const uint8_t* known_dev /* [m], or NULL */, const float* values_dev /* [m], or NULL */, int decimals,
+                         const char* unknown /* host */, int64_t m, uint8_t* text_dev /* [m][l] */, int l, void* stream);
+int dif_frames_annotate(uint8_t* out_dev /* [n][h][w][3] */, int64_t n, int h, int w, const int64_t* offsets_dev /* [n + 1] */,
+                        const float* boxes_dev /* [m][4] */, int64_t m, const float* landmarks_dev /* [m][5][2], or NULL */,
+                        const uint8_t* text_dev /* [m][l], or NULL */, int l, const uint8_t* colors_dev /* [m][3], or NULL */,
+                        const uint8_t* color /* [3], host */, const uint8_t* select_dev /* [m], or NULL */, float margin,
+                        int thickness, int scale, int mark, void* stream);
+
 /* ------------------------------------------------------------------ ArcMargin logits
  * Not in the reference (north_star only; ArcFace, Deng et al. 2019):
  * logits = s * cos(theta + m * onehot(label)); labels_dev NULL -> s * cos(theta). */
