@@ -79,6 +79,13 @@ SIGNATURES = {
     'dif_annotate_compose': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_int64, c_void_p, c_int, c_void_p]),
     'dif_frames_annotate': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
+    'dif_box_overlap': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'dif_det_workspace_size': (c_int64, [c_int64, c_int64, c_int]),
+    'dif_det_match': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, P(c_double), c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'dif_det_curve': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_int64, c_void_p]),
+    'dif_det_ap': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     'dif_gallery_create': (c_int, [P(c_void_p), c_int]),
     'dif_gallery_destroy': (c_int, [c_void_p]),
     'dif_gallery_set': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),

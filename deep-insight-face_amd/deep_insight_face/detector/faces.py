@@ -220,6 +220,16 @@ class FrameFaces(typing.NamedTuple):
         return annotate.annotate_frames(frames, self.offsets, self.boxes, self.landmarks, text, colors, select, margin, thickness, scale,
                                         mark, out)
 
+    def evaluate(self, gt_boxes, gt_offsets, iou_thresholds=(0.5,), gt_ignore=None):
+        """These detections against the labelled boxes of the same N frames, on the device (``evaluation.detection.
+        evaluate_detections``; ``dif_det_match``, where the rule is written out): ``gt_boxes`` [T, 4] left, top, right,
+        bottom with ``gt_offsets`` [N + 1] as a CSR list over the frames, ``gt_ignore`` [T] bool for truths that count for
+        nobody -> a ``DetectionEval``: per face the truth it overlaps most, its float64 IoU and its outcome at each IoU
+        threshold, and the precision / recall curve and average precision of the batch.  ``M == 0`` and ``T == 0`` work; over
+        many batches use ``evaluation.detection.DetectionEvaluator``.  Nothing is read back."""
+        from ..evaluation import detection
+        return detection.evaluate_detections(self.boxes, self.scores, self.offsets, gt_boxes, gt_offsets, iou_thresholds, gt_ignore)
+
     def templates(self, labels, weighted=False, normalize: bool = True):
         """One template per person of the batch: the embeddings pooled by ``labels`` [M] (what ``cluster`` or ``dbscan``
         returned; a negative label -- noise -- leaves the face out) -> (templates [T, d] float32, template_labels [T] int64

@@ -1125,6 +1125,78 @@ int dif_frames_annotate(uint8_t* out_dev /* [n][h][w][3] */, int64_t n, int h, i
                         const uint8_t* color /* [3], host */, const uint8_t* select_dev /* [m], or NULL */, float margin,
                         int thickness, int scale, int mark, void* stream);
 
+/* ------------------------------------------------------------------ detector evaluation (csrc/deteval.hip)
+ * The detections of a detector matched to labelled boxes, and the precision / recall curve and average precision of all
+ * of them, on the device (deep_insight_face.detector.utility: compute_overlap, compute_ap; deep_insight_face.evaluation.
+ * detection: evaluate_detections, DetectionEvaluator; FrameFaces.evaluate).  The reference ships the two primitives,
+ * detector/utility.py:281-306 compute_overlap and :309-334 compute_ap (py-faster-rcnn); the rule around them is that of their
+ * consumers (keras-retinanet / keras-yolo3 `evaluate`) with Pascal VOC's "difficult" flags.  tests/detection_ref.py restates
+ * it in NumPy as the sequential loop.  Parity with the WIDER FACE devkit's own protocol is unpinned.
+ *
+ * dif_box_overlap: out[i][c] = compute_overlap(a, b)[i][c] in float64 on the float32 coordinates (left, top, right, bottom)
+ *   widened to float64, the reference's operations in its order -- area_b = (b2 - b0) * (b3 - b1); iw = min(a2, b2) -
+ *   max(a0, b0); ih = min(a3, b3) - max(a1, b1); both clamped below at 0; ua = (a2 - a0) * (a3 - a1) + area_b - iw * ih,
+ *   clamped below at DBL_EPSILON; iw * ih / ua; no +1, no fused multiply-add -- so the reference's value bit for bit.
+ *   Deviation: a pair with a coordinate that is not finite has overlap 0 (the reference: NaN).
+ *
+ * dif_det_match: one batch of whole frames.
+ * Inputs: det_offsets_dev int64 [n_frames + 1] and gt_offsets_dev int64 [n_frames + 1], the exclusive prefix sums of the
+ *   detections and of the truths per frame; det_boxes_dev float [m][4], det_scores_dev float [m], in any order inside a
+ *   frame; gt_boxes_dev float [t][4]; gt_ignore_dev uint8 [t], non-zero = an ignored truth, or NULL = none is; thr_host,
+ *   j IoU thresholds as doubles ON THE HOST, 1 <= j <= DIF_DET_MAX_THRESHOLDS, each in (0, 1].  Whatever the offsets hold,
+ *   no row outside [0, m) or [0, t) is touched; a detection that no frame covers has no truth.
+ * Outputs: assigned_out_dev int32 [m]: the first maximum (np.argmax: the lowest row) of the detection's overlaps with the
+ *   truths of its frame, as a row of gt_boxes, -1 in a frame without truths; iou_out_dev double [m]: that maximum, 0
+ *   without one; outcome_out_dev uint8 [j][m]; n_truth_out_dev int64 [1]: the truths that are not ignored.
+ * Outcome at threshold thr[j], a frame's detections walked by descending score -- ties to the lower row, NaN last, that is
+ *   np.argsort(-scores, kind='stable'):
+ *     assigned < 0 or iou < thr[j]      DIF_DET_FP       (iou == thr[j] is a hit)
+ *     else the truth is ignored         DIF_DET_DROPPED  neither true nor false positive; it takes nothing
+ *     else the truth is not yet taken   DIF_DET_TP       and the truth is taken
+ *     else                              DIF_DET_FP       a detection never falls through to its second-best truth
+ *
+ * dif_det_curve: all detections seen, whatever batches they came in.
+ * Inputs: scores_dev float [m]; outcome_dev uint8 [j][m] as dif_det_match wrote it (batches concatenated along m);
+ *   n_truth_dev int64 [1] ON THE DEVICE, the sum over the batches.
+ * Outputs: order_out_dev int64 [m]: the rows by descending score (the order above, over all m); tp_cum_out_dev and
+ *   fp_cum_out_dev int64 [j][m]: the inclusive counts of outcomes DIF_DET_TP / DIF_DET_FP in that order; recall_out_dev
+ *   double [j][m] = tp_cum / n_truth, 0 with n_truth = 0; precision_out_dev double [j][m] = tp_cum / max(tp_cum + fp_cum,
+ *   DBL_EPSILON), one float64 division each; ap_out_dev double [j] = compute_ap of the two curves (dif_det_ap).  m = 0
+ *   writes ap = 0 and nothing else.  The order of a batch restricted to a frame is the order of all rows restricted to it,
+ *   so batches of any sizes give the bits of one call.
+ *
+ * dif_det_ap: out_dev double [1] = compute_ap(recall, precision) of m points, double each: with the sentinels (0, 0) in front
+ *   and (1, 0) behind, the envelope -- the running maximum of the precision from the right, a NaN taken over as np.maximum
+ *   does -- and the sum of (recall[i] - recall[i - 1]) * envelope[i] over the i where the recall changes.  The terms are summed
+ *   in a fixed order -- per tile of DIF_DET_SCAN_TILE points a fixed tree, the tiles last to first -- so equal curves give
+ *   equal bits; NumPy sums pairwise, and the two orders differ by at most (number of terms) * 2^-52 on a curve whose recall
+ *   ends at or below 1.  dif_det_curve's ap has the bits of dif_det_ap on its own curves.
+ *
+ * workspace_dev: dif_det_workspace_size(m, t, j) bytes of the caller's, aligned to 8 (dif_det_curve: t = 0).  Nothing is read
+ *   back to the host and no block waits for another; the only atomics are an integer minimum and an integer sum.  Every
+ *   output is a function of the inputs alone.  Fails before any launch on: sizes negative or above DIF_DET_MAX_ROWS, j or a
+ *   threshold outside its range, rows without a frame, a NULL pointer that is needed, a workspace too small. */
+#define DIF_DET_MAX_THRESHOLDS 16
+#define DIF_DET_MAX_ROWS 0x7fff0000
+#define DIF_DET_SCAN_TILE 1024
+#define DIF_DET_FP 0
+#define DIF_DET_TP 1
+#define DIF_DET_DROPPED 2
+int dif_box_overlap(const float* a_dev /* [n][4] */, int64_t n, const float* b_dev /* [k][4] */, int64_t k, double* out_dev /* [n][k] */,
+                    void* stream);
+int64_t dif_det_workspace_size(int64_t m, int64_t t, int j);
+int dif_det_match(const int64_t* det_offsets_dev /* [n_frames + 1] */, const float* det_boxes_dev /* [m][4] */,
+                  const float* det_scores_dev /* [m] */, int64_t m, const int64_t* gt_offsets_dev /* [n_frames + 1] */,
+                  const float* gt_boxes_dev /* [t][4] */, const uint8_t* gt_ignore_dev /* [t], or NULL */, int64_t t, int64_t n_frames,
+                  const double* thr_host /* [j] */, int j, int32_t* assigned_out_dev /* [m] */, double* iou_out_dev /* [m] */,
+                  uint8_t* outcome_out_dev /* [j][m] */, int64_t* n_truth_out_dev /* [1] */, void* workspace_dev, int64_t workspace_bytes,
+                  void* stream);
+int dif_det_curve(const float* scores_dev /* [m] */, const uint8_t* outcome_dev /* [j][m] */, const int64_t* n_truth_dev /* [1] */, int64_t m,
+                  int j, int64_t* order_out_dev /* [m] */, int64_t* tp_cum_out_dev /* [j][m] */, int64_t* fp_cum_out_dev /* [j][m] */,
+                  double* recall_out_dev /* [j][m] */, double* precision_out_dev /* [j][m] */, double* ap_out_dev /* [j] */,
+                  void* workspace_dev, int64_t workspace_bytes, void* stream);
+int dif_det_ap(const double* recall_dev /* [m] */, const double* precision_dev /* [m] */, int64_t m, double* out_dev /* [1] */, void* stream);
+
 /* ------------------------------------------------------------------ ArcMargin logits
  * Not in the reference (north_star only; ArcFace, Deng et al. 2019):
  * logits = s * cos(theta + m * onehot(label)); labels_dev NULL -> s * cos(theta). */
