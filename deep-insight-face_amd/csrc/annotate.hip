@@ -19,7 +19,7 @@
 #include "../../include/dif.h"
 #include "dif_internal.hpp"
 #include "font5x7.hpp"
-#include "frame_region.hpp"
+#include "frame_rows.hpp"
 
 namespace dif {
 
@@ -27,9 +27,9 @@ constexpr int kAnnThreads = 256;
 constexpr int kAnnWaves = kAnnThreads / 64;
 constexpr int kAnnMaxBands = 4;                  // most blocks per face
 // Blocks of annotate_paint_kernel that an MI355X holds at once, which ann_bands fills and no more: 256 CUs x kAnnBlocksPerCu.
-// Six per CU is the kernel's occupancy in DESIGN 4y's table (79 VGPRs: six waves per SIMD; its 24 KB of LDS allow six blocks
-// too).  If -Rpass-analysis=kernel-resource-usage reports another occupancy for the kernel, this constant and that table move
-// with it; only the speed depends on it, never a byte of the output.
+// Six per CU is the kernel's occupancy in profiles/frame_shared_resource_usage.txt: its 24 KB of LDS allow six blocks (its 49
+// VGPRs would allow more).  If -Rpass-analysis=kernel-resource-usage reports another occupancy for the kernel, this constant
+// and that table move with it; only the speed depends on it, never a byte of the output.
 constexpr int kAnnBlocksPerCu = 6;
 constexpr int kAnnResident = 256 * kAnnBlocksPerCu;
 constexpr int kAnnListFaces = kAnnThreads;       // lower faces of the frame that one pass of the block can list
@@ -186,26 +186,15 @@ __global__ __launch_bounds__(kAnnThreads) void annotate_paint_kernel(unsigned ch
   // the selected faces of lower rows of the frame: listed once when one pass of the block covers them
   const long long lower = i - first;
   const bool use_list = lower <= kAnnListFaces;
+  auto lower_face = [&](long long r, AnnFoot* q) {
+    return (!select || select[r]) && ann_foot(r, boxes, landmarks, text, l, margin, t, s, mark, w, q);
+  };
   int n_listed = 0;
-  if (use_list) {
-    bool hit = false;
-    AnnFoot q;
-    if (tid < lower) {
-      const long long r = first + tid;
-      if ((!select || select[r]) && ann_foot(r, boxes, landmarks, text, l, margin, t, s, mark, w, &q))
-        hit = q.bound.x0 < cx1 && q.bound.x1 > cx0 && q.bound.y0 < y1 && q.bound.y1 > y0;
-    }
-    const unsigned long long votes = __ballot(hit);
-    if (lane == 0) wave_hits[wave] = __popcll(votes);
-    __syncthreads();
-    int before = 0;
-#pragma unroll
-    for (int v = 0; v < kAnnWaves; ++v) {
-      if (v < wave) before += wave_hits[v];
-      n_listed += wave_hits[v];
-    }
-    if (hit) listed[before + __popcll(votes & ((1ull << lane) - 1ull))] = q;
-  }
+  if (use_list)
+    n_listed = frame_list_lower<kAnnWaves>(tid, lane, wave, lower, first, [&](long long r, AnnFoot* q) {
+      return lower_face(r, q) && q->bound.x0 < cx1 && q->bound.x1 > cx0 && q->bound.y0 < y1 && q->bound.y1 > y0;
+    }, listed, wave_hits);
+  // (the glyph rows go to LDS between the list and the barrier that closes both)
 #pragma unroll
   for (int k = 0; k < 2; ++k)
     if (tid + k * kAnnThreads < me.len * 7) glyph_rows[tid + k * kAnnThreads] = (unsigned char)glyph_row[k];
@@ -225,15 +214,9 @@ __global__ __launch_bounds__(kAnnThreads) void annotate_paint_kernel(unsigned ch
       const int y = ry0 + (int)(p / rw), x = rx0 + (int)(p % rw);
       bool taken = e > 0 && ann_in(mine.plate, x, y);        // a higher element of the face itself
       for (int k = 0; k < marks_before && !taken; ++k) taken = ann_in_mark(mine.mx[k], mine.my[k], mark, x, y);
-      if (use_list) {
-        for (int k = 0; k < n_listed && !taken; ++k) taken = ann_covers(listed[k], t, mark, x, y);
-      } else {
-        for (long long r = first; r < i && !taken; ++r) {
-          AnnFoot f;
-          taken = (!select || select[r]) && ann_foot(r, boxes, landmarks, text, l, margin, t, s, mark, w, &f) && ann_covers(f, t, mark, x, y);
-        }
-      }
-      if (taken) continue;
+      if (taken || frame_lower_covers(use_list, listed, n_listed, first, i, lower_face,
+                                      [&](const AnnFoot& f) { return ann_covers(f, t, mark, x, y); }))
+        continue;
       unsigned v = paint;
       if (e == 0) {
         const int gu = x - q.x0 - s, gv = y - q.y0 - s;

@@ -1,11 +1,13 @@
 // hipcc-flags: -ffp-contract=fast-honor-pragmas
-// (build.py compiles with -ffp-contract=fast, which disregards `#pragma clang fp contract(off)`; box_iou below needs it)
+// (build.py compiles with -ffp-contract=fast, which disregards `#pragma clang fp contract(off)`; box_iou.hpp needs it.
+// Everything else in this file contracts as before.)
 // YOLOv3-face post-processing on the device: the box decode of
 // deep_insight_face/detector/yolov3.py:36-106 (yolo_head, correct_boxes, boxes_and_scores) and
 // the per-class score filter + greedy non-max suppression of :122-172 (get_yolo_output, which
 // calls tf.image.non_max_suppression).  Memory-bound / tiny: one thread per anchor box for the
 // decode, one block per (image, class) for the suppression.
 #include "../../include/dif.h"
+#include "box_iou.hpp"
 #include "dif_internal.hpp"
 
 namespace dif {
@@ -62,22 +64,6 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const YoloArgs a) {
     o[3] = (cx + ww / 2.f) * iw;
     for (int c = 0; c < a.C; ++c) a.scores[i * a.C + c] = conf * sigmoidf(f[5 + c]);   // boxes_and_scores :104
   }
-}
-
-// IoU with the corner normalisation of tf.image.non_max_suppression, every product rounded to float32 before it is added:
-// contracted, the union became fma(-ih, iw, ap + aq), one rounding fewer than the float32 statement the tests compare
-// with, and an IoU that lands exactly on the threshold was suppressed.  The pragma holds because this file is compiled with
-// -ffp-contract=fast-honor-pragmas (first line); everything else in it contracts as before.
-__device__ __forceinline__ float box_iou(const float* p, const float* q) {
-#pragma clang fp contract(off)
-  const float py0 = fminf(p[0], p[2]), py1 = fmaxf(p[0], p[2]), px0 = fminf(p[1], p[3]), px1 = fmaxf(p[1], p[3]);
-  const float qy0 = fminf(q[0], q[2]), qy1 = fmaxf(q[0], q[2]), qx0 = fminf(q[1], q[3]), qx1 = fmaxf(q[1], q[3]);
-  const float ap = (py1 - py0) * (px1 - px0), aq = (qy1 - qy0) * (qx1 - qx0);
-  if (ap <= 0.f || aq <= 0.f) return 0.f;
-  const float ih = fmaxf(fminf(py1, qy1) - fmaxf(py0, qy0), 0.f);
-  const float iw = fmaxf(fminf(px1, qx1) - fmaxf(px0, qx0), 0.f);
-  const float inter = ih * iw;
-  return inter / (ap + aq - inter);
 }
 
 // One block per (image, class).  Greedy: pick the best remaining score (ties: lower index, the

@@ -22,10 +22,8 @@
 //   det_overlap_kernel    one thread per pair (dif_box_overlap)
 //   det_best_kernel       one thread per detection over the truths of its frame; a block whose detections share a frame
 //                         stages that frame's truths through LDS, kDetGtChunk at a time
-//   det_keys_kernel       } a stable LSD radix sort of (monotone uint32 key of the score, row) in four 8-bit passes, the
-//   det_hist_kernel       } passes of csrc/templates.hip restated for 32-bit keys: a histogram per block of kDetSortTile
-//   det_hist_scan_kernel  } keys, an exclusive scan over [digit][block] by one block, and a scatter that ranks a key among
-//   det_scatter_kernel    } the equal digits in front of it in its block (ballots in a wave, counters across the waves)
+//   det_keys_kernel       (monotone uint32 key of the score, row) pairs, which the stable LSD radix sort of
+//                         csrc/radix_sort.hip orders in four 8-bit passes (radix_sort_run without a plan)
 //   det_truth_kernel      claim <- none, n_truth
 //   det_claim_kernel, det_classify_kernel    the outcome rule above
 //   det_count_kernel      } the J scans in reduce / scan / apply form: per tile of kDetScanTile ranks the counts, one wave
@@ -41,15 +39,13 @@
 // minimum of the claim and the integer sum of n_truth; every output is a function of the input alone.
 #include "../../include/dif.h"
 #include "dif_internal.hpp"
+#include "frame_rows.hpp"
 
 namespace dif {
 
 constexpr int kDetThreads = 256;
 constexpr int kDetWaves = kDetThreads / 64;
 constexpr int kDetGtChunk = 256;                            // truths of a frame in LDS at a time: one per thread
-constexpr int kDetSortItems = 8;                            // keys per thread and pass
-constexpr int kDetSortTile = kDetThreads * kDetSortItems;   // keys per block and pass
-constexpr int kDetHistScanThreads = 1024;
 constexpr int kDetScanItems = 4;                            // ranks per thread: thread t holds ranks [4 t, 4 t + 4) of its tile
 constexpr int kDetScanTile = DIF_DET_SCAN_TILE;
 static_assert(kDetScanTile == kDetThreads * kDetScanItems, "DIF_DET_SCAN_TILE");
@@ -95,25 +91,6 @@ __global__ __launch_bounds__(kDetThreads) void det_overlap_kernel(const float* _
   out[i] = fa && fb ? det_overlap(qa, qb) : 0.0;
 }
 
-// the frame of row d: the last f in [0, n) with off[f] <= d (off[0] = 0; n >= 1)
-__device__ __forceinline__ int64_t det_frame_of(const int64_t* __restrict__ off, int64_t n, int64_t d) {
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (off[mid] <= d) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// rows [begin, end) of frame f, whatever `off` holds: never outside [0, total]
-__device__ __forceinline__ void det_frame_rows(const int64_t* __restrict__ off, int64_t f, int64_t total, int64_t* begin, int64_t* end) {
-  int64_t b = off[f], e = off[f + 1];
-  b = b < 0 ? 0 : (b > total ? total : b);
-  e = e < b ? b : (e > total ? total : e);
-  *begin = b;
-  *end = e;
-}
-
 __global__ __launch_bounds__(kDetThreads) void det_best_kernel(const int64_t* __restrict__ doff, const int64_t* __restrict__ goff, int64_t n,
                                                                const float* __restrict__ dbox, int64_t m, const float* __restrict__ gbox,
                                                                int64_t t, int* __restrict__ assigned, double* __restrict__ iou) {
@@ -123,12 +100,12 @@ __global__ __launch_bounds__(kDetThreads) void det_best_kernel(const int64_t* __
   const int64_t d0 = (int64_t)blockIdx.x * kDetThreads, d = d0 + tid;
   const bool live = d < m;
   const int64_t dd = live ? d : m - 1;          // a thread past the end walks with the last row and writes nothing
-  const int64_t f = det_frame_of(doff, n, dd);
+  const int64_t f = frame_bisect(doff, n, dd);
   int64_t b, e, gb = 0, ge = 0;
-  det_frame_rows(doff, f, m, &b, &e);
+  frame_rows(doff, f, m, &b, &e);
   const bool in = dd >= b && dd < e;            // (false only when offsets is no prefix sum: the row is in no frame)
-  if (in) det_frame_rows(goff, f, t, &gb, &ge);
-  const int64_t f0 = det_frame_of(doff, n, d0);
+  if (in) frame_rows(goff, f, t, &gb, &ge);
+  const int64_t f0 = frame_bisect(doff, n, d0);
   const int shared = __syncthreads_and(in && f == f0);     // the block's detections share a frame: gb, ge are uniform
   double a[4];
   const bool fa = det_load_box(dbox + dd * 4, a);
@@ -170,108 +147,6 @@ __global__ __launch_bounds__(kDetThreads) void det_keys_kernel(const float* __re
   const unsigned mono = u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);     // ascending with the score
   keys[i] = s != s ? 0xffffffffu : ~mono;       // (~mono = 0xffffffff takes a NaN's bits: no number shares the key)
   pos[i] = (int)i;
-}
-
-__global__ __launch_bounds__(kDetThreads) void det_hist_kernel(const unsigned* __restrict__ keys, int shift, int m, int nb,
-                                                               unsigned* __restrict__ hist) {
-  __shared__ unsigned h[256];
-  const int tid = threadIdx.x;
-  h[tid] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kDetSortTile;
-#pragma unroll
-  for (int r = 0; r < kDetSortItems; ++r) {
-    const int64_t i = base + r * kDetThreads + tid;
-    if (i < m) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  hist[(int64_t)tid * nb + blockIdx.x] = h[tid];
-}
-
-// exclusive scan of data[0 .. E) in place, by ONE block: a thread sums a contiguous share, the shares are scanned across
-// the block, and the thread rewrites its share
-__global__ __launch_bounds__(kDetHistScanThreads) void det_hist_scan_kernel(unsigned* __restrict__ data, int64_t E) {
-  __shared__ unsigned wave_total[kDetHistScanThreads / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t per = (E + kDetHistScanThreads - 1) / kDetHistScanThreads;
-  const int64_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
-  unsigned s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += data[i];
-  unsigned inc = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned v = __shfl_up(inc, off);
-    if (lane >= off) inc += v;
-  }
-  if (lane == 63) wave_total[wave] = inc;
-  __syncthreads();
-  unsigned run = inc - s;
-  for (int w = 0; w < wave; ++w) run += wave_total[w];
-  for (int64_t i = lo; i < hi; ++i) {
-    const unsigned v = data[i];
-    data[i] = run;
-    run += v;
-  }
-}
-
-// Key i of the block's tile goes to hist[digit][block] (keys with a smaller digit, and keys with this digit in the blocks
-// in front) + the keys with this digit in front of it in the tile.  Tile order: wave w holds keys [w * 512, (w + 1) * 512)
-// of the tile, round r of the wave keys [r * 64, (r + 1) * 64) of those, lane by lane.
-__global__ __launch_bounds__(kDetThreads) void det_scatter_kernel(const unsigned* __restrict__ kin, const int* __restrict__ pin,
-                                                                  unsigned* __restrict__ kout, int* __restrict__ pout, int shift, int m, int nb,
-                                                                  const unsigned* __restrict__ hist) {
-  __shared__ unsigned cnt[kDetWaves][256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int w = 0; w < kDetWaves; ++w) cnt[w][tid] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kDetSortTile + wave * (kDetSortItems * 64);
-  unsigned key[kDetSortItems];
-  int p[kDetSortItems];
-  unsigned off[kDetSortItems];
-#pragma unroll
-  for (int r = 0; r < kDetSortItems; ++r) {
-    const int64_t i = base + r * 64 + lane;
-    const bool valid = i < m;
-    key[r] = valid ? kin[i] : 0u;
-    p[r] = valid ? pin[i] : 0;
-    const unsigned dg = (key[r] >> shift) & 255u;
-    unsigned long long same = __ballot(valid);  // the valid lanes of the wave that hold this lane's digit
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const bool one = (dg >> bit) & 1u;
-      const unsigned long long bal = __ballot(one);
-      same &= one ? bal : ~bal;
-    }
-    const unsigned long long below = same & ((1ull << lane) - 1ull);
-    off[r] = valid ? cnt[wave][dg] + (unsigned)__popcll(below) : 0u;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    if (valid && below == 0ull) cnt[wave][dg] += (unsigned)__popcll(same);   // one lane per digit: distinct addresses
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  __syncthreads();
-  {
-    unsigned run = hist[(int64_t)tid * nb + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < kDetWaves; ++w) {
-      const unsigned c = cnt[w][tid];
-      cnt[w][tid] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kDetSortItems; ++r) {
-    const int64_t i = base + r * 64 + lane;
-    if (i < m) {
-      const unsigned dst = cnt[wave][(key[r] >> shift) & 255u] + off[r];
-      kout[dst] = key[r];
-      pout[dst] = p[r];
-    }
-  }
 }
 
 // the sorted rows -> rank_out[row] = rank (dif_det_match) and / or order_out[rank] = row (dif_det_curve)
@@ -549,8 +424,6 @@ __global__ __launch_bounds__(kDetThreads) void det_ap_kernel(const double* __res
 
 using namespace dif;
 
-static size_t det_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 struct DetWork {
   unsigned *k0, *k1, *hist;
   int *p0, *p1, *rank, *claim;
@@ -561,25 +434,19 @@ struct DetWork {
 static int64_t det_blocks(int64_t items, int per) { return (items + per - 1) / per; }
 
 static size_t det_carve(void* base, int64_t m, int64_t t, int J, DetWork* w) {
-  char* q = (char*)base;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    char* p = q + at;
-    at += det_align(bytes);
-    return (void*)p;
-  };
-  const size_t nb = (size_t)det_blocks(m, kDetSortTile), nt = (size_t)det_blocks(m, kDetScanTile);
-  w->k0 = (unsigned*)take((size_t)m * 4);
-  w->k1 = (unsigned*)take((size_t)m * 4);
-  w->p0 = (int*)take((size_t)m * 4);
-  w->p1 = (int*)take((size_t)m * 4);
-  w->hist = (unsigned*)take(256 * nb * 4);
-  w->rank = (int*)take((size_t)m * 4);
-  w->claim = (int*)take((size_t)J * (size_t)t * 4);
-  w->part = (int64_t*)take((size_t)J * nt * 16);
-  w->tmax = (double*)take((size_t)J * nt * 8);
-  w->tsum = (double*)take((size_t)J * nt * 8);
-  return at;
+  Carver c(base);
+  const size_t nt = (size_t)det_blocks(m, kDetScanTile);
+  w->k0 = (unsigned*)c.take((size_t)m * 4);
+  w->k1 = (unsigned*)c.take((size_t)m * 4);
+  w->p0 = (int*)c.take((size_t)m * 4);
+  w->p1 = (int*)c.take((size_t)m * 4);
+  w->hist = (unsigned*)c.take(radix_sort_hist_bytes(m));
+  w->rank = (int*)c.take((size_t)m * 4);
+  w->claim = (int*)c.take((size_t)J * (size_t)t * 4);
+  w->part = (int64_t*)c.take((size_t)J * nt * 16);
+  w->tmax = (double*)c.take((size_t)J * nt * 8);
+  w->tsum = (double*)c.take((size_t)J * nt * 8);
+  return c.at;
 }
 
 static int det_check_sizes(const char* fn, int64_t m, int64_t t, int J) {
@@ -591,19 +458,8 @@ static int det_check_sizes(const char* fn, int64_t m, int64_t t, int J) {
 
 // the rows of scores[0 .. m) in order -> w.p0 (m > 0)
 static int det_sort(const float* scores_dev, int64_t m, const DetWork& w, hipStream_t st) {
-  const int nb = (int)det_blocks(m, kDetSortTile);
   hipLaunchKernelGGL(det_keys_kernel, dim3((unsigned)det_blocks(m, kDetThreads)), dim3(kDetThreads), 0, st, scores_dev, (int)m, w.k0, w.p0);
-  for (int pass = 0; pass < 4; ++pass) {
-    const unsigned* kin = pass & 1 ? w.k1 : w.k0;
-    unsigned* kout = pass & 1 ? w.k0 : w.k1;
-    const int* pin = pass & 1 ? w.p1 : w.p0;
-    int* pout = pass & 1 ? w.p0 : w.p1;
-    hipLaunchKernelGGL(det_hist_kernel, dim3(nb), dim3(kDetThreads), 0, st, kin, 8 * pass, (int)m, nb, w.hist);
-    hipLaunchKernelGGL(det_hist_scan_kernel, dim3(1), dim3(kDetHistScanThreads), 0, st, w.hist, (int64_t)256 * nb);
-    hipLaunchKernelGGL(det_scatter_kernel, dim3(nb), dim3(kDetThreads), 0, st, kin, pin, kout, pout, 8 * pass, (int)m, nb, w.hist);
-  }
-  DIF_HIP(hipGetLastError());
-  return 0;                                     // (four passes: the sorted pairs are back in k0 / p0)
+  return radix_sort_run<unsigned>(nullptr, 4, w.k0, w.k1, w.p0, w.p1, m, w.hist, st);   // (four passes: the sorted pairs are back in k0 / p0)
 }
 
 extern "C" {

@@ -136,6 +136,32 @@ int pairwise_run(const float* e1, int64_t n1, const float* e2, int64_t n2, int D
 int match_merge_run(const void* keys, int64_t key_pitch, const void* idx, int64_t idx_pitch, const void* dist,
                     int64_t dist_pitch, int R, int B, int64_t* idx_out, float* dist_out, hipStream_t st);   // pitches in bytes
 
+// csrc/radix_sort.hip: the stable LSD radix sort of (key, position) pairs on 8-bit digits, K = unsigned or unsigned long long.
+// The plan of a sort whose skipped passes are known on the device alone:
+struct RadixPlan {
+  int active[8], src[8];   // per pass: does it run, and which of the two buffers holds its input
+  int final_buf, pad;      // the buffer that holds the sorted pairs
+};
+constexpr int kRadixSortTile = 2048;         // keys per block and pass (radix_sort.hip: kSortThreads * kSortItems)
+int radix_sort_tile();                       // ... for a caller that sizes its blocks at run time
+size_t radix_sort_hist_bytes(int64_t m);     // the [256][blocks] histogram of a pass over m keys
+// enqueues passes 0 .. passes - 1 over (k0, p0) / (k1, p1).  plan_dev null: every pass runs, pass b reads buffer b & 1
+template <typename K>
+int radix_sort_run(const RadixPlan* plan_dev, int passes, K* k0, K* k1, int* p0, int* p1, int64_t m, unsigned* hist, hipStream_t st);
+int block_scan_run(unsigned* data, int64_t E, hipStream_t st);   // the sort's scan on its own: exclusive, in place, by one block
+
+// One allocation shared out in steps of 256 bytes.  With a null base take() returns null and `at` still counts: the size.
+struct Carver {
+  char* base;
+  size_t at = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  void* take(size_t bytes) {
+    char* q = base ? base + at : nullptr;
+    at += (bytes + 255) & ~(size_t)255;
+    return q;
+  }
+};
+
 // csrc/match_shard.hip: merges of R per-shard results laid out [R][n][...]
 int shard_merge_lists_run(bool by_dist, const int64_t* count, const int64_t* idx, const float* dist, int R, int n, int L,
                           int64_t* count_out, int64_t* idx_out, float* dist_out, hipStream_t st);

@@ -17,7 +17,7 @@
 // No atomics, one writer per output byte, nothing read back.
 #include "../../include/dif.h"
 #include "dif_internal.hpp"
-#include "frame_region.hpp"
+#include "frame_rows.hpp"
 
 namespace dif {
 
@@ -162,25 +162,12 @@ __global__ __launch_bounds__(kPaintThreads) void redact_paint_kernel(unsigned ch
   // the selected faces of lower rows of the frame: listed once when one pass of the block covers them
   const long long lower = i - face.first;
   const bool use_list = lower <= kListFaces;
+  auto lower_face = [&](long long r, FrameRegion* q) { return (!select || select[r]) && frame_region(boxes + 4 * r, margin, q); };
   int n_listed = 0;
   if (use_list) {
-    bool hit = false;
-    FrameRegion q;
-    if (tid < lower) {
-      const long long r = face.first + tid;
-      if ((!select || select[r]) && frame_region(boxes + 4 * r, margin, &q))
-        hit = q.X0 < face.cx1 && q.X1 > face.cx0 && q.Y0 < y1 && q.Y1 > y0;
-    }
-    const unsigned long long votes = __ballot(hit);
-    if (lane == 0) wave_hits[wave] = __popcll(votes);
-    __syncthreads();
-    int before = 0;
-#pragma unroll
-    for (int v = 0; v < kPaintWaves; ++v) {
-      if (v < wave) before += wave_hits[v];
-      n_listed += wave_hits[v];
-    }
-    if (hit) listed[before + __popcll(votes & ((1ull << lane) - 1ull))] = q;
+    n_listed = frame_list_lower<kPaintWaves>(tid, lane, wave, lower, face.first, [&](long long r, FrameRegion* q) {
+      return lower_face(r, q) && q->X0 < face.cx1 && q->X1 > face.cx0 && q->Y0 < y1 && q->Y1 > y0;
+    }, listed, wave_hits);
     __syncthreads();
   }
   unsigned char* __restrict__ dst = out + (size_t)face.frame * (size_t)h * (size_t)w * 3;
@@ -203,16 +190,9 @@ __global__ __launch_bounds__(kPaintThreads) void redact_paint_kernel(unsigned ch
     }
     for (int x = face.cx0 + lane; x < face.cx1; x += 64) {
       if (!redact_covers(g, shape, x, y)) continue;
-      bool taken = false;
-      if (use_list) {
-        for (int e = 0; e < n_listed && !taken; ++e) taken = redact_covers(listed[e], shape, x, y);
-      } else {
-        for (long long r = face.first; r < i && !taken; ++r) {
-          FrameRegion q;
-          taken = (!select || select[r]) && frame_region(boxes + 4 * r, margin, &q) && redact_covers(q, shape, x, y);
-        }
-      }
-      if (taken) continue;
+      if (frame_lower_covers(use_list, listed, n_listed, face.first, i, lower_face,
+                             [&](const FrameRegion& q) { return redact_covers(q, shape, x, y); }))
+        continue;
       const int dx = x - g.X0;
       unsigned v;
       if (mode == 0) {

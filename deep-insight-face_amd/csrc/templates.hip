@@ -6,19 +6,17 @@
 //                                  varies, a byte without such a bit is constant and its sort pass is skipped
 //           pool_init_kernel       (key, position) pairs -- the t0 state labels in front of the n new ones, every negative
 //                                  label mapped to ONE key above all others -- and the plan of the eight passes
-//           pool_hist_kernel       } one stable LSD radix pass on an 8-bit digit: a histogram per block of kSortTile keys,
-//           pool_scan_kernel       } an exclusive scan over [digit][block] by one block, and a scatter that ranks every
-//           pool_scatter_kernel    } key among the equal digits in front of it in its block (ballots inside a wave, per-wave
-//                                  counters across the waves).  All eight passes are enqueued; a skipped one returns at
-//                                  once, and which of the two buffers a pass reads is part of the plan in device memory
-//           pool_heads_kernel      segment heads per block of kHeadBlock sorted keys (pool_scan_kernel scans them)
+//           radix_sort_run         the stable LSD radix sort of csrc/radix_sort.hip under that plan.  All eight passes are
+//                                  enqueued; a skipped one returns at once, and which of the two buffers a pass reads is
+//                                  part of the plan in device memory
+//           pool_heads_kernel      segment heads per block of kHeadBlock sorted keys (block_scan_run scans them)
 //           pool_index_kernel      template number of every key -> index_out, the start of every segment, T
 //   reduce  pool_reduce_kernel     one thread per (segment, float4 column): the segment's rows in sorted -- that is, row --
 //                                  order into ONE accumulator, the loads of kLookAhead rows issued in front of their
 //                                  adds and their positions a chunk earlier
 //   best    pool_best_kernel       one thread per segment: the row with the greatest key, in the segment's order (best shot)
 //   finish  pool_finish_kernel     one wave per template: sums / divisor, and the row's norm in NumPy's order (np_sum)
-// The only atomics are the ORs of pool_stats_kernel and LDS counters whose totals do not depend on the order; every
+// The only atomics are the ORs of pool_stats_kernel and the sort's LDS counters, whose totals do not depend on the order; every
 // output is a function of the input alone.
 #include "../../include/dif.h"
 #include "match_ref.hpp"
@@ -26,11 +24,11 @@
 
 namespace dif {
 
+// The tile of the sort's passes, restated from csrc/radix_sort.hip where the tests of this file's sizes read it
+// (tests/test_templates_gpu.py); the assertion keeps the two from drifting apart.
 constexpr int kSortThreads = 256;
-constexpr int kSortWaves = kSortThreads / 64;
-constexpr int kSortItems = 8;                               // keys per thread and pass
-constexpr int kSortTile = kSortThreads * kSortItems;        // keys per block and pass
-constexpr int kScanThreads = 1024;
+constexpr int kSortItems = 8;
+static_assert(kSortThreads * kSortItems == kRadixSortTile, "the sort's tile: csrc/radix_sort.hip");
 constexpr int kHeadBlock = 256;                             // sorted keys per block of pool_heads_kernel / pool_index_kernel
 constexpr int kLookAhead = 16;                              // rows of a segment in flight in pool_reduce_kernel
 constexpr unsigned long long kNegBit = 1ull << 63;
@@ -38,8 +36,7 @@ constexpr unsigned long long kNegBit = 1ull << 63;
 struct PoolMeta {
   unsigned long long or_all, nor_all;   // OR of the non-negative labels, OR of their complements
   int any_neg, any_nonneg;
-  int active[8], src[8];                // per pass: does it run, and which buffer holds its input
-  int final_buf, pad;                   // the buffer that holds the sorted pairs
+  RadixPlan sort;                       // the eight passes: pool_init_kernel writes it, radix_sort_run follows it
   long long T;                          // templates after the group
 };
 
@@ -94,125 +91,11 @@ __global__ __launch_bounds__(256) void pool_init_kernel(const int64_t* __restric
     int buf = 0;
     for (int b = 0; b < 8; ++b) {
       const int on = ((varies >> (8 * b)) & 0xff) != 0;
-      meta->active[b] = on;
-      meta->src[b] = buf;
+      meta->sort.active[b] = on;
+      meta->sort.src[b] = buf;
       buf ^= on;
     }
-    meta->final_buf = buf;
-  }
-}
-
-__global__ __launch_bounds__(kSortThreads) void pool_hist_kernel(const PoolMeta* __restrict__ meta, int b,
-                                                                 const unsigned long long* __restrict__ k0,
-                                                                 const unsigned long long* __restrict__ k1, int m, int nb,
-                                                                 unsigned* __restrict__ hist) {
-  if (!meta->active[b]) return;
-  const unsigned long long* __restrict__ keys = meta->src[b] ? k1 : k0;
-  __shared__ unsigned h[256];
-  const int tid = threadIdx.x;
-  h[tid] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kSortTile;
-#pragma unroll
-  for (int r = 0; r < kSortItems; ++r) {
-    const int64_t i = base + r * kSortThreads + tid;
-    if (i < m) atomicAdd(&h[(unsigned)(keys[i] >> (8 * b)) & 255u], 1u);
-  }
-  __syncthreads();
-  hist[(int64_t)tid * nb + blockIdx.x] = h[tid];
-}
-
-// exclusive scan of data[0 .. E) in place, by ONE block: a thread sums a contiguous share, the shares are scanned across
-// the block, and the thread rewrites its share.  `active` (or null): a skipped pass has nothing to scan.
-__global__ __launch_bounds__(kScanThreads) void pool_scan_kernel(const int* __restrict__ active, unsigned* __restrict__ data, int E) {
-  if (active && !*active) return;
-  __shared__ unsigned wave_total[kScanThreads / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t per = ((int64_t)E + kScanThreads - 1) / kScanThreads;
-  const int64_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
-  unsigned s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += data[i];
-  unsigned inc = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned v = __shfl_up(inc, off);
-    if (lane >= off) inc += v;
-  }
-  if (lane == 63) wave_total[wave] = inc;
-  __syncthreads();
-  unsigned run = inc - s;
-  for (int w = 0; w < wave; ++w) run += wave_total[w];
-  for (int64_t i = lo; i < hi; ++i) {
-    const unsigned v = data[i];
-    data[i] = run;
-    run += v;
-  }
-}
-
-// Key i of the block's tile goes to hist[digit][block] (keys with a smaller digit, and keys with this digit in the blocks
-// in front) + the keys with this digit in front of it in the tile.  Tile order: wave w holds keys [w * 512, (w + 1) * 512)
-// of the tile, round r of the wave keys [r * 64, (r + 1) * 64) of those, lane by lane.
-__global__ __launch_bounds__(kSortThreads) void pool_scatter_kernel(const PoolMeta* __restrict__ meta, int b, unsigned long long* __restrict__ k0,
-                                                                    unsigned long long* __restrict__ k1, int* __restrict__ p0,
-                                                                    int* __restrict__ p1, int m, int nb,
-                                                                    const unsigned* __restrict__ hist) {
-  if (!meta->active[b]) return;
-  const int src = meta->src[b];
-  const unsigned long long* kin = src ? k1 : k0;
-  unsigned long long* kout = src ? k0 : k1;
-  const int* pin = src ? p1 : p0;
-  int* pout = src ? p0 : p1;
-  __shared__ unsigned cnt[kSortWaves][256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int w = 0; w < kSortWaves; ++w) cnt[w][tid] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + wave * (kSortItems * 64);
-  unsigned long long key[kSortItems];
-  int p[kSortItems];
-  unsigned off[kSortItems];
-#pragma unroll
-  for (int r = 0; r < kSortItems; ++r) {
-    const int64_t i = base + r * 64 + lane;
-    const bool valid = i < m;
-    key[r] = valid ? kin[i] : 0ull;
-    p[r] = valid ? pin[i] : 0;
-    const unsigned dg = (unsigned)(key[r] >> (8 * b)) & 255u;
-    unsigned long long same = __ballot(valid);       // the valid lanes of the wave that hold this lane's digit
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const bool one = (dg >> bit) & 1u;
-      const unsigned long long bal = __ballot(one);
-      same &= one ? bal : ~bal;
-    }
-    const unsigned long long below = same & ((1ull << lane) - 1ull);
-    off[r] = valid ? cnt[wave][dg] + (unsigned)__popcll(below) : 0u;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    if (valid && below == 0ull) cnt[wave][dg] += (unsigned)__popcll(same);   // one lane per digit: distinct addresses
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  __syncthreads();
-  {
-    unsigned run = hist[(int64_t)tid * nb + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) {
-      const unsigned c = cnt[w][tid];
-      cnt[w][tid] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kSortItems; ++r) {
-    const int64_t i = base + r * 64 + lane;
-    if (i < m) {
-      const unsigned dst = cnt[wave][(unsigned)(key[r] >> (8 * b)) & 255u] + off[r];
-      kout[dst] = key[r];
-      pout[dst] = p[r];
-    }
+    meta->sort.final_buf = buf;
   }
 }
 
@@ -226,7 +109,7 @@ __device__ __forceinline__ bool pool_is_head(const unsigned long long* __restric
 __global__ __launch_bounds__(kHeadBlock) void pool_heads_kernel(const PoolMeta* __restrict__ meta, const unsigned long long* __restrict__ k0,
                                                                 const unsigned long long* __restrict__ k1, int m,
                                                                 unsigned* __restrict__ block_heads) {
-  const unsigned long long* __restrict__ keys = meta->final_buf ? k1 : k0;
+  const unsigned long long* __restrict__ keys = meta->sort.final_buf ? k1 : k0;
   __shared__ int wave_total[kHeadBlock / 64];
   const int tid = threadIdx.x;
   const unsigned long long mask = __ballot(pool_is_head(keys, (int64_t)blockIdx.x * kHeadBlock + tid, m));
@@ -247,7 +130,7 @@ __global__ __launch_bounds__(kHeadBlock) void pool_index_kernel(PoolMeta* __rest
                                                                 const int* __restrict__ p1, int m, int t0,
                                                                 const unsigned* __restrict__ block_heads, int* __restrict__ seg_start,
                                                                 int64_t* __restrict__ index_out, int64_t* __restrict__ t_out) {
-  const int fin = meta->final_buf;
+  const int fin = meta->sort.final_buf;
   const unsigned long long* __restrict__ keys = fin ? k1 : k0;
   const int* __restrict__ pos = fin ? p1 : p0;
   __shared__ int wave_total[kHeadBlock / 64];
@@ -288,7 +171,7 @@ __global__ __launch_bounds__(256) void pool_reduce_kernel(const PoolMeta* __rest
   const int64_t seg = gid / q;
   const int c = (int)(gid - seg * q);
   if (seg >= t) return;
-  const int fin = meta->final_buf;
+  const int fin = meta->sort.final_buf;
   const int* __restrict__ order = fin ? p1 : p0;
   const int b = seg_start[seg], e = seg_start[seg + 1];
   const int first = order[b];
@@ -367,7 +250,7 @@ __global__ __launch_bounds__(256) void pool_best_kernel(const PoolMeta* __restri
   if (meta->T != t) return;                     // as pool_reduce_kernel: nothing into buffers of a wrong size
   const int64_t seg = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (seg >= t) return;
-  const int fin = meta->final_buf;
+  const int fin = meta->sort.final_buf;
   const int* __restrict__ order = fin ? p1 : p0;
   const int b = seg_start[seg], e = seg_start[seg + 1];
   float best = __builtin_nanf("");
@@ -434,7 +317,7 @@ struct dif_pool {
   PoolMeta* meta = nullptr;
   unsigned long long* keys[2] = {nullptr, nullptr};
   int* pos[2] = {nullptr, nullptr};
-  unsigned* hist = nullptr;      // [256][blocks of kSortTile]
+  unsigned* hist = nullptr;      // the sort's histogram
   unsigned* block_heads = nullptr;
   int* seg_start = nullptr;      // [T + 1]
   bool grouped = false;          // the workspace holds the order of a group ...
@@ -443,20 +326,15 @@ struct dif_pool {
   hipEvent_t t_event = nullptr;
 };
 
-static size_t pool_carve(dif_pool* p, int64_t m, int64_t nb, int64_t nhb) {
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p->ws ? p->ws + at : nullptr;
-    at += (bytes + 255) & ~(size_t)255;
-    return q;
-  };
-  p->meta = (PoolMeta*)take(sizeof(PoolMeta));
-  for (int i = 0; i < 2; ++i) p->keys[i] = (unsigned long long*)take((size_t)m * 8);
-  for (int i = 0; i < 2; ++i) p->pos[i] = (int*)take((size_t)m * 4);
-  p->hist = (unsigned*)take((size_t)nb * 256 * 4);
-  p->block_heads = (unsigned*)take((size_t)nhb * 4);
-  p->seg_start = (int*)take((size_t)(m + 1) * 4);
-  return at;
+static size_t pool_carve(dif_pool* p, int64_t m, int64_t nhb) {
+  Carver c(p->ws);
+  p->meta = (PoolMeta*)c.take(sizeof(PoolMeta));
+  for (int i = 0; i < 2; ++i) p->keys[i] = (unsigned long long*)c.take((size_t)m * 8);
+  for (int i = 0; i < 2; ++i) p->pos[i] = (int*)c.take((size_t)m * 4);
+  p->hist = (unsigned*)c.take(radix_sort_hist_bytes(m > 0 ? m : 1));
+  p->block_heads = (unsigned*)c.take((size_t)nhb * 4);
+  p->seg_start = (int*)c.take((size_t)(m + 1) * 4);
+  return c.at;
 }
 
 static bool misaligned16(const void* q) { return ((uintptr_t)q & 15) != 0; }
@@ -499,27 +377,21 @@ int dif_pool_group(dif_pool* p, const int64_t* state_labels_dev, int64_t t0, con
   hipStream_t st = (hipStream_t)stream;
   p->grouped = false;
   const int64_t m = t0 + n;
-  const int64_t nb = m > 0 ? (m + kSortTile - 1) / kSortTile : 1;
+  const int64_t nb = m > 0 ? (m + radix_sort_tile() - 1) / radix_sort_tile() : 1;   // blocks of a sort pass
   const int64_t nhb = (m + 1 + kHeadBlock - 1) / kHeadBlock;
   if (nb * 256 > 0x7fffffff) return set_error("dif_pool_group: sizes out of range");
   dif_pool probe;
-  const size_t need = pool_carve(&probe, m, nb, nhb);
+  const size_t need = pool_carve(&probe, m, nhb);
   if (grow(&p->ws, &p->ws_cap, need, 1)) return -1;
-  pool_carve(p, m, nb, nhb);
+  pool_carve(p, m, nhb);
   DIF_HIP(hipMemsetAsync(p->meta, 0, sizeof(PoolMeta), st));
   const unsigned flat = (unsigned)(m > 0 ? (nb < 2048 ? nb : 2048) : 1);
   hipLaunchKernelGGL(pool_stats_kernel, dim3(flat), dim3(256), 0, st, state_labels_dev, (int)t0, labels_dev, (int)m, p->meta);
   hipLaunchKernelGGL(pool_init_kernel, dim3(flat), dim3(256), 0, st, state_labels_dev, (int)t0, labels_dev, (int)m, p->meta, p->keys[0],
                      p->pos[0]);
-  for (int b = 0; b < 8 && m > 1; ++b) {
-    hipLaunchKernelGGL(pool_hist_kernel, dim3((unsigned)nb), dim3(kSortThreads), 0, st, p->meta, b, p->keys[0], p->keys[1], (int)m, (int)nb,
-                       p->hist);
-    hipLaunchKernelGGL(pool_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, &p->meta->active[b], p->hist, (int)(nb * 256));
-    hipLaunchKernelGGL(pool_scatter_kernel, dim3((unsigned)nb), dim3(kSortThreads), 0, st, p->meta, b, p->keys[0], p->keys[1], p->pos[0],
-                       p->pos[1], (int)m, (int)nb, p->hist);
-  }
+  if (m > 1 && radix_sort_run(&p->meta->sort, 8, p->keys[0], p->keys[1], p->pos[0], p->pos[1], m, p->hist, st)) return -1;
   hipLaunchKernelGGL(pool_heads_kernel, dim3((unsigned)nhb), dim3(kHeadBlock), 0, st, p->meta, p->keys[0], p->keys[1], (int)m, p->block_heads);
-  hipLaunchKernelGGL(pool_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const int*)nullptr, p->block_heads, (int)nhb);
+  if (block_scan_run(p->block_heads, nhb, st)) return -1;
   hipLaunchKernelGGL(pool_index_kernel, dim3((unsigned)nhb), dim3(kHeadBlock), 0, st, p->meta, p->keys[0], p->keys[1], p->pos[0], p->pos[1],
                      (int)m, (int)t0, p->block_heads, p->seg_start, index_out_dev, t_out_dev);
   DIF_HIP(hipGetLastError());

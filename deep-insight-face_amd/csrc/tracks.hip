@@ -1,5 +1,5 @@
 // hipcc-flags: -ffp-contract=off
-// (box_iou and ref_distance below restate float32 arithmetic operation by operation: a product is rounded before it is
+// (box_iou of box_iou.hpp and ref_distance restate float32 arithmetic operation by operation: a product is rounded before it is
 // added, and match_ref.hpp asks for this flag of every translation unit that includes it)
 // Tracks: the faces of a sequence of frames linked into tracks (include/dif.h, "tracks").
 //   tracks_cand_kernel    one block per (face j, gap g): the faces of frame f - g are the tails j may continue.  Lane p
@@ -18,6 +18,8 @@
 // Frames are numbered over the state and the call together: state slot s holds frame s (0 .. G - 1), `pad` empty frames
 // follow (batches without a face that the caller skipped), and frame n of the call is frame G + pad + n.
 #include "../../include/dif.h"
+#include "box_iou.hpp"
+#include "frame_rows.hpp"
 #include "gemm_core.hpp"
 #include "match_ref.hpp"
 
@@ -74,15 +76,6 @@ __device__ __forceinline__ TrackState track_state_in(const TrackSeq& q) {
   return s;
 }
 
-// rows [begin, end) of frame n of the call, whatever `offsets` holds: never outside [0, m]
-__device__ __forceinline__ void track_frame_rows(const TrackSeq& q, int64_t n, int64_t* begin, int64_t* end) {
-  int64_t b = q.offsets[n], e = q.offsets[n + 1];
-  b = b < 0 ? 0 : (b > q.m ? q.m : b);
-  e = e < b ? b : (e > q.m ? q.m : e);
-  *begin = b;
-  *end = e;
-}
-
 // The face at position p of frame cf as an index over [the state's G * Ks slots][the call's m rows], or -1: no such
 // frame, no such face, or a clipped one.
 __device__ __forceinline__ int64_t track_tail(const TrackSeq& q, int64_t cf, int p) {
@@ -91,22 +84,8 @@ __device__ __forceinline__ int64_t track_tail(const TrackSeq& q, int64_t cf, int
   const int64_t n = cf - q.G - q.pad;
   if (n < 0 || n >= q.n_frames || p >= q.kmax) return -1;
   int64_t b, e;
-  track_frame_rows(q, n, &b, &e);
+  frame_rows(q.offsets, n, q.m, &b, &e);
   return p < e - b ? (int64_t)q.G * q.Ks + b + p : -1;
-}
-
-// box_iou of csrc/detector.hip, restated: the min / max corner normalisation pairs element 0 with 2 and 1 with 3, so it
-// serves left, top, right, bottom as it serves y0, x0, y1, x1; every product and sum is rounded on its own.
-__device__ __forceinline__ float track_iou(const float* p, const float* q) {
-#pragma clang fp contract(off)
-  const float py0 = fminf(p[0], p[2]), py1 = fmaxf(p[0], p[2]), px0 = fminf(p[1], p[3]), px1 = fmaxf(p[1], p[3]);
-  const float qy0 = fminf(q[0], q[2]), qy1 = fmaxf(q[0], q[2]), qx0 = fminf(q[1], q[3]), qx1 = fmaxf(q[1], q[3]);
-  const float ap = (py1 - py0) * (px1 - px0), aq = (qy1 - qy0) * (qx1 - qx0);
-  if (ap <= 0.f || aq <= 0.f) return 0.f;
-  const float ih = fmaxf(fminf(py1, qy1) - fmaxf(py0, qy0), 0.f);
-  const float iw = fmaxf(fminf(px1, qx1) - fmaxf(px0, qx0), 0.f);
-  const float inter = ih * iw;
-  return inter / (ap + aq - inter);
 }
 
 __global__ __launch_bounds__(256) void tracks_cand_kernel(const TrackSeq q, const float* __restrict__ boxes, const float* __restrict__ emb,
@@ -117,14 +96,9 @@ __global__ __launch_bounds__(256) void tracks_cand_kernel(const TrackSeq q, cons
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t j = blockIdx.x / q.G;
   const int g = (int)(blockIdx.x - j * q.G) + 1;
-  // the frame of row j: the last n with offsets[n] <= j
-  int64_t lo = 0, hi = q.n_frames;              // offsets[lo] <= j < offsets[hi] (offsets[0] = 0, offsets[N] = m)
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (q.offsets[mid] <= j) lo = mid; else hi = mid;
-  }
+  const int64_t lo = frame_bisect(q.offsets, q.n_frames, j);   // the frame of row j (offsets[0] = 0, offsets[N] = m)
   int64_t b, e;
-  track_frame_rows(q, lo, &b, &e);
+  frame_rows(q.offsets, lo, q.m, &b, &e);
   if (j < b || j >= e || j - b >= q.kmax) return;           // (uniform over the block) a clipped face: its slots are never read
   const int64_t cf = q.G + q.pad + lo;
   const int64_t c = lane < q.K ? track_tail(q, cf - g, lane) : -1;
@@ -132,7 +106,7 @@ __global__ __launch_bounds__(256) void tracks_cand_kernel(const TrackSeq q, cons
   bool pass = false;
   if (c >= 0) {
     const float* tb = c < Sn ? track_state_in(q).boxes + c * 4 : boxes + (c - Sn) * 4;
-    pass = track_iou(tb, boxes + j * 4) >= min_iou;         // (a NaN IoU compares false)
+    pass = box_iou(tb, boxes + j * 4) >= min_iou;           // (a NaN IoU compares false)
   }
   const unsigned long long mask = __ballot(pass);
   float* __restrict__ row = cand + (j * q.G + (q.G - g)) * q.K;
@@ -221,7 +195,7 @@ __global__ __launch_bounds__(kWalkThreads) void tracks_walk_kernel(const TrackSe
   if (tid < q.pad) ring_cnt[(G + tid) % G] = 0;   // the frames the caller skipped (pad <= G)
   int links = 0, clipped = 0, faces = 0;        // (faces: the rows the frames cover -- m when offsets is what dif.h asks for)
   const int N = (int)q.n_frames, M = (int)q.m;
-  // track_frame_rows' clamps, in ints: offsets[n + 1] closes frame n and opens the next, offsets[n + 2] is requested a frame ahead
+  // frame_rows' clamps, in ints: offsets[n + 1] closes frame n and opens the next, offsets[n + 2] is requested a frame ahead
   auto clamped = [&](int64_t v) { return (int)(v < 0 ? 0 : (v > M ? M : v)); };
   int off_e = N > 0 ? clamped(q.offsets[0]) : 0, off_next = N > 0 ? clamped(q.offsets[1]) : 0;
   for (int n = 0; n < N; ++n) {
@@ -360,7 +334,13 @@ __global__ __launch_bounds__(256) void tracks_state_kernel(const TrackSeq q, con
 
 using namespace dif;
 
-static size_t track_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// the workspace: the candidate table [m][G * K] and the closed flags [state slots][rows of the call]
+static size_t track_carve(void* base, int64_t m, int G, int K, int Ks, float** cand, int** closed) {
+  Carver c(base);
+  *cand = (float*)c.take((size_t)m * G * K * 4);
+  *closed = (int*)c.take(((size_t)G * Ks + (size_t)m) * 4);
+  return c.at;
+}
 
 static int track_check_shape(const char* fn, int max_gap, int k, int d) {
   if (max_gap < 1 || max_gap > kTrackGap) return set_error("%s: max_gap %d outside [1, %d]", fn, max_gap, kTrackGap);
@@ -382,7 +362,9 @@ int64_t dif_tracks_workspace_size(int64_t m, int max_gap, int kmax, int state_k)
   if (state_k != 0 && track_check_shape("dif_tracks_workspace_size", max_gap, state_k, 1)) return -1;
   if (track_check_shape("dif_tracks_workspace_size", max_gap, kmax, 1)) return -1;
   const int K = kmax > state_k ? kmax : state_k;
-  return (int64_t)(track_align((size_t)m * max_gap * K * 4) + track_align(((size_t)max_gap * state_k + (size_t)m) * 4));
+  float* cand;
+  int* closed;
+  return (int64_t)track_carve(nullptr, m, max_gap, K, state_k, &cand, &closed);
 }
 
 int dif_tracks_link(const int64_t* offsets_dev, const float* boxes_dev, const float* emb_dev, int64_t n_frames, int64_t m, int d,
@@ -430,8 +412,9 @@ int dif_tracks_link(const int64_t* offsets_dev, const float* boxes_dev, const fl
   q.K = kmax > state_k_in ? kmax : state_k_in;
   q.state = state_in_dev;
   q.d = d;
-  float* cand = (float*)workspace_dev;
-  int* closed = (int*)((char*)workspace_dev + track_align((size_t)m * max_gap * q.K * 4));
+  float* cand;
+  int* closed;
+  track_carve(workspace_dev, m, max_gap, q.K, state_k_in, &cand, &closed);
   if (m > 0 && (passes & DIF_TRACKS_PASS_CAND))
     hipLaunchKernelGGL(tracks_cand_kernel, dim3((unsigned)(m * max_gap)), dim3(256), 0, st, q, boxes_dev, emb_dev, d, tolerance, min_iou, metric,
                        plan, cand);

@@ -10,6 +10,7 @@ the same bits."""
 import ctypes
 import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -116,6 +117,35 @@ def test_scan_sizes(cuda, m):
     for q in range(len(thr)):
         N.check(N.lib.dif_det_ap(N.ptr(res.recall[q]), N.ptr(res.precision[q]), m, N.ptr(out), N.stream_ptr()))
         assert _same_bits(out.cpu().numpy(), got['ap'][q:q + 1])
+
+
+def _sort_const(name):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, 'deep-insight-face_amd', 'csrc', 'radix_sort.hip')).read()
+    return int(re.search(r'constexpr int %s = (\d+);' % name, src).group(1))
+
+
+SORT_SHARE = _sort_const('kSortItems') * 64                                # keys of a tile that one wave ranks, 64 per round
+SORT_TILE = _sort_const('kSortThreads') * _sort_const('kSortItems')        # keys per block of the radix sort
+
+
+@pytest.mark.parametrize('m', [SORT_SHARE - 1, SORT_SHARE, SORT_SHARE + 1, SORT_TILE - 1, SORT_TILE, SORT_TILE + 1])
+def test_sort_sizes(cuda, m):
+    """M one below, at and one above a wave's share of the sort's tile and the tile itself (csrc/radix_sort.hip, 32-bit keys):
+    the last key alone in the next wave's counters, and alone in the next block.  The order is stable only if equal scores keep
+    their rows' order across every hand-off of the ranking -- a wave's rounds of 64, the waves' shares, the blocks' tiles -- so
+    the input must hold equal scores on both sides of each hand-off that M reaches; that is asserted before the device is asked."""
+    case, thr = _sized(m), (0.5, 0.75)
+    scores = case['det_scores']
+    assert len(scores) == m
+    for unit in (64, SORT_SHARE, SORT_TILE):
+        if m > unit:
+            part = np.arange(m) // unit
+            assert any(len(np.unique(part[scores == v])) > 1 for v in np.unique(scores)), (m, unit, 'no equal scores across this hand-off')
+    got = _check(_evaluate(case, thr, cuda), _want('sized_%d' % m, thr), m)
+    again = _np(_evaluate(case, thr, cuda))
+    for k in FIELDS + ('ap',):
+        assert _same_bits(got[k], again[k]), (m, k)
 
 
 @pytest.mark.parametrize('name,chunks', [('seeded', [37]), ('seeded', [30, 7]), ('seeded', [3, 1, 20, 6, 7]), ('crowd', [2, 2]),
